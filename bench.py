@@ -12,6 +12,12 @@ group is used for the barrier and the max-over-ranks time only.
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, primes, warms up, times ONE block of exactly K steps and prints the result line.  --full adds what
+is measured beside the headline: ten timed blocks (their median is then the headline), the cold block, the stage-event,
+latency and sustained passes, the roofline block and the CPU baseline.  --dump-outputs DIR writes what the last timed
+step returned (U, trajectory cost, per-rollout costs and weights, the slid control sequence and history) as DIR/*.npy;
+the timed steps start from the new handle's seed, controls and history, so the arrays are the same run after run.
 """
 import argparse
 import json
@@ -110,6 +116,35 @@ def init_dist(backend, devices=None, force=False):
     else:
         dist.init_process_group(backend=backend)
     return rank, device, world, dist
+
+
+DUMP_MAX_PER_ARRAY = 1 << 19  # elements kept of a per-rollout vector: 2 MB in f32, 8 ranks x 2 vectors stay under 64 MB
+
+
+def last_step_outputs(sol, cuda):
+    """What a caller of the timed path holds after its last step: mppi_get_results of the solve (U, trajectory cost,
+    per-rollout costs and weights of the last iteration) and the control sequence and history after the slide."""
+    if not cuda:  # the --selftest-cpu stand-in keeps the control sequence and history only
+        return {"control_seq": sol.get_control_seq(), "control_hist": sol.hist}
+    r = sol.get_results()
+    return {"U": r["U"], "traj_cost": np.array([r["traj_cost"]], np.float32), "costs": r["costs"], "weights": r["w"],
+            "control_seq": sol.get_control_seq(), "control_hist": sol.get_control_hist()}
+
+
+def dump_outputs(directory, outputs, prefix=""):
+    """DIR/<prefix><name>.npy per array (f32 / f64 only).  A per-rollout vector longer than DUMP_MAX_PER_ARRAY is cut to a
+    fixed, seeded sample of its entries, the same for every vector of that length; the indices go beside it as
+    <prefix>sample_index_<length>.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.ndim == 1 and a.size > DUMP_MAX_PER_ARRAY:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_MAX_PER_ARRAY, replace=False))
+            np.save(os.path.join(directory, "%ssample_index_%d.npy" % (prefix, a.size)), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
 
 
 def pin_to_gpu_numa(device):
@@ -301,16 +336,23 @@ def main():
                     help="timed steps inside one library call (mppi_control_ticks) or one ctypes call per ABI call")
     ap.add_argument("--prime-ms", type=float, default=250.0,
                     help="initialisation before the warm-up steps: solves repeated for this long (clock ramp, code load)")
-    ap.add_argument("--repeats", type=int, default=10,
-                    help="timed blocks of --steps steps each; their MEDIAN is the reported value / ms_per_step (SURVEY 8d), "
-                         "the first block alone is first_block_ms_per_step, min / max are extra keys")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline: --repeats blocks, the cold block, the stage-event, "
+                         "latency and sustained passes, the roofline block and the CPU baseline (a plain run times one block)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (f32; a per-rollout vector "
+                         "beyond %d entries as a fixed, seeded sample); more than one rank: DIR/rank<r>_<name>.npy"
+                         % DUMP_MAX_PER_ARRAY)
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps each (default 1; 10 with --full); their MEDIAN is the reported value / "
+                         "ms_per_step (SURVEY 8d), the first block alone is first_block_ms_per_step, min / max are extra keys")
     ap.add_argument("--latency-solves", type=int, default=200,
-                    help="separate pass after the timed region: steps timed one by one (median solve latency)")
+                    help="--full: separate pass after the timed region: steps timed one by one (median solve latency)")
     ap.add_argument("--event-solves", type=int, default=64,
-                    help="separate pass after the timed region: solves with HIP events around every stage")
+                    help="--full: separate pass after the timed region: solves with HIP events around every stage")
     ap.add_argument("--sustained-s", type=float, default=2.0,
-                    help="separate pass after the timed region: the step repeated for this many seconds (sustained rate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: separate pass after the timed region: the step repeated for this many seconds (sustained rate)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-chain", action="store_true",
                     help="A/B: mppi_control_ticks launches every solve when its turn comes instead of one tick ahead "
                          "(mppi_debug_set_chained_ticks(0))")
@@ -325,6 +367,10 @@ def main():
     ap.add_argument("--devices", type=str, default="",
                     help="rank -> device map, e.g. '0,0' (default: device = LOCAL_RANK)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        raise SystemExit("--steps and --repeats must be >= 1, --warmup >= 0")
 
     selftest = args.selftest_cpu
     backend = "gloo" if selftest else args.dist_backend
@@ -408,10 +454,10 @@ def main():
     # that code objects are loaded, allocations are settled and the GPU has left its idle clock state (a
     # fresh process starts at the idle shader clock and the W = 5 steps the driver asks for last 0.4 ms).
     # A controller runs for minutes at 50 Hz; the steady state is the quantity of interest.  Reported below.
-    # Before any of that, the contract read literally: W warm-up steps on the fresh process, then the K timed steps --
+    # --full: before any of that, the contract read literally: W warm-up steps on the fresh process, then the K timed steps --
     # reported as the extra key "cold" beside the primed figure (the first solves of a process run at the idle shader clock).
     cold_s = None
-    if cuda and args.prime_ms > 0:
+    if args.full and cuda and args.prime_ms > 0:
         run_steps(args.warmup)
         cold_s = timed_block()
         local_s.clear()
@@ -421,15 +467,24 @@ def main():
         run_steps(20)
         n_prime += 20
     sync()
+    if cuda:
+        # the priming pass runs for a wall-clock time, so the number of solves behind it varies: the handle goes back to
+        # where mppi_create left it (generator at the workload's seed, offset 0; initial controls; zero history), and the
+        # warm-up and timed steps see the same inputs in every run
+        sol.seed(cfg.get("seed", 1234), 0)
+        sol.reset_controls()
+        sol.set_control_hist(np.zeros(4, np.float32))
     run_steps(args.warmup)
     # the contract's timed region: no event records, no per-step host timing inside it
     elapsed = timed_block()
-    # the same block repeated (off the headline number): spread of the measurement
-    block_s = [elapsed] + [timed_block() for _ in range(max(0, args.repeats - 1))]
+    # --full: the same block repeated (the median of the blocks is then the headline): spread of the measurement
+    block_s = [elapsed] + [timed_block() for _ in range(args.repeats - 1)]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step_outputs(sol, cuda), "" if world == 1 else "rank%d_" % rank)
     # separate pass 1, directly behind the timed blocks (the GPU in the state they ran in: behind the 2 s sustained pass the
     # same kernel measures ~12 % longer): HIP events around the stages of every solve (they lengthen the launch gaps, so
     # they stay out of the timed region); the rollout kernel's duration feeds the roofline block
-    if cuda:
+    if args.full and cuda:
         sol.enable_stage_timing(1)
         sol.reset_stage_times()
         run_steps(args.event_solves)
@@ -438,7 +493,7 @@ def main():
         sol.enable_stage_timing(0)
     # separate pass 2: every step timed on its own (one ctypes call per ABI call): median solve latency
     per_solve_ms = None
-    if cuda and rank == 0 and args.latency_solves > 0:
+    if args.full and cuda and rank == 0 and args.latency_solves > 0:
         lat = []
         for _ in range(args.latency_solves):
             t1 = time.perf_counter()
@@ -450,7 +505,7 @@ def main():
     # separate pass 3: a sustained run (off the headline number): the same step for --sustained-s seconds of wall time --
     # what a controller that runs for minutes sees, and long enough for a utilisation sampler to catch the GPU at work
     sustained = None
-    if cuda and args.sustained_s > 0:
+    if args.full and cuda and args.sustained_s > 0:
         sync()
         n_s, t_s = 0, time.perf_counter()
         while time.perf_counter() - t_s < args.sustained_s:
@@ -465,7 +520,7 @@ def main():
 
     # what every rank ran (proves the instances are distinct), gathered off the timed region
     own_roofline = None
-    if cuda:
+    if args.full and cuda:
         # this rank's rollout kernel against the roofline (north_star: "rollouts/s and achieved HBM GB/s vs. the roofline" at
         # 1 / 2 / 4 / 8 GPUs): its own stage events, the algorithmic bytes and flop of its own launch
         st_ = stage_times
@@ -505,11 +560,13 @@ def main():
             "value": value, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * typical / args.steps,
             "first_block_ms_per_step": 1e3 * elapsed / args.steps,
-            "value_basis": "median of %d timed blocks of exactly %d steps each; a block = barrier + synchronize, the steps, "
+            "value_basis": "%s; a block = barrier + synchronize, the steps, "
                            "synchronize on every rank, timed on every rank, MAX over ranks of the ranks' own times (one all-reduce "
                            "after the block); the closing barrier of the contract is executed behind every block and is NOT inside "
                            "the figure: the bracket closed behind it is ms_per_step_incl_closing_barrier; the first block alone: "
-                           "first_block_ms_per_step" % (len(block_s), args.steps),
+                           "first_block_ms_per_step" % ("one timed block of exactly %d steps" % args.steps if len(block_s) == 1 else
+                                                        "median of %d timed blocks of exactly %d steps each" % (len(block_s), args.steps)),
+            "full": args.full,
             "ms_per_step_incl_closing_barrier": 1e3 * float(np.median(incl_s)) / args.steps,
             "blocks_ms_per_step": [1e3 * x / args.steps for x in block_s],
             "blocks_ms_per_step_incl_closing_barrier": [1e3 * x / args.steps for x in incl_s],
@@ -525,7 +582,8 @@ def main():
                        "timed_loop": (("native (mppi_control_ticks%s)" % ("" if not args.no_chain else ", chain off")) if native
                                       else "python (one ctypes call per ABI call)"),
                        "host_affinity": affinity if cuda else "unchanged",
-                       "priming": "%d untimed solves (%.0f ms) before the %d warm-up steps" % (n_prime, args.prime_ms, args.warmup),
+                       "priming": "%d untimed solves (%.0f ms), then seed, controls and history back to the new handle's, "
+                                  "before the %d warm-up steps" % (n_prime, args.prime_ms, args.warmup),
                        "parallelism": "replicas x%d (no collective)" % world,
                        "process_group": backend if dist is not None else "none"},
             "state_updates_per_s": value * T,
@@ -542,7 +600,7 @@ def main():
             "sustained": sustained,
             "instances": instances,
         }
-        if cuda:
+        if args.full and cuda:
             st = stage_times
             n = max(1, st["n_solves"])
             rollout_s = st["rollout_ms"] * 1e-3 / n / iters

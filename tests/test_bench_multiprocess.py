@@ -24,7 +24,7 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--K", "128", "--T", "20", "--selftest-cpu"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--K", "128", "--T", "20", "--selftest-cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -63,7 +63,7 @@ def test_bench_two_ranks_real_solver_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29613", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "20", "--warmup", "5", "--dist-backend", "gloo", "--devices", "0,0",
-           "--repeats", "3", "--latency-solves", "20", "--event-solves", "8", "--prime-ms", "50"]
+           "--full", "--repeats", "3", "--latency-solves", "20", "--event-solves", "8", "--prime-ms", "50"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -112,7 +112,7 @@ def test_bench_four_ranks_real_solver_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", "29619", os.path.join(ROOT, "bench.py"),
            "--gpus", "4", "--steps", "10", "--warmup", "3", "--dist-backend", "gloo", "--devices", "0,0,0,0",
-           "--repeats", "2", "--latency-solves", "0", "--event-solves", "4", "--prime-ms", "20", "--sustained-s", "0"]
+           "--full", "--repeats", "2", "--latency-solves", "0", "--event-solves", "4", "--prime-ms", "20", "--sustained-s", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -138,7 +138,7 @@ def test_bench_rccl_process_group_smoke_at_world_size_one():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29621", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3",
-           "--force-process-group", "--dist-backend", "nccl", "--repeats", "2", "--latency-solves", "0", "--event-solves", "4",
+           "--force-process-group", "--dist-backend", "nccl", "--full", "--repeats", "2", "--latency-solves", "0", "--event-solves", "4",
            "--prime-ms", "20", "--sustained-s", "0", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

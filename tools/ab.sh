@@ -3,6 +3,7 @@
 # Same-box A/B of two builds of libmppi_hip.so (MPPI_LIB_PATH override of autorally_amd/capi.py),
 # alternating A, B, A, B ... so that clock drift of the box hits both arms alike.
 tag=$1; A=$2; B=$3; n=$4; shift 4
+set -- --full "$@"  # the lines below read stage_ms: a --full run
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/$tag
 for i in $(seq 1 $n); do

@@ -2,6 +2,7 @@
 # tools/abn.sh <out-tag> <rounds> "<lib1.so> <lib2.so> ..." <bench.py arguments...>: same-box comparison of several
 # builds of libmppi_hip.so, interleaved round-robin (see tools/ab.sh)
 tag=$1; n=$2; libs=$3; shift 3
+set -- --full "$@"  # the lines below read stage_ms: a --full run
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/$tag
 for i in $(seq 1 $n); do

@@ -9,7 +9,7 @@ ap.add_argument("--steps", type=int, default=50)
 a = ap.parse_args()
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for K in a.K.split(","):
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--repeats", "3", "--latency-solves", "0",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--repeats", "3", "--latency-solves", "0",
            "--K", K, "--T", str(a.T), "--steps", str(a.steps), "--warmup", "5", "--variant", a.variant]
     if a.layers:
         cmd += ["--layers", a.layers]

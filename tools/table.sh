@@ -5,6 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/table
 row() {  # tag, then bench.py arguments
   tag=$1; shift
+  set -- --full "$@"  # stage_ms, roofline, per_solve_ms and cpu_baseline are --full's
   python3 bench.py "$@" > gpurun_out/table/$tag.json 2> gpurun_out/table/$tag.err || { echo "$tag FAILED"; tail -3 gpurun_out/table/$tag.err; return; }
   python3 - <<PY
 import json

@@ -9,6 +9,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/tail_ab
 row() {  # tag, form, then bench.py arguments
   tag=$1; form=$2; shift; shift
+  set -- --full "$@"  # the line below reads stage_ms: a --full run
   lib=""; [ -f tools/variants/$form.so ] && lib=$PWD/tools/variants/$form.so  # a form that is a variant build (tools/build_variant.sh)
   MPPI_LIB_PATH=$lib MPPI_TAIL_FORM=$form python3 bench.py --no-cpu-baseline "$@" > gpurun_out/tail_ab/$tag.$form.json 2> gpurun_out/tail_ab/$tag.$form.err || { echo "$tag $form FAILED"; tail -3 gpurun_out/tail_ab/$tag.$form.err; return; }
   python3 - <<PY
