@@ -65,6 +65,7 @@ SYMBOLS = [
     "mppi_debug_inject_handover_fault", "mppi_compute_feedback_gains_pair", "mppi_set_host_threads",
     "mppi_debug_capture_iterations", "mppi_debug_get_iterations", "mppi_set_wait_timeout", "mppi_debug_form_candidates",
     "mppi_debug_set_chained_ticks", "mppi_debug_min_cost",
+    "mppi_arm", "mppi_arm_batch", "mppi_disarm", "mppi_is_armed",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -72,7 +73,8 @@ ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi
                 "mppi_nominal_traj_pair")
 ABI3_SYMBOLS = ("mppi_compute_feedback_gains_pair", "mppi_set_host_threads")
 ABI4_SYMBOLS = ("mppi_debug_capture_iterations", "mppi_debug_get_iterations", "mppi_set_wait_timeout", "mppi_debug_form_candidates")
-ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost")
+ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost", "mppi_arm", "mppi_arm_batch", "mppi_disarm",
+                "mppi_is_armed")
 
 _lib = None
 
@@ -161,6 +163,10 @@ def lib():
         if v5:
             L.mppi_debug_set_chained_ticks.argtypes = [hp, C.c_int]
             L.mppi_debug_min_cost.argtypes = [hp, C.c_int, C.POINTER(C.c_int)]
+            L.mppi_arm.argtypes = [hp, C.c_double]
+            L.mppi_arm_batch.argtypes = [C.POINTER(hp), C.c_int, C.c_double]
+            L.mppi_disarm.argtypes = [hp]
+            L.mppi_is_armed.argtypes = [hp]
         for s in SYMBOLS:  # every declared symbol of the library's ABI version must be there
             if (v2 or s not in ABI2_SYMBOLS) and (v3 or s not in ABI3_SYMBOLS) and (v4 or s not in ABI4_SYMBOLS) and \
                     (v5 or s not in ABI5_SYMBOLS):
@@ -341,6 +347,18 @@ class Solver:
         self._ck(self.L.mppi_debug_min_cost(self.h, int(on), C.byref(got)))
         return bool(got.value)
 
+    def arm(self, max_wait_s=0.01):
+        """mppi_arm: enqueue the next solve now, gated; the next compute_control[_async] opens it with its state.
+        Raises MppiError (status ERR_UNSUPPORTED) where the handle's form / configuration has no gated form."""
+        self._ck(self.L.mppi_arm(self.h, float(max_wait_s)))
+
+    def disarm(self):
+        """mppi_disarm: call the armed solve off (never blocks on the GPU)."""
+        self._ck(self.L.mppi_disarm(self.h))
+
+    def is_armed(self):
+        return bool(self.L.mppi_is_armed(self.h))
+
     def compute_control_async(self, state):
         self._ck(self.L.mppi_compute_control_async(self.h, _fp(_f32(state, (7,)))))
 
@@ -465,6 +483,16 @@ def compute_control_batch(solvers, states, blocking=True):
     if rc != OK:
         msgs = [s.L.mppi_last_error(s.h).decode() for s in solvers]
         raise MppiError(rc, "; ".join(m for m in msgs if m))
+
+
+def arm_batch(solvers, max_wait_s=0.01):
+    """mppi_arm_batch: arm the solves of the next compute_control_batch(solvers, ...) -- one gated launch where the batch is
+    one launch, else each solver on its own.  Raises MppiError (ERR_UNSUPPORTED) if a solver could not be armed."""
+    n = len(solvers)
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    rc = solvers[0].L.mppi_arm_batch(hs, n, float(max_wait_s))
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
 
 
 def control_ticks_batch(solvers, states, n_ticks, stride=1):

@@ -158,6 +158,7 @@ const char *mppi_rollout_variant(const mppi_handle *h)
 int mppi_set_rollout_variant(mppi_handle *h, const char *name)
 {
   if (!h || !name) return MPPI_ERR_INVALID;
+  DISARM(h);
   auto need = [&](bool ok, const char *what) { return ok ? MPPI_OK : fail(h, MPPI_ERR_UNSUPPORTED, what); };
   int rc = MPPI_OK;
   if (strcmp(name, "auto") == 0) {

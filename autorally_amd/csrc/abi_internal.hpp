@@ -151,6 +151,7 @@ struct mppi_handle {
   int explicit_iters = 0;  // >0: d_noise holds that many explicit iterations for the next solve
   bool pending = false;       // a solve is enqueued, results not yet collected
   bool pending_timed = false;
+  bool pending_armed = false;  // the pending solve is one that was armed (mppi_arm): wait_pending checks its rows too
   float traj_cost = 0.0f, baseline = 0.0f, eta = 0.0f;
 
   int spin_budget = 0, fault_wave = 0;  // mppi_debug_inject_handover_fault (0, 0: kSpinBudget, no fault)
@@ -166,6 +167,24 @@ struct mppi_handle {
   bool chain = true;   // mppi_debug_set_chained_ticks
   bool ahead = false;  // a gated solve is enqueued behind the pending one
   float *ahead_vbuf = nullptr;  // where that solve leaves its applied controls
+  // The gate block is double-buffered (gate_blk: the block of the latest gated solve; gate_host / gate_dev below): the tail of a
+  // gated solve still reads hist from its block after the host has seen its result, when the next gated solve's gate is written.
+  int gate_blk = 0;
+  // solve-ahead (mppi_arm, abi_solve.hip): the handle's NEXT solve is enqueued, gated, and waits for the next compute call
+  int armed = 0;                 // 0: not armed; 1: a latency form with its in-kernel generator; 2: the multi4-tree form with the
+                                 // prefetched generator kernel (abi_solve.hip: arm_kind)
+  unsigned arm_seq = 0;          // the armed solve's sequence number (its gate word)
+  unsigned seq_floor = 0;        // a called-off solve published under this number: every later solve takes a larger one
+  int arm_in = 0;                // d_in_buf the armed solve's tail smooths into (its slid copy: the other one)
+  float *arm_vbuf = nullptr;     // where the armed solve leaves its applied controls
+  int arm_n = 0;                 // > 0: armed in one launch together with arm_peers[0 .. arm_n) (mppi_arm_batch)
+  mppi_handle *arm_peers[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipStream_t arm_stream = nullptr;  // the stream the armed solve went to (the handle's own, or the device's batch stream)
+  hipEvent_t ev_arm = nullptr;   // recorded on arm_stream in front of the armed solve: readers of the last result wait for it alone
+  std::chrono::steady_clock::time_point arm_until;  // the host's deadline for opening the gate (a margin inside max_wait_s)
+  // the armed solve writes its costs and weights into the second pair (swapped in when its gate opens): the last result's
+  // vectors stay readable while it is armed, and a solve called off leaves them alone
+  float *d_costs_alt = nullptr, *d_w_alt = nullptr;
   bool timed_out = false;        // a wait ran out of time and that solve's device work may still run: recover_timed_out (abi_solve.hip)
   bool no_result = false;        // the last solve was lost (timeout): mppi_get_results refuses until a solve completes
   bool timing = false;
@@ -235,6 +254,19 @@ int recover_timed_out(mppi_handle *h);
 bool gen_beside_rollout(const mppi_handle *h);
 int own_stream(mppi_handle *h);
 void free_all(mppi_handle *h);
+
+// the gate block of the latest gated solve: the host's pointer and the kernels'; blocks lie gate_block_stride floats apart
+inline size_t gate_block_stride(int T) { return (gate_block_floats(T) + 63) & ~(size_t)63; }
+inline unsigned *gate_host(const mppi_handle *h) { return h->gate_cpu + (size_t)h->gate_blk * gate_block_stride(h->T); }
+inline const unsigned *gate_dev(const mppi_handle *h) { return h->d_gate + (size_t)h->gate_blk * gate_block_stride(h->T); }
+// abi_solve.hip: the armed solve is called off (its gate opened with the cancel bit; never blocks on the device); the handle's
+// generator stream is put back where it was.  Every call that changes what the armed solve would compute calls this first.
+int solve_ahead_disarm(mppi_handle *h);
+#define DISARM(h)                           \
+  do {                                      \
+    int rc__ = solve_ahead_disarm(h);       \
+    if (rc__) return rc__;                  \
+  } while (0)
 
 // where small follow-up work (upload of U, the slide kernel) goes: behind the handle's latest work, wherever it is
 inline hipStream_t work_stream(const mppi_handle *h) { return h->order_stream ? h->order_stream : h->stream; }

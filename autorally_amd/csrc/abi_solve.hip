@@ -77,6 +77,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.inline_noise = 0;
   a.gate = nullptr;
   a.gate_seq = 0;
+  a.gate_ticks = 10000000u;  // 100 ms (mppi_control_ticks); mppi_arm sets its own
   a.min_cost = nullptr;  // tag_min_cost
   a.min_cost_tag = 0;
   // roles 32-34 are waits of the streaming tail kernel (tail_launch): the rollout runs with its defaults
@@ -228,6 +229,14 @@ int prefetch_noise(mppi_handle *h)
   return MPPI_OK;
 }
 
+// the sequence number of the next solve: above every number a solve on this handle published under -- the last one, and a
+// solve called off (solve_ahead_disarm) whose tail kernel still publishes (poisoned) under its own
+static unsigned next_seq(mppi_handle *h)
+{
+  h->seq = (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
+  return h->seq;
+}
+
 int upload_controls_if_dirty(mppi_handle *h, hipStream_t stream)
 {
   if (!h->u_dirty) return MPPI_OK;
@@ -308,6 +317,7 @@ int wait_pending(mppi_handle *h)
   // offered, and nothing waits for this solve a second time (recover_timed_out)
   auto give_up = [&](const char *what, bool timed_out) {
     h->pending = false;
+    h->pending_armed = false;
     h->pending_timed = false;
     h->u_dirty = true;
     h->slid_valid = false;
@@ -340,21 +350,30 @@ int wait_pending(mppi_handle *h)
   h->baseline = h->h_res[4 * h->T + 0];
   h->eta = h->h_res[4 * h->T + 2];
   h->traj_cost = h->h_res[4 * (h->T + 1) + 0];
+  // The result block is checked BEFORE the host's copies of U take it: a poisoned or failed solve never reaches h->U (the next
+  // solve starts from the sequence the host held; the device copy, which that solve's tail smoothed, is not trusted).
+  // The minimum-cost rollout has weight 1 and costs are capped (never NaN), so eta >= 1 always.
+  // Anything else means a rollout wavefront gave up on a hand-over (its spin budget) and poisoned
+  // its costs: report it instead of returning a NaN control sequence.
+  const bool eta_ok = h->eta >= 1.0f;
+  bool rows_ok = true;
+  if (eta_ok && (tail_is_stream(h->K) || h->pending_armed)) {
+    // the one-launch tail of many-chunk solves: a row workgroup whose wait for another workgroup's granule ran out of time
+    // published NaN in place of what it waited for; a gated solve: its rows, whatever its tail
+    rows_ok = std::isfinite(h->traj_cost);
+    for (int t = 0; t < h->T && rows_ok; t++) rows_ok = std::isfinite(h->h_res[4 * t]) && std::isfinite(h->h_res[4 * t + 2]);
+  }
+  h->pending_armed = false;
+  if (!eta_ok || !rows_ok) {
+    h->u_dirty = true;
+    h->slid_valid = false;
+    return fail(h, MPPI_ERR_HIP, !eta_ok ? "solve produced a non-finite normaliser (device hand-over failed)"
+                                         : "solve produced non-finite controls (device hand-over failed)");
+  }
   savgol_host(h, h->h_res, 4, 2);  // rows [u0, seq, u1, seq] of the result block
 #ifdef MPPI_HOSTPROF
   HP(4, hp_seen);
 #endif
-  // The minimum-cost rollout has weight 1 and costs are capped (never NaN), so eta >= 1 always.
-  // Anything else means a rollout wavefront gave up on a hand-over (its spin budget) and poisoned
-  // its costs: report it instead of returning a NaN control sequence.
-  if (!(h->eta >= 1.0f)) return fail(h, MPPI_ERR_HIP, "solve produced a non-finite normaliser (device hand-over failed)");
-  if (tail_is_stream(h->K)) {
-    // the one-launch tail of many-chunk solves: a row workgroup whose wait for another workgroup's granule ran out of time
-    // published NaN in place of what it waited for
-    bool finite = std::isfinite(h->traj_cost);
-    for (size_t i = 0; i < h->U.size() && finite; i++) finite = std::isfinite(h->U[i]);
-    if (!finite) return fail(h, MPPI_ERR_HIP, "solve produced non-finite controls (device hand-over failed)");
-  }
   if (h->pending_timed) {
     h->pending_timed = false;
     for (size_t it = 0; it < h->ev.size(); it++) {
@@ -409,6 +428,9 @@ TailLaunch tail_launch(const mppi_handle *h, const float *V, bool last)
   return l;
 }
 
+static bool arm_usable(const mppi_handle *h);
+static int open_armed(mppi_handle *h, const float *state);
+
 int enqueue_solve(mppi_handle *h, const float *state)
 {
 #ifdef MPPI_HOSTPROF
@@ -421,6 +443,13 @@ int enqueue_solve(mppi_handle *h, const float *state)
   rc = recover_timed_out(h);
   if (rc) return rc;
   rc = wait_pending(h);  // finish a previous asynchronous solve first
+  if (h->armed) {
+    // armed (mppi_arm): this call opens the gate of the solve already enqueued -- unless the previous solve failed, the armed
+    // solve belongs to a batch, or its deadline has passed: then it is called off and this solve runs as if it never was
+    if (rc == MPPI_OK && h->arm_n == 0 && arm_usable(h)) return open_armed(h, state);
+    const int drc = solve_ahead_disarm(h);
+    if (rc == MPPI_OK) rc = drc;
+  }
   if (rc) return rc;
   const int K = h->K, T = h->T, iters = h->cfg.num_iters;
   if (h->explicit_iters > 0 && h->explicit_iters != iters)
@@ -431,7 +460,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
   const bool timed = h->timing && (h->timing_count++ % (unsigned)h->timing_every) == 0;
   const bool explicit_noise = h->explicit_iters > 0;
   const size_t slot_sz = (size_t)K * T * 2;
-  h->seq++;
+  next_seq(h);
   for (int it = 0; it < iters; it++) {
     Events *ev = timed ? &h->ev[it] : nullptr;
     if (ev) HIPCHK(h, hipEventRecord(ev->e[0], h->stream));
@@ -523,11 +552,11 @@ int enqueue_solve(mppi_handle *h, const float *state)
 // optimization stride.
 // 1: a latency form with riders and its in-kernel generator (the row form, the automatic m44 form); 2: the automatic multi4-tree
 // form with the stand-alone generator kernel prefetched on a second stream; 0: not chained
-static int chain_kind(const mppi_handle *h, int n_ticks, int stride)
+// (also the forms mppi_arm enqueues ahead: arm_kind)
+static int arm_kind(const mppi_handle *h)
 {
-  if (!(h->chain && n_ticks >= 2 && h->d_gate != nullptr && stride == h->cfg.optimization_stride && wants_slid_copy(h) &&
-        h->cfg.num_iters == 1 && !h->timing && !h->capture && h->explicit_iters == 0 && !h->basis && h->fault_wave == 0 &&
-        h->have_nn && h->have_map && h->have_cost && !h->timed_out))
+  if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
+        h->explicit_iters == 0 && !h->basis && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
     return 0;
   const Form f = form_of(h);
   if ((form_is_row(f) || f == Form::M44) && has_noise_wave(h) && !h->prefetch_valid) return 1;
@@ -536,6 +565,11 @@ static int chain_kind(const mppi_handle *h, int n_ticks, int stride)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;
   return 0;
 }
+static int chain_kind(const mppi_handle *h, int n_ticks, int stride)
+{
+  if (!(h->chain && n_ticks >= 2 && stride == h->cfg.optimization_stride)) return 0;
+  return arm_kind(h);
+}
 
 // the gate block of solve `word`: its nominal sequence and history (the host's copies, smoothed and slid), its state in every
 // replica, then (fenced) the gate word in every replica
@@ -543,7 +577,7 @@ static void write_gate(mppi_handle *h, const float *state, unsigned word)
 {
   // (memcpy: wide stores -- the block is write-combining memory behind the PCIe BAR where gate_bar is set; the fences order the
   // payload before the gate words and push both out)
-  unsigned *g = h->gate_cpu;
+  unsigned *g = gate_host(h);
   const int T = h->T;
   memcpy(g + kGateUOffset, h->U.data(), sizeof(float) * 2 * (size_t)T);
   memcpy(g + gate_hist_offset(T), h->hist.data(), sizeof(float) * 4);
@@ -576,18 +610,19 @@ static int enqueue_ahead(mppi_handle *h, const float *state, bool last_of_chain,
     rc = acquire_noise(h, &noise);
     if (rc) return rc;
   }
+  h->gate_blk ^= 1;  // this solve's gate block; the pending solve's tail may still read its own
   RolloutArgs a;
   fill_rollout_args(h, state, noise, a);
   rc = tag_min_cost(h, a, h->stream);
   if (rc) return rc;
-  a.U = reinterpret_cast<const float *>(h->d_gate) + kGateUOffset;
+  a.U = reinterpret_cast<const float *>(gate_dev(h)) + kGateUOffset;
   if (kind == 1) {
     a.inline_noise = 1;
     a.rng_in = h->d_rng[h->rng_cur];
     a.rng_out = h->d_rng[1 - h->rng_cur];
     h->rng_cur = 1 - h->rng_cur;
   }
-  a.gate = h->d_gate;
+  a.gate = gate_dev(h);
   a.gate_seq = h->seq + 1;
   rc = launch_rollout(h, a);
   if (rc) return rc;
@@ -595,7 +630,7 @@ static int enqueue_ahead(mppi_handle *h, const float *state, bool last_of_chain,
   if (++h->tail_epoch == 0) h->tail_epoch = 1;  // the tag of this tail launch's granules (many-chunk solves)
   TailLaunch l = tail_launch(h, noise, true);
   l.seq = h->seq + 1;
-  l.hist = reinterpret_cast<const float *>(h->d_gate) + gate_hist_offset(h->T);
+  l.hist = reinterpret_cast<const float *>(gate_dev(h)) + gate_hist_offset(h->T);
   if (last_of_chain) {
     l.U = h->d_in;
     l.hist_out = h->d_in + 2 * h->T;
@@ -664,6 +699,293 @@ static int control_ticks_chained(mppi_handle *h, const float *state, int n_ticks
   return MPPI_OK;
 }
 
+// ---- solve-ahead (mppi_arm) ------------------------------------------------------------------------------------------------
+// The chained ticks' mechanism for any caller: mppi_arm enqueues the handle's NEXT solve now, gated (enqueue_ahead's rollout and
+// the ordinary tail -- smoothing and the slid copy, as the last solve of a chain), behind a pending solve or on an idle stream.
+// Its kernels start, load their weights, draw their first noise and wait; the next mppi_compute_control[_async] does not launch:
+// it writes ITS state, the host's U and hist into the gate block and opens the gate.  Results are bit for bit those of the same
+// calls without mppi_arm.  What the armed solve changes before its gate opens is all undone by solve_ahead_disarm: its costs /
+// weights go to the second pair of vectors, its applied controls to the generator buffer nobody reads, its generator draw
+// (kind 1: the rng_cur flip; kind 2: the prefetched draws, regenerated) is put back, and the sequence number it publishes under is
+// never used again.  The device copy of [U | hist] is not kept up while armed (u_dirty: slides are the host's alone); the
+// armed tail rewrites both buffers, and the gate's opening points d_in at the one it smooths into.
+
+// max_wait_s in 100 MHz ticks; the host opens the gate only inside a margin of that (the kernels' clock starts when they do,
+// which is after the arming call): a gate opened in time is never one the kernels have given up on
+static unsigned arm_ticks(double max_wait_s) { return (unsigned)(max_wait_s * 1e8); }
+static std::chrono::steady_clock::time_point arm_deadline(double max_wait_s)
+{
+  const double open_s = 0.9 * max_wait_s - 50e-6;
+  return std::chrono::steady_clock::now() + std::chrono::nanoseconds((long long)((open_s > 0.0 ? open_s : 0.0) * 1e9));
+}
+
+// the armed solve's rollout and tail arguments (state: from the gate block)
+static void armed_args(mppi_handle *h, float *noise, RolloutArgs &a, TailLaunch &l, double max_wait_s)
+{
+  static const float no_state[kStateDim] = {0, 0, 0, 0, 0, 0, 0};
+  fill_rollout_args(h, no_state, noise, a);
+  a.costs = h->d_costs_alt;
+  a.U = reinterpret_cast<const float *>(gate_dev(h)) + kGateUOffset;
+  a.gate = gate_dev(h);
+  a.gate_seq = h->arm_seq;
+  a.gate_ticks = arm_ticks(max_wait_s);
+  l = tail_launch(h, noise, true);
+  l.costs = h->d_costs_alt;
+  l.w = h->d_w_alt;
+  l.seq = h->arm_seq;
+  l.hist = reinterpret_cast<const float *>(gate_dev(h)) + gate_hist_offset(h->T);
+  l.U = h->d_in;
+  l.hist_out = h->d_in + 2 * h->T;
+  l.slid = h->d_in_buf[1 - h->in_cur];
+}
+
+// the handle's bookkeeping once its armed solve is on a stream
+static void mark_armed(mppi_handle *h, int kind, float *vbuf, hipStream_t stream, double max_wait_s)
+{
+  h->armed = kind;
+  h->arm_in = h->in_cur;
+  h->arm_vbuf = vbuf;
+  h->arm_stream = stream;
+  h->arm_until = arm_deadline(max_wait_s);
+  h->arm_n = 0;
+  h->u_dirty = true;  // slides until the gate opens are the host's alone (a device slide would queue behind the gated kernel)
+  h->slid_valid = false;
+}
+
+static int arm_one(mppi_handle *h, double max_wait_s)
+{
+  const int kind = arm_kind(h);
+  if (!kind) return fail(h, MPPI_ERR_UNSUPPORTED, "this handle's form / configuration has no gated form (mppi_arm)");
+  HIPCHK(h, ensure_device(h->cfg.device));
+  OWN(h);  // behind a pending batched solve: the batch stream hands over first (as a solve on the handle's own stream does)
+  h->arm_seq = (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
+  h->gate_blk ^= 1;
+  float *noise = h->d_gen[1 - h->gen_cur];  // kind 1: the in-kernel generator's applied controls go to the buffer nobody reads
+  if (kind == 2) {
+    // the draws prefetched for this solve (or, if none are, generated now behind the stream's work); solve_ahead_disarm puts
+    // them back
+    int rc = acquire_noise(h, &noise);
+    if (rc) return rc;
+  }
+  HIPCHK(h, hipEventRecord(h->ev_arm, h->stream));
+  RolloutArgs a;
+  TailLaunch l;
+  armed_args(h, noise, a, l, max_wait_s);
+  int rc = tag_min_cost(h, a, h->stream);
+  if (rc) return rc;
+  l.min_cost_tag = h->min_cost_tag;
+  if (kind == 1) {
+    a.inline_noise = 1;
+    a.rng_in = h->d_rng[h->rng_cur];
+    a.rng_out = h->d_rng[1 - h->rng_cur];
+    h->rng_cur = 1 - h->rng_cur;
+  }
+  // from here on the handle is armed (a launch error below is called off like any armed solve)
+  mark_armed(h, kind, noise, h->stream, max_wait_s);
+  rc = launch_rollout(h, a);
+  if (rc == MPPI_OK) {
+    if (++h->tail_epoch == 0) h->tail_epoch = 1;
+    l.epoch = h->tail_epoch;
+    const hipError_t e = launch_solve_tail(l, h->stream);
+    if (e != hipSuccess) rc = fail(h, MPPI_ERR_HIP, "armed tail launch", e);
+  }
+  if (rc) (void)solve_ahead_disarm(h);
+  return rc;
+}
+
+// the gate of one armed handle is opened with the cancel bit; its generator stream goes back to where it was
+static int disarm_one(mppi_handle *h)
+{
+  if (!h->armed) return MPPI_OK;
+  const int kind = h->armed;
+  h->armed = 0;
+  h->arm_n = 0;
+  unsigned *g = gate_host(h);
+  for (int r = 0; r < kGateReplicas; r++) __atomic_store_n(g + 16 * r + 7, h->arm_seq | kGateCancel, __ATOMIC_RELAXED);
+  __builtin_ia32_sfence();
+  // its tail publishes (poisoned) under arm_seq and rewrites both device copies of [U | hist]
+  h->seq_floor = h->arm_seq;
+  h->u_dirty = true;
+  h->slid_valid = false;
+  h->order_stream = h->arm_stream;
+  if (kind == 1) {
+    h->rng_cur = 1 - h->rng_cur;  // the called-off kernel read rng_in and wrote the other buffer: the stream is where it was
+    return MPPI_OK;
+  }
+  // kind 2: its draws were consumed (and the called-off kernel may write its applied controls over them): drawn again from the
+  // generator state they came from, into the same buffer, once the called-off solve has ended -- as a prefetch
+  HIPCHK(h, ensure_device(h->cfg.device));
+  h->gen_cur = 1 - h->gen_cur;
+  h->rng_cur = 1 - h->rng_cur;
+  HIPCHK(h, hipEventRecord(h->ev_s1, h->arm_stream));
+  HIPCHK(h, hipStreamWaitEvent(h->gstream, h->ev_s1, 0));
+  int rc = launch_generator(h, h->d_gen[1 - h->gen_cur]);
+  if (rc) return rc;
+  h->prefetch_valid = true;
+  return MPPI_OK;
+}
+
+int solve_ahead_disarm(mppi_handle *h)
+{
+  if (!h || !h->armed) return MPPI_OK;
+  if (h->arm_n > 0) {  // armed in one launch with its partners: the launch is called off for all of them
+    mppi_handle *peers[kMaxBatch];
+    const int n = h->arm_n;
+    for (int i = 0; i < n; i++) peers[i] = h->arm_peers[i];
+    int rc = MPPI_OK;
+    for (int i = 0; i < n; i++) {
+      const int r = disarm_one(peers[i]);
+      if (r && !rc) rc = r;
+    }
+    return rc;
+  }
+  return disarm_one(h);
+}
+
+// may the armed solve's gate still be opened?  Inside the host's deadline, and its tail has not published (a gated kernel that
+// gave up -- or was called off -- publishes poisoned rows under its number)
+static bool arm_usable(const mppi_handle *h)
+{
+  if (std::chrono::steady_clock::now() >= h->arm_until) return false;
+  const volatile unsigned *words = reinterpret_cast<const volatile unsigned *>(h->h_res);
+  const unsigned s1 = __atomic_load_n(words + 1, __ATOMIC_ACQUIRE), s3 = __atomic_load_n(words + 4 * (h->T + 1) + 1, __ATOMIC_ACQUIRE);
+  return s1 != h->arm_seq && s3 != h->arm_seq;
+}
+
+// the compute call of an armed handle (its previous solve collected): the gate opens with this state; the armed solve becomes the
+// pending one
+static int open_armed(mppi_handle *h, const float *state)
+{
+  const int kind = h->armed;
+  h->armed = 0;
+  h->arm_n = 0;
+  h->seq = h->arm_seq;
+  write_gate(h, state, h->seq);
+  h->order_stream = h->arm_stream;
+  std::swap(h->d_costs, h->d_costs_alt);
+  std::swap(h->d_w, h->d_w_alt);
+  h->v_buf = h->arm_vbuf;
+  if (kind == 1) h->gen_cur = h->arm_vbuf == h->d_gen[0] ? 0 : 1;
+  h->in_cur = h->arm_in;
+  h->d_in = h->d_in_buf[h->in_cur];
+  h->u_dirty = false;  // the armed tail smooths into d_in and leaves the slid copy in the other buffer
+  h->slid_valid = true;
+  if (kind == 2) {  // the draws of the solve after it, behind the opened gate (as the chained ticks do)
+    const int rc = prefetch_noise(h);
+    if (rc) {
+      h->pending = true;
+      h->pending_armed = true;
+      return rc;
+    }
+  }
+  h->pending = true;
+  h->pending_timed = false;
+  h->pending_armed = true;
+  h->explicit_iters = 0;
+  return MPPI_OK;
+}
+
+// mppi_arm_batch: one launch for the batch where mppi_compute_control_batch would use one (the row form's batched kernel, gated)
+static bool batch_together(mppi_handle *const *hs, int n);
+static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
+{
+  mppi_handle *h0 = hs[0];
+  if (!form_is_row(form_of(h0))) return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
+  for (int i = 0; i < n; i++)
+    if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");
+  HIPCHK(h0, ensure_device(h0->cfg.device));
+  if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
+  const hipStream_t S = h0->batch_s;
+  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    if (h->order_stream != S) {  // the hand-over to the batch stream, as mppi_compute_control_batch_async makes it
+      hipError_t e = hipStreamSynchronize(h->order_stream ? h->order_stream : h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->gstream);
+      if (e != hipSuccess) return fail(h, MPPI_ERR_HIP, "armed batch: stream hand-over", e);
+      h->order_stream = S;
+    }
+  }
+  QuadBatchArgs qb;
+  TailLaunch tl[kMaxBatch];
+  qb.n = n;
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    h->arm_seq = (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
+    h->gate_blk ^= 1;
+    float *noise = h->d_gen[1 - h->gen_cur];
+    HIPCHK(h, hipEventRecord(h->ev_arm, S));
+    RolloutArgs &a = qb.inst[i];
+    armed_args(h, noise, a, tl[i], max_wait_s);
+    if (int trc = tag_min_cost(h, a, S)) return trc;
+    tl[i].min_cost_tag = h->min_cost_tag;
+    a.inline_noise = 1;
+    a.rng_in = h->d_rng[h->rng_cur];
+    a.rng_out = h->d_rng[1 - h->rng_cur];
+    h->rng_cur = 1 - h->rng_cur;
+    mark_armed(h, 1, noise, S, max_wait_s);
+  }
+  for (int i = 0; i < n; i++) {
+    hs[i]->arm_n = n;
+    for (int q = 0; q < n; q++) hs[i]->arm_peers[q] = hs[q];
+  }
+  for (int i = n; i < kMaxBatch; i++) qb.inst[i] = qb.inst[0];
+  hipError_t e = launch_rollout_row_batch(qb, form_of(h0) == Form::RowTree, S);
+  if (e == hipSuccess) {
+    for (int i = 0; i < n; i++) {
+      if (++hs[i]->tail_epoch == 0) hs[i]->tail_epoch = 1;
+      tl[i].epoch = hs[i]->tail_epoch;
+    }
+    e = launch_solve_tail_batch(tl, n, S);
+  }
+  if (e != hipSuccess) {
+    const int rc = fail(h0, MPPI_ERR_HIP, "armed batched launch", e);
+    (void)solve_ahead_disarm(h0);
+    return rc;
+  }
+  return MPPI_OK;
+}
+
+// One launch for all instances where the quad form serves them together (every wave of every group still gets a
+// SIMD of its own: the sum of the groups fits the CUs); otherwise every solve on its own handle's stream, as
+// n calls of mppi_compute_control_async would do.  (mppi_compute_control_batch_async, mppi_arm_batch)
+static bool batch_together(mppi_handle *const *hs, int n)
+{
+  const mppi_handle *h0 = hs[0];
+  bool together = n >= 2 && n <= kMaxBatch;
+  int waves = 0;
+  for (int i = 0; i < n && together; i++) {
+    const mppi_handle *h = hs[i];
+    // network model: the four-wavefront form; basis-function model: its three-wavefront form (in-kernel generator)
+    const Form f = form_of(h);
+    const bool form_ok = h->basis ? (h0->basis && f == Form::Bf3)
+                                  : (!h0->basis && (f == Form::Quad || form_is_row(f)) && f == form_of(h0) &&
+                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden);
+    // one kernel instance serves the whole batch: the instances must agree on what it is specialised for (affine / projective
+    // costmap transform, control cost or none) -- a superset kernel would compute 0 * x where the single solve computes
+    // nothing, which differs for a non-finite x (ADVICE round 3); such a pair is solved one by one
+    CostArgs ci, c0;
+    fill_cost_args(h, ci);
+    fill_cost_args(h0, c0);
+    together = form_ok && ci.affine == c0.affine && ci.need_control_cost == c0.need_control_cost &&
+               h->cfg.device == h0->cfg.device && h->cfg.num_iters == h0->cfg.num_iters &&
+               h->K <= 4096 && !h->timing && !h->capture && !h->prefetch_valid && h->have_nn && h->have_map && h->have_cost;
+    // waves of a group that need a SIMD each: quad 4, row 4 dynamics waves (its riders ride), basis functions 3
+    waves += h->basis ? 3 * (h->K / 64) : 4 * (h->K / kRolloutsPerWave);
+  }
+  return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
+}
+
+static bool armed_as_batch(mppi_handle *const *hs, int n)
+{
+  for (int i = 0; i < n; i++) {
+    if (!hs[i]->armed || hs[i]->arm_n != n) return false;
+    for (int q = 0; q < n; q++)
+      if (hs[i]->arm_peers[q] != hs[q]) return false;
+  }
+  return true;
+}
+
 }  // namespace mppi_abi
 
 extern "C" {
@@ -707,32 +1029,37 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
   }
   // the host-side halves of this tick (nominal replays, DDP passes) are a solve's length away: the helper thread wakes now
   if (n == 2 && g_host_threads.load(std::memory_order_relaxed) >= 2) host_helper_arm();
-  // One launch for all instances where the quad form serves them together (every wave of every group still gets a
-  // SIMD of its own: the sum of the groups fits the CUs); otherwise every solve on its own handle's stream, as
-  // n calls of mppi_compute_control_async would do.
-  mppi_handle *h0 = hs[0];
-  bool together = n >= 2 && n <= kMaxBatch;
-  int waves = 0;
-  for (int i = 0; i < n && together; i++) {
-    const mppi_handle *h = hs[i];
-    // network model: the four-wavefront form; basis-function model: its three-wavefront form (in-kernel generator)
-    const Form f = form_of(h);
-    const bool form_ok = h->basis ? (h0->basis && f == Form::Bf3)
-                                  : (!h0->basis && (f == Form::Quad || form_is_row(f)) && f == form_of(h0) &&
-                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden);
-    // one kernel instance serves the whole batch: the instances must agree on what it is specialised for (affine / projective
-    // costmap transform, control cost or none) -- a superset kernel would compute 0 * x where the single solve computes
-    // nothing, which differs for a non-finite x (ADVICE round 3); such a pair is solved one by one
-    CostArgs ci, c0;
-    fill_cost_args(h, ci);
-    fill_cost_args(h0, c0);
-    together = form_ok && ci.affine == c0.affine && ci.need_control_cost == c0.need_control_cost &&
-               h->cfg.device == h0->cfg.device && h->cfg.num_iters == h0->cfg.num_iters &&
-               h->K <= 4096 && !h->timing && !h->capture && !h->prefetch_valid && h->have_nn && h->have_map && h->have_cost;
-    // waves of a group that need a SIMD each: quad 4, row 4 dynamics waves (its riders ride), basis functions 3
-    waves += h->basis ? 3 * (h->K / 64) : 4 * (h->K / kRolloutsPerWave);
+  // armed together (mppi_arm_batch) with exactly these handles in this order: the gates open.  Any other batch calls the
+  // armed solves of its handles off first.
+  if (armed_as_batch(hs, n)) {
+    int rc = MPPI_OK;
+    bool usable = true;
+    for (int i = 0; i < n; i++) {
+      mppi_handle *h = hs[i];
+      if (rc == MPPI_OK) rc = check_ready(h);
+      if (rc == MPPI_OK) rc = recover_timed_out(h);
+      if (rc == MPPI_OK) rc = wait_pending(h);
+      usable = usable && arm_usable(h);
+    }
+    if (rc == MPPI_OK && usable) {
+      for (int i = 0; i < n; i++) {
+        const int orc = open_armed(hs[i], states + (size_t)MPPI_STATE_DIM * i);
+        if (orc && !rc) rc = orc;
+      }
+      return rc;
+    }
+    const int drc = solve_ahead_disarm(hs[0]);
+    if (rc) return rc;
+    if (drc) return drc;
   }
-  together = together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
+  const bool together = batch_together(hs, n);
+  for (int i = 0; i < n; i++) {  // an armed solve of another batch; one armed alone where this batch is one launch
+    if (hs[i]->armed && (hs[i]->arm_n > 0 || together)) {
+      const int drc = solve_ahead_disarm(hs[i]);
+      if (drc) return drc;
+    }
+  }
+  mppi_handle *h0 = hs[0];
   if (!together) {
     for (int i = 0; i < n; i++) {
       const int rc = mppi_compute_control_async(hs[i], states + (size_t)MPPI_STATE_DIM * i);
@@ -781,7 +1108,7 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     }
     rc = upload_controls_if_dirty(h, S);
     if (rc) return poison(rc);
-    h->seq++;
+    next_seq(h);
   }
   for (int it = 0; it < iters; it++) {
     QuadBatchArgs qb;
@@ -855,6 +1182,7 @@ int mppi_control_ticks_batch(mppi_handle *const *hs, const float *states, int n,
 int mppi_control_ticks(mppi_handle *h, const float state[MPPI_STATE_DIM], int n_ticks, int stride)
 {
   if (!h || n_ticks < 0 || stride < 0) return MPPI_ERR_INVALID;
+  DISARM(h);
   const int kind = state ? chain_kind(h, n_ticks, stride) : 0;
   if (kind) return control_ticks_chained(h, state, n_ticks, stride, kind);
   for (int i = 0; i < n_ticks; i++) {
@@ -876,7 +1204,12 @@ int mppi_get_results(mppi_handle *h, float *U, float *traj_cost, float *costs, f
   if (h->no_result) return fail(h, MPPI_ERR_HIP, "the last solve timed out: no result");
   if (U) memcpy(U, h->U.data(), sizeof(float) * 2 * (size_t)h->T);
   if (traj_cost) *traj_cost = h->traj_cost;
-  if (costs || weights) {
+  if ((costs || weights) && h->armed) {
+    // the armed solve writes the other pair of vectors: these are the last result's once the stream has passed the point in
+    // front of the armed solve (the blocking copies of the null stream do not wait for the handle's non-blocking streams)
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipEventSynchronize(h->ev_arm));
+  } else if (costs || weights) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     OWN(h);
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -895,6 +1228,15 @@ int mppi_get_applied_controls(mppi_handle *h, float *V, size_t n)
   if (rc) return rc;
   if (h->no_result) return fail(h, MPPI_ERR_HIP, "the last solve timed out: no result");
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (h->armed) {
+    // the armed solve leaves its applied controls elsewhere: the last solve's are read on the generator stream, behind the
+    // point in front of the armed solve, not behind the armed kernels
+    HIPCHK(h, hipStreamWaitEvent(h->gstream, h->ev_arm, 0));
+    HIPCHK(h, launch_tk_to_kt(h->v_buf, h->d_stage, h->K, h->T, h->gstream));
+    HIPCHK(h, hipMemcpyAsync(V, h->d_stage, slot * sizeof(float), hipMemcpyDeviceToHost, h->gstream));
+    HIPCHK(h, hipStreamSynchronize(h->gstream));
+    return MPPI_OK;
+  }
   OWN(h);
   HIPCHK(h, launch_tk_to_kt(h->v_buf, h->d_stage, h->K, h->T, h->stream));
   HIPCHK(h, hipMemcpyAsync(V, h->d_stage, slot * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -907,6 +1249,7 @@ int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
   int rc = check_ready(h);
   if (rc) return rc;
   if (!state || !costs) return fail(h, MPPI_ERR_INVALID, "NULL argument");
+  DISARM(h);
   HIPCHK(h, hipSetDevice(h->cfg.device));
   rc = recover_timed_out(h);
   if (rc) return rc;
@@ -948,6 +1291,7 @@ int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
 int mppi_debug_capture_iterations(mppi_handle *h, int on)
 {
   if (!h) return MPPI_ERR_INVALID;
+  DISARM(h);
   int rc = mppi_synchronize(h);
   if (rc) return rc;
   if (on && !h->d_cap) {
@@ -995,6 +1339,54 @@ int mppi_debug_get_iterations(mppi_handle *h, float *U_raw, float *costs, float 
  * the control history are what the next solve starts from, no call waits for the lost solve again (each returns MPPI_ERR_HIP at
  * once while its device work is still running, one hipStreamQuery per call) and the handle works again once that work has
  * drained.  mppi_destroy synchronises the handle's streams and may block for as long as that work runs. */
+/* Solve-ahead (csrc/abi_solve.hip: mppi_arm). */
+int mppi_arm(mppi_handle *h, double max_wait_s)
+{
+  if (!h || !(max_wait_s > 0.0 && max_wait_s <= 0.1)) return MPPI_ERR_INVALID;
+  if (h->armed && h->arm_n == 0) return MPPI_OK;  // already armed
+  DISARM(h);  // (armed as part of a batch)
+  return arm_one(h, max_wait_s);
+}
+
+int mppi_arm_batch(mppi_handle *const *hs, int n, double max_wait_s)
+{
+  if (!hs || n < 1 || n > 64 || !(max_wait_s > 0.0 && max_wait_s <= 0.1)) return MPPI_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!hs[i]) return MPPI_ERR_INVALID;
+    for (int q = 0; q < i; q++)
+      if (hs[q] == hs[i]) return fail(hs[i], MPPI_ERR_INVALID, "the same handle twice in one batch");
+  }
+  if (n >= 2 && armed_as_batch(hs, n)) return MPPI_OK;
+  for (int i = 0; i < n; i++)
+    if (hs[i]->armed && (hs[i]->arm_n > 0 || n >= 2)) DISARM(hs[i]);
+  if (n >= 2) {
+    for (int i = 0; i < n; i++) {  // the batch's own checks first (what batch_together reads)
+      int rc = check_ready(hs[i]);
+      if (rc) return rc;
+    }
+    if (batch_together(hs, n)) return arm_together(hs, n, max_wait_s);
+  }
+  // each handle on its own, where it can be: MPPI_ERR_UNSUPPORTED if one could not be (the others stay armed)
+  int out = MPPI_OK;
+  for (int i = 0; i < n; i++) {
+    const int rc = mppi_arm(hs[i], max_wait_s);
+    if (rc == MPPI_ERR_UNSUPPORTED) out = rc;
+    else if (rc) return rc;
+  }
+  return out;
+}
+
+int mppi_disarm(mppi_handle *h)
+{
+  if (!h) return MPPI_ERR_INVALID;
+  return solve_ahead_disarm(h);
+}
+
+int mppi_is_armed(const mppi_handle *h)
+{
+  return (h && h->armed) ? 1 : 0;
+}
+
 int mppi_set_wait_timeout(mppi_handle *h, double seconds)
 {
   if (!h || !(seconds > 0.0)) return MPPI_ERR_INVALID;

@@ -44,7 +44,7 @@ void free_all(mppi_handle *h)
 {
   if (!h) return;
   float *fp[] = {h->d_theta_s, h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
-                 h->d_w, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_row64pack, h->d_m44pack, h->d_cap};
+                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_row64pack, h->d_m44pack, h->d_cap};
   for (float *p : fp)
     if (p) (void)hipFree(p);
   if (h->d_invt) (void)hipFree(h->d_invt);
@@ -67,6 +67,7 @@ void free_all(mppi_handle *h)
   for (auto &e : h->ev_gt)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_s1) (void)hipEventDestroy(h->ev_s1);
+  if (h->ev_arm) (void)hipEventDestroy(h->ev_arm);
   if (h->gstream) (void)hipStreamDestroy(h->gstream);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -196,6 +197,7 @@ int mppi_create(const mppi_config *cfg, mppi_handle **out)
   CR(hipEventCreate(&h->ev_gt[0]));
   CR(hipEventCreate(&h->ev_gt[1]));
   CR(hipEventCreateWithFlags(&h->ev_s1, hipEventDisableTiming));
+  CR(hipEventCreateWithFlags(&h->ev_arm, hipEventDisableTiming));
   h->n_slots = std::max(1, cfg->num_iters);
   CR(hipMalloc(&h->d_in_buf[0], sizeof(float) * (2 * (size_t)h->T + 4)));
   CR(hipMalloc(&h->d_in_buf[1], sizeof(float) * (2 * (size_t)h->T + 4)));
@@ -226,6 +228,8 @@ int mppi_create(const mppi_config *cfg, mppi_handle **out)
   CR(hipMalloc(&h->d_stage, sizeof(float) * KT2));
   CR(hipMalloc(&h->d_costs, sizeof(float) * h->K));
   CR(hipMalloc(&h->d_w, sizeof(float) * h->K));
+  CR(hipMalloc(&h->d_costs_alt, sizeof(float) * h->K));
+  CR(hipMalloc(&h->d_w_alt, sizeof(float) * h->K));
   CR(hipMalloc(&h->d_theta, sizeof(float) * h->net.num_params));
   CR(hipMalloc(&h->d_theta_s, sizeof(float) * h->net.num_params));
   if (h->mfma_ok)
@@ -250,7 +254,8 @@ int mppi_create(const mppi_config *cfg, mppi_handle **out)
   }
   {
     // gate block of the chained control ticks: fine-grained device memory the host can store into (large BAR), else host-mapped
-    const size_t gate_bytes = sizeof(float) * gate_block_floats(h->T);  // replicas of [state, gate word], then U[T][2], hist[4]
+    // two blocks (gate_blk), each: replicas of [state, gate word], then U[T][2], hist[4]
+    const size_t gate_bytes = sizeof(float) * 2 * gate_block_stride(h->T);
     void *gp = nullptr;
     if (prop.isLargeBar && hipExtMallocWithFlags(&gp, gate_bytes, hipDeviceMallocFinegrained) == hipSuccess && gp != nullptr) {
       h->gate_cpu = h->d_gate = static_cast<unsigned *>(gp);
@@ -293,6 +298,7 @@ int mppi_destroy(mppi_handle *h)
 {
   if (!h) return MPPI_ERR_INVALID;
   (void)hipSetDevice(h->cfg.device);
+  (void)solve_ahead_disarm(h);  // its gated kernels end at once (poisoned): the synchronisations below do not wait for a deadline
   if (h->order_stream && h->order_stream != h->stream) (void)hipStreamSynchronize(h->order_stream);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
@@ -303,6 +309,7 @@ int mppi_destroy(mppi_handle *h)
 int mppi_set_bf_params(mppi_handle *h, const float *W, size_t n)
 {
   if (!h || !W) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (!h->basis) return fail(h, MPPI_ERR_STATE, "handle was created with a network (n_layers != 0)");
   if (n != (size_t)(4 * kNumBfs)) return fail(h, MPPI_ERR_INVALID, "W size != 4 * 25");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -317,6 +324,7 @@ int mppi_set_bf_params(mppi_handle *h, const float *W, size_t n)
 int mppi_set_nn_params(mppi_handle *h, const float *theta, size_t n)
 {
   if (!h || !theta) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (h->basis) return fail(h, MPPI_ERR_STATE, "handle was created for basis-function dynamics: use mppi_set_bf_params");
   if (n != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, "theta size != NUM_PARAMS");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -360,6 +368,7 @@ int mppi_set_nn_params(mppi_handle *h, const float *theta, size_t n)
 int mppi_update_model(mppi_handle *h, const int *description, int n_desc, const float *data, size_t n)
 {
   if (!h || !description || !data) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (h->basis) return fail(h, MPPI_ERR_STATE, "updateModel exists for the network model only");
   // neural_net_model.cu:155-161: a mismatching description leaves the model untouched
   for (int i = 0; i < n_desc; i++)
@@ -384,6 +393,7 @@ int mppi_update_model(mppi_handle *h, const int *description, int n_desc, const 
 int mppi_set_control_limits(mppi_handle *h, const float umin[2], const float umax[2])
 {
   if (!h || !umin || !umax) return MPPI_ERR_INVALID;
+  DISARM(h);
   for (int i = 0; i < 2; i++) {
     h->u_lo[i] = umin[i];
     h->u_hi[i] = umax[i];
@@ -395,6 +405,7 @@ int mppi_set_costmap(mppi_handle *h, int width, int height, const float *rgba, c
                      const float r_c2[3], const float trs[3])
 {
   if (!h || !rgba || !r_c1 || !r_c2 || !trs) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (width <= 0 || height <= 0 || (size_t)width * (size_t)height > ((size_t)1 << 30))
     return fail(h, MPPI_ERR_INVALID, "bad costmap size");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -424,6 +435,7 @@ int mppi_set_costmap(mppi_handle *h, int width, int height, const float *rgba, c
 int mppi_set_costmap_transform(mppi_handle *h, const float r_c1[3], const float r_c2[3], const float trs[3])
 {
   if (!h || !r_c1 || !r_c2 || !trs) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (!h->have_map) return fail(h, MPPI_ERR_STATE, "mppi_set_costmap has not been called");
   for (int i = 0; i < 3; i++) {  // kernel arguments of the next launch; nothing on the device changes
     h->r_c1[i] = r_c1[i];
@@ -436,6 +448,7 @@ int mppi_set_costmap_transform(mppi_handle *h, const float r_c1[3], const float 
 int mppi_set_costmap_channel(mppi_handle *h, int channel, const float *data, size_t n)
 {
   if (!h || !data) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (!h->have_map) return fail(h, MPPI_ERR_STATE, "mppi_set_costmap has not been called");
   if (channel < 0 || channel > 3 || n != (size_t)h->map_w * h->map_h)
     return fail(h, MPPI_ERR_INVALID, "bad channel or size");
@@ -452,6 +465,7 @@ int mppi_set_costmap_channel(mppi_handle *h, int channel, const float *data, siz
 int mppi_set_cost_params(mppi_handle *h, const mppi_cost_params *p)
 {
   if (!h || !p) return MPPI_ERR_INVALID;
+  DISARM(h);
   h->cost = *p;
   h->have_cost = true;
   return MPPI_OK;
@@ -577,6 +591,7 @@ int mppi_slide_control_seq(mppi_handle *h, int stride)
 int mppi_seed(mppi_handle *h, uint64_t seed, uint64_t offset)
 {
   if (!h) return MPPI_ERR_INVALID;
+  DISARM(h);
   HIPCHK(h, hipSetDevice(h->cfg.device));
   int rc = mppi_synchronize(h);
   if (rc) return rc;
@@ -593,6 +608,7 @@ int mppi_seed(mppi_handle *h, uint64_t seed, uint64_t offset)
 int mppi_set_noise(mppi_handle *h, const float *eps, size_t n)
 {
   if (!h || !eps) return MPPI_ERR_INVALID;
+  DISARM(h);
   const size_t slot = (size_t)h->K * h->T * 2;
   if (n != slot * (size_t)h->cfg.num_iters) return fail(h, MPPI_ERR_INVALID, "noise size != num_iters*K*T*2");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -614,6 +630,7 @@ int mppi_set_noise(mppi_handle *h, const float *eps, size_t n)
 int mppi_generate_noise(mppi_handle *h, float *eps_out, size_t n)
 {
   if (!h || !eps_out) return MPPI_ERR_INVALID;
+  DISARM(h);
   const size_t slot_sz = (size_t)h->K * h->T * 2;
   if (n != slot_sz) return fail(h, MPPI_ERR_INVALID, "n != K*T*2");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -634,6 +651,7 @@ int mppi_debug_cost_raster(mppi_handle *h, float x, float y, float heading, int 
                            int ppm, float *out, size_t n)
 {
   if (!h || !out || width_m <= 0 || height_m <= 0 || ppm <= 0) return MPPI_ERR_INVALID;
+  DISARM(h);
   const size_t W = (size_t)width_m * ppm, H = (size_t)height_m * ppm;
   if (W > 8192 || H > 8192 || n != W * H) return fail(h, MPPI_ERR_INVALID, "n != (width_m*ppm) * (height_m*ppm)");
   if (!h->have_map) return fail(h, MPPI_ERR_STATE, "mppi_set_costmap has not been called");
@@ -655,6 +673,7 @@ int mppi_debug_cost_raster(mppi_handle *h, float x, float y, float heading, int 
 int mppi_enable_stage_timing(mppi_handle *h, int on)
 {
   if (!h) return MPPI_ERR_INVALID;
+  DISARM(h);
   h->timing = on != 0;
   h->timing_every = on > 1 ? on : 1;  // on = N > 1: sample every Nth solve
   h->timing_count = 0;
@@ -685,6 +704,7 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out)
 int mppi_debug_inject_handover_fault(mppi_handle *h, int wave, int spin_budget)
 {
   if (!h || wave < 0 || (wave > 12 && (wave < 32 || wave > 34)) || spin_budget < 0) return MPPI_ERR_INVALID;
+  DISARM(h);
   h->fault_wave = wave;
   h->spin_budget = spin_budget;
   return MPPI_OK;
@@ -695,6 +715,7 @@ int mppi_debug_inject_handover_fault(mppi_handle *h, int wave, int spin_budget)
 int mppi_debug_min_cost(mppi_handle *h, int on, int *from_rollout)
 {
   if (!h) return MPPI_ERR_INVALID;
+  DISARM(h);
   int rc = mppi_synchronize(h);
   if (rc) return rc;
   if (on >= 0) h->use_min_cost = on != 0;
@@ -711,6 +732,7 @@ int mppi_debug_min_cost(mppi_handle *h, int on, int *from_rollout)
 int mppi_debug_set_chained_ticks(mppi_handle *h, int on)
 {
   if (!h) return MPPI_ERR_INVALID;
+  DISARM(h);
   int rc = mppi_synchronize(h);
   if (rc) return rc;
   h->chain = on != 0;
@@ -722,6 +744,7 @@ int mppi_debug_set_chained_ticks(mppi_handle *h, int on)
 int mppi_debug_dynamics(mppi_handle *h, int n, const float *states, const float *controls, float *ders)
 {
   if (!h || n <= 0 || !states || !controls || !ders) return MPPI_ERR_INVALID;
+  DISARM(h);
   if (!h->have_nn) return fail(h, MPPI_ERR_STATE, "mppi_set_nn_params has not been called");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   OWN(h);

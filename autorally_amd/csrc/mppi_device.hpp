@@ -58,6 +58,10 @@ struct RolloutArgs {
   // (kGateReplicas copies of 64 B each, written by the host; workgroup b polls copy b % kGateReplicas).  nullptr: not gated.
   const unsigned *gate;
   unsigned gate_seq;
+  // the gated kernel's deadline: how long (100 MHz real-time ticks) a pose wave waits for its gate before it gives up and the
+  // group's costs are poisoned (mppi_arm's max_wait_s; the chained ticks of mppi_control_ticks: 100 ms).  Sits in the padding
+  // in front of min_cost: the block keeps its size.
+  unsigned gate_ticks;
   // the launch's minimum cost for the tail kernel that follows (publish_min_cost below): kMinCostLines keys, the launch's tag.
   // nullptr: not published (the tail takes the minimum itself)
   unsigned long long *min_cost;
@@ -428,7 +432,7 @@ __device__ __forceinline__ void spin_finish(int budget, uint32_t a_fail, uint32_
 // Gated launch (the chained control ticks of abi_solve.hip; SH with gstate[8] and gate_open[8]: the row, m44 and multi4-tree forms): ONE wave of the group -- the pose wave; the multi form: the control wave -- waits for the host to open the gate -- word 7 of this workgroup's copy of the gate block equal to
 // a.gate_seq -- and hands the block's vehicle state to the dynamics waves through LDS.  The gate word is host-written memory
 // (device memory the host stores into through the PCIe BAR, or host-mapped memory): system-scope loads.  The wait is bounded by
-// the 100 MHz real-time counter (100 ms); a gate that stays shut, or is opened with the cancel bit, leaves the pose wave with an
+// the 100 MHz real-time counter (a.gate_ticks: the arming call's max_wait_s, 100 ms in the chained ticks); a gate that stays shut, or is opened with the cancel bit, leaves the pose wave with an
 // exhausted poll budget: the group's costs are poisoned (NaN) as after any other failed hand-over, the kernel ends.
 template <class SH>
 __device__ __forceinline__ int group_gate_wait(const RolloutArgs &a, SH &sh)
@@ -440,7 +444,7 @@ __device__ __forceinline__ int group_gate_wait(const RolloutArgs &a, SH &sh)
   for (;;) {
     v = __hip_atomic_load(blk + 7, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if ((v & ~kGateCancel) == a.gate_seq) break;
-    if (__builtin_amdgcn_s_memrealtime() - t0 > 10000000ull) { v = kGateCancel; break; }
+    if (__builtin_amdgcn_s_memrealtime() - t0 > (unsigned long long)a.gate_ticks) { v = kGateCancel; break; }
     __builtin_amdgcn_s_sleep(2);
   }
   // the state words were stored before the gate word (the host fences between them): loaded only now

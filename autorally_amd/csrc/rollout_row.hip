@@ -366,7 +366,7 @@ __global__ __launch_bounds__(512) void rollout_row_kernel(const RolloutArgs a)
   __shared__ __attribute__((aligned(16))) RowShared<H> sh;
   row_group<H, AFFINE, CTRL, TREE>(a, sh);
 }
-// the same kernel enqueued one solve ahead (a.gate != nullptr): see row_gate_wait
+// the same kernel enqueued one solve ahead (a.gate != nullptr): see group_gate_wait (mppi_device.hpp)
 template <int H, bool AFFINE, bool CTRL, bool TREE>
 __global__ __launch_bounds__(512) void rollout_row_gated_kernel(const RolloutArgs a)
 {
@@ -391,6 +391,22 @@ __global__ __launch_bounds__(512) void rollout_row_batch_kernel(const QuadBatchA
 #undef MPPI_ROW_BODY
 }
 
+// the same batched kernel enqueued one solve ahead (mppi_arm_batch): every instance's argument block carries its OWN handle's
+// gate block (a.gate, a.gate_seq, a.gate_ticks; a.U points at the nominal sequence inside it), whose pose wave polls replica
+// blockIdx.x % kGateReplicas of it -- blockIdx.x is the group index inside the instance, as in the single gated kernel
+template <int H, bool AFFINE, bool CTRL, bool TREE, int NB>
+__global__ __launch_bounds__(512) void rollout_row_batch_gated_kernel(const QuadBatchArgsT<NB> b)
+{
+  __shared__ __attribute__((aligned(16))) RowShared<H> sh;
+#define MPPI_ROW_BODY(A)                                                                                   \
+  do {                                                                                                     \
+    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* a smaller instance than the largest */     \
+    row_group<H, AFFINE, CTRL, TREE, true>((A), sh);                                                       \
+  } while (0)
+  MPPI_BATCH_DISPATCH(NB, b, MPPI_ROW_BODY);
+#undef MPPI_ROW_BODY
+}
+
 bool row_variant_supported(int hidden, int n_hidden) { return hidden == 32 && n_hidden == 2; }
 int row_pack_floats() { return kRowPackEntries * 16 * 4; }
 
@@ -402,12 +418,12 @@ int row_pack_floats() { return kRowPackEntries * 16 * 4; }
     else if (!affine && !ctrl) LAUNCH((KERN<32, false, false, TREE>), __VA_ARGS__);                           \
     else LAUNCH((KERN<32, false, true, TREE>), __VA_ARGS__);                                                  \
   } while (0)
-#define MPPI_ROW_BATCH_DISPATCH(TREE, NB, ...)                                                                                  \
+#define MPPI_ROW_BATCH_DISPATCH(KERN, TREE, NB, ...)                                                                            \
   do {                                                                                                                          \
-    if (affine && !ctrl) hipLaunchKernelGGL((rollout_row_batch_kernel<32, true, false, TREE, NB>), __VA_ARGS__);                \
-    else if (affine && ctrl) hipLaunchKernelGGL((rollout_row_batch_kernel<32, true, true, TREE, NB>), __VA_ARGS__);             \
-    else if (!affine && !ctrl) hipLaunchKernelGGL((rollout_row_batch_kernel<32, false, false, TREE, NB>), __VA_ARGS__);         \
-    else hipLaunchKernelGGL((rollout_row_batch_kernel<32, false, true, TREE, NB>), __VA_ARGS__);                                \
+    if (affine && !ctrl) hipLaunchKernelGGL((KERN<32, true, false, TREE, NB>), __VA_ARGS__);                                    \
+    else if (affine && ctrl) hipLaunchKernelGGL((KERN<32, true, true, TREE, NB>), __VA_ARGS__);                                 \
+    else if (!affine && !ctrl) hipLaunchKernelGGL((KERN<32, false, false, TREE, NB>), __VA_ARGS__);                             \
+    else hipLaunchKernelGGL((KERN<32, false, true, TREE, NB>), __VA_ARGS__);                                                    \
   } while (0)
 
 hipError_t launch_rollout_row_batch(const QuadBatchArgs &b, bool tree, hipStream_t stream)
@@ -415,7 +431,9 @@ hipError_t launch_rollout_row_batch(const QuadBatchArgs &b, bool tree, hipStream
   if (b.n < 1 || b.n > kMaxBatch) return hipErrorInvalidValue;
   bool affine = true, ctrl = false;  // the general forms are exact supersets (rollout_mfma.hip)
   int gmax = 0;
+  const bool gated = b.inst[0].gate != nullptr;  // mppi_arm_batch: every instance gated on its own block, or none
   for (int i = 0; i < b.n; i++) {
+    if ((b.inst[i].gate != nullptr) != gated) return hipErrorInvalidValue;
     affine = affine && b.inst[i].cost.affine != 0;
     ctrl = ctrl || b.inst[i].cost.need_control_cost != 0;
     gmax = b.inst[i].K / kRolloutsPerWave > gmax ? b.inst[i].K / kRolloutsPerWave : gmax;
@@ -423,11 +441,21 @@ hipError_t launch_rollout_row_batch(const QuadBatchArgs &b, bool tree, hipStream
   const dim3 grid(gmax, b.n), block(512);
   if (b.n <= 2) {  // the two controllers of a tick: half the argument segment
     const QuadBatchArgsT<2> b2 = batch_args_prefix<2>(b);
-    if (tree) MPPI_ROW_BATCH_DISPATCH(true, 2, grid, block, 0, stream, b2);
-    else MPPI_ROW_BATCH_DISPATCH(false, 2, grid, block, 0, stream, b2);
+    if (gated) {
+      if (tree) MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_gated_kernel, true, 2, grid, block, 0, stream, b2);
+      else MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_gated_kernel, false, 2, grid, block, 0, stream, b2);
+    } else {
+      if (tree) MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_kernel, true, 2, grid, block, 0, stream, b2);
+      else MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_kernel, false, 2, grid, block, 0, stream, b2);
+    }
   } else {
-    if (tree) MPPI_ROW_BATCH_DISPATCH(true, 4, grid, block, 0, stream, b);
-    else MPPI_ROW_BATCH_DISPATCH(false, 4, grid, block, 0, stream, b);
+    if (gated) {
+      if (tree) MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_gated_kernel, true, 4, grid, block, 0, stream, b);
+      else MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_gated_kernel, false, 4, grid, block, 0, stream, b);
+    } else {
+      if (tree) MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_kernel, true, 4, grid, block, 0, stream, b);
+      else MPPI_ROW_BATCH_DISPATCH(rollout_row_batch_kernel, false, 4, grid, block, 0, stream, b);
+    }
   }
   return hipGetLastError();
 }

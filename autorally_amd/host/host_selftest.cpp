@@ -59,6 +59,8 @@ struct FakeController {
   static void startControlPair(FakeController *a, const float *s, FakeController *p) { a->startControl(s); p->startControl(); }
   static void finishControlPair(FakeController *a, FakeController *p) { a->finishControl(); p->finishControl(); }
   static void computeFeedbackGainsPair(FakeController *a, FakeController *p, const float *s) { a->computeFeedbackGains(s); p->computeFeedbackGains(s); }
+  static void armControlPair(FakeController *, FakeController *, double) {}  // solve-ahead: nothing to enqueue here
+  void disarm() {}
   void finishControl() {}
   float getComputedTrajectoryCost() const { return cost; }
   std::vector<float> getControlSeq() const { return control_seq; }

@@ -668,6 +668,27 @@ class MPPIControllerT {
       throw std::runtime_error(std::string("libmppi_hip: ") + mppi_strerror(rc) + " (" + mppi_last_error(actual->h_) +
                                " | " + mppi_last_error(predicted->h_) + ")");
   }
+  // Solve-ahead (mppi_arm): this controller's NEXT solve is enqueued now, gated -- its kernels start and wait at most max_wait_s
+  // for the next startControl / computeControl, which then opens the gate with its state instead of launching.  Results are
+  // bit for bit the same.  MPPI_ERR_UNSUPPORTED (no gated form for this configuration) is no error: the solve launches as before.
+  void arm(double max_wait_s)
+  {
+    syncParams(false);  // what the armed solve computes with (a later change calls it off: the setters disarm)
+    const int rc = mppi_arm(h_, max_wait_s);
+    if (rc != MPPI_ERR_UNSUPPORTED) ck(rc);
+  }
+  void disarm() { ck(mppi_disarm(h_)); }
+  // both solves of the next startControlPair, armed together: one gated launch where the pair is one launch
+  static void armControlPair(MPPIControllerT *actual, MPPIControllerT *predicted, double max_wait_s)
+  {
+    actual->syncParams(false);
+    predicted->syncParams(false);
+    mppi_handle *hs[2] = {actual->h_, predicted->h_};
+    const int rc = mppi_arm_batch(hs, 2, max_wait_s);
+    if (rc != MPPI_OK && rc != MPPI_ERR_UNSUPPORTED)
+      throw std::runtime_error(std::string("libmppi_hip: ") + mppi_strerror(rc) + " (" + mppi_last_error(actual->h_) +
+                               " | " + mppi_last_error(predicted->h_) + ")");
+  }
   void finishControl()
   {
     float tc = 0.0f;

@@ -36,13 +36,14 @@ template <class DYNAMICS_T, class MAKE_MODEL>
 int path_integral_main(int argc, char **argv, int default_rollouts, MAKE_MODEL make_model)
 {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s <launch.xml> [--rollouts K] [--layers 6-32-32-4] [--max-iter N] [--no-sleep] [--host-threads 1|2] [--rollout-variant auto|mfma|...] "
+    fprintf(stderr, "usage: %s <launch.xml> [--rollouts K] [--layers 6-32-32-4] [--max-iter N] [--no-sleep] [--solve-ahead] [--host-threads 1|2] [--rollout-variant auto|mfma|...] "
                     "[--device D] [--trace file] [--set key=value]\n", argv[0]);
     return 2;
   }
   int rollouts = default_rollouts;  // MPPI_NUM_ROLLOUTS__, path_integral_main.cu:66,71
   std::vector<int> layers = {6, 32, 32, 4};  // NeuralNetModel<7,2,3,6,32,32,4>, :69
   int max_iter = -1, device = 0;
+  bool solve_ahead = false;  // --solve-ahead: the loop parameter solve_ahead (run_control_loop.hpp)
   bool sleep_to_rate = true;
   const char *trace_path = nullptr;
   bool have_dcfg = false, debug_image = false;  // stand-ins for the plant's dynamic_reconfigure / debug window
@@ -68,6 +69,7 @@ int path_integral_main(int argc, char **argv, int default_rollouts, MAKE_MODEL m
     else if (!strcmp(argv[i], "--trace") && i + 1 < argc) trace_path = argv[++i];
     else if (!strcmp(argv[i], "--set") && i + 1 < argc) overrides.push_back(argv[++i]);
     else if (!strcmp(argv[i], "--no-sleep")) sleep_to_rate = false;
+    else if (!strcmp(argv[i], "--solve-ahead")) solve_ahead = true;
     else if (!strcmp(argv[i], "--host-threads") && i + 1 < argc) host_threads = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--rollout-variant") && i + 1 < argc) rollout_variant = argv[++i];
     else if (!strcmp(argv[i], "--dcfg-desired-speed") && i + 1 < argc) { dcfg_speed = atof(argv[++i]); have_dcfg = true; }
@@ -92,6 +94,7 @@ int path_integral_main(int argc, char **argv, int default_rollouts, MAKE_MODEL m
       else params[k] = ParamValue(v);
     }
     if (max_iter >= 0) params["profiler_max_iter"] = ParamValue(max_iter);
+    if (solve_ahead) params["solve_ahead"] = ParamValue(true);
     params["debug_mode"] = ParamValue(pose_script == nullptr);  // headless: self-simulation unless poses are scripted
 
     MPPICosts costs(&params);

@@ -170,6 +170,11 @@ LoopStats runControlLoop(CONTROLLER_T *predicted_state_controller, CONTROLLER_T 
   const bool only_predicted = (bool)(*params)["use_only_predicted_state_controller"];
   const int max_iter = params->count("profiler_max_iter") ? (int)(*params)["profiler_max_iter"] : INT_MAX;
   const bool use_feedback_gains = params->count("use_feedback_gains") ? (bool)(*params)["use_feedback_gains"] : false;  // :100
+  // solve-ahead (not in the reference; absent = off): the next tick's two solves are armed (mppi_arm_batch) so that its
+  // startControlPair opens their gates instead of launching -- without sleeps right after this tick's results are in, with
+  // sleeps when the sleep ends (the next pose is almost due: a gated kernel never sits out a control period)
+  const bool solve_ahead = params->count("solve_ahead") ? (bool)(*params)["solve_ahead"] : false;
+  const double solve_ahead_wait = params->count("solve_ahead_max_wait") ? (double)(*params)["solve_ahead_max_wait"] : 0.01;  // s
 
   float state[7] = {x_pos, y_pos, heading, 0, 0, 0, 0};
   std::vector<float> controlSolution, stateSolution, feedback_gain;
@@ -255,6 +260,8 @@ LoopStats runControlLoop(CONTROLLER_T *predicted_state_controller, CONTROLLER_T 
     const auto t_solve0 = std::chrono::steady_clock::now();
     CONTROLLER_T::startControlPair(actual_state_controller, state, predicted_state_controller);
     CONTROLLER_T::finishControlPair(actual_state_controller, predicted_state_controller);
+    if (solve_ahead && !sleep_to_rate && num_iter < max_iter)
+      CONTROLLER_T::armControlPair(actual_state_controller, predicted_state_controller, solve_ahead_wait);
     const auto t_solve1 = std::chrono::steady_clock::now();
     if (use_feedback_gains)  // :220-225: both controllers, from the measured state
       CONTROLLER_T::computeFeedbackGainsPair(actual_state_controller, predicted_state_controller, state);
@@ -317,11 +324,17 @@ LoopStats runControlLoop(CONTROLLER_T *predicted_state_controller, CONTROLLER_T 
       std::this_thread::sleep_for(std::chrono::microseconds(50));
       fp_ms = std::chrono::steady_clock::now() - loop_start;
     }
+    if (solve_ahead && sleep_to_rate && is_alive->load() && num_iter < max_iter)
+      CONTROLLER_T::armControlPair(actual_state_controller, predicted_state_controller, solve_ahead_wait);
     const double sleep = fp_ms.count() - tick;
     // :315-318
     avgOptimizationLoopTime = (num_iter - 1.0) / num_iter * avgOptimizationLoopTime + 1000.0 * optimizationLoopTime / num_iter;
     avgTick = (num_iter - 1.0) / num_iter * avgTick + tick / num_iter;
     avgSleep = (num_iter - 1.0) / num_iter * avgSleep + sleep / num_iter;
+  }
+  if (solve_ahead) {  // (the loop arms no solve behind its last tick; an early stop may leave one armed)
+    actual_state_controller->disarm();
+    predicted_state_controller->disarm();
   }
   st.iterations = num_iter;
   st.avg_tick_ms = avgTick;

@@ -37,7 +37,8 @@ extern "C" {
 /* 5: solves of more than 4096 rollouts run a one-launch tail (in-launch hand-overs with a deadline: fault roles 32-34 of
  *    mppi_debug_inject_handover_fault); after a wait timeout the lost solve is not waited for again (mppi_set_wait_timeout);
  *    "mfma" / "valu" / "valu_lds" drop a form forced by name; variants "multi1", "multi4u[_gen]", "row64_r8" removed;
- *    + mppi_debug_set_chained_ticks (mppi_control_ticks enqueues one solve ahead), + mppi_debug_min_cost. */
+ *    + mppi_debug_set_chained_ticks (mppi_control_ticks enqueues one solve ahead), + mppi_debug_min_cost;
+ *    + mppi_arm, mppi_arm_batch, mppi_disarm, mppi_is_armed (solve-ahead for a new state every tick; compatible additions). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -187,6 +188,30 @@ int mppi_synchronize(mppi_handle *h);
  * mppi_synchronize / mppi_get_results.  The blocking form waits for all of them. */
 int mppi_compute_control_batch_async(mppi_handle *const *handles, const float *states, int n);
 int mppi_compute_control_batch(mppi_handle *const *handles, const float *states, int n);
+/* Solve-ahead: the launch call and the dispatch of the NEXT solve leave the control step.  mppi_arm enqueues this handle's next
+ * solve now, gated: its kernels start (weights, first noise) and wait at most max_wait_s (0 < max_wait_s <= 0.1) for the next
+ * mppi_compute_control[_async] to supply the state -- that call does not launch, it writes its state, the host's U and hist into
+ * the gate and opens it.  May be called with a solve pending (the armed one goes behind it) or idle.  MPPI_ERR_UNSUPPORTED
+ * (nothing enqueued, handle unchanged) where the handle's form / configuration has no gated form: num_iters > 1, the
+ * basis-function model, forms other than the row forms, the automatic m44 form and the automatic multi4-tree form with its
+ * generator kernel, stage timing, capture, explicit noise.  Results are bit for bit those of the same calls without mppi_arm;
+ * the slide stride between ticks may vary, and mppi_set_control_seq / _hist between arm and compute go through the gate.
+ * Every call that changes what the armed solve would compute (model, cost, costmap, limits, seed, noise, variant, timing,
+ * capture, mppi_rollout_only, mppi_control_ticks, the debug entries, mppi_destroy) calls it off first; the generator stream is
+ * then where it would be had the handle never been armed.  mppi_get_results and mppi_get_applied_controls are served without
+ * waiting on the armed kernels.  A compute that arrives after max_wait_s (a margin inside it) calls the armed solve off and
+ * solves unarmed, with the same bits.  The device's batch stream is shared: a batch of other handles enqueued while a batch is
+ * armed runs after that batch's gate opens. */
+int mppi_arm(mppi_handle *h, double max_wait_s);
+/* The same for the solves of one mppi_compute_control_batch[_async](handles, states, n) call: the shared one-launch form where
+ * the batch would use it (the row form's batched kernel), otherwise each handle armed on its own where it can be
+ * (MPPI_ERR_UNSUPPORTED if one could not be; the others stay armed).  Only a batch call with the same handles in the same order
+ * opens the gates; any other call on one of them calls the whole armed launch off first. */
+int mppi_arm_batch(mppi_handle *const *handles, int n, double max_wait_s);
+/* Calls the armed solve off (its gate opens with the cancel bit); never blocks on the GPU. */
+int mppi_disarm(mppi_handle *h);
+/* 1 while a solve is armed, else 0. */
+int mppi_is_armed(const mppi_handle *h);
 /* mppi_control_ticks for several controllers: n_ticks times { mppi_compute_control_batch; mppi_slide_control_seq
  * (handles[i], stride) for every i } -- the solve part of runControlLoop's tick for its two controllers. */
 int mppi_control_ticks_batch(mppi_handle *const *handles, const float *states, int n, int n_ticks, int stride);

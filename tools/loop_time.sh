@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/loop_time.sh [iterations]: avg_tick_ms of the ROS-free binaries' control loop (two controllers, debug-mode
-# self-simulation, no sleep) with and without feedback gains, on the synthetic oval.  One JSON line per run.
+# self-simulation, no sleep) with and without feedback gains, and with --solve-ahead (the next tick's pair armed), on the
+# synthetic oval.  One JSON line per run.
 cd "$GRAFT_REPO_ROOT" || exit 1
 export PYTHONPATH=$GRAFT_REPO_ROOT
 N=${1:-2000}
@@ -20,6 +21,8 @@ for fb in false true; do
   echo "path_integral_nn K=1920 use_feedback_gains=$fb"
   AR_MPPI_PARAMS_PATH=$D ./autorally_amd/bin/path_integral_nn autorally_amd/host/launch/path_integral_nn.launch --rollouts 1920 --max-iter $N --no-sleep --set x_pos=0.0 --set y_pos=-10.0 --set heading=0.0 --set use_feedback_gains=$fb | tail -1 | cut -c1-330
 done
+echo "path_integral_nn K=1920 use_feedback_gains=false --solve-ahead"
+AR_MPPI_PARAMS_PATH=$D ./autorally_amd/bin/path_integral_nn autorally_amd/host/launch/path_integral_nn.launch --rollouts 1920 --max-iter $N --no-sleep --solve-ahead --set x_pos=0.0 --set y_pos=-10.0 --set heading=0.0 --set use_feedback_gains=false | tail -1 | cut -c1-330
 for fb in false true; do
   echo "path_integral_bf K=2560 use_feedback_gains=$fb"
   AR_MPPI_PARAMS_PATH=$D ./autorally_amd/bin/path_integral_bf autorally_amd/host/launch/path_integral_bf.launch --rollouts 2560 --max-iter $N --no-sleep --set x_pos=0.0 --set y_pos=-10.0 --set heading=0.0 --set use_feedback_gains=$fb | tail -1 | cut -c1-330
