@@ -14,29 +14,12 @@ from autorally_amd import params as P
 from autorally_amd import synthetic as S
 from oracle import oracle as O
 from tests.helpers import noise_for, rel_err
+from tests.ref64 import _np_basis
 
 
 def _bf_cfg(golden_dir, K=256, T=40, track="oval", **over):
     W = P.load_bf_npz(os.path.join(golden_dir, "models", "basis_function_09_12_2018.npz"))
     return S.make_config(K, T, track=track, bf_W=W, **over)
-
-
-def _np_basis(s, u):
-    """float64 numpy restatement of CarBasisFuncs::basisFuncX (car_bfs.cuh:44-120), written
-    independently of the C one, for the values (not the rounding) of the 25 functions."""
-    s4, s5, s6, s3 = float(s[4]), float(s[5]), float(s[6]), float(s[3])
-    u0, u1 = float(u[0]), float(u[1])
-    big = s4 > .1
-    A = np.tan(np.arctan(s5 / s4 + .45 * s6 / s4) - u0) if big else np.tan(-u0)
-    B = (s5 / s4 - .35 * s6 / s4) if big else 0.0
-    su = np.sin(u0)
-    return np.array([
-        u1, s4 / 10.0, su * A / 1200.0, su * A * abs(A) / 1440000.0, su * A ** 3 / 1728000000.0,
-        s6 * s5 / 25.0, s6 / 10.0, s5 / 10.0, su, (s5 / s4 / 40.0) if big else 0.0,
-        A / 1400.0, A * abs(A) / 1960000, A ** 3 / 2744000000,
-        B / 40.0 if big else 0.0, B * abs(B) / 1600.0 if big else 0.0, B ** 3 / 64000.0 if big else 0.0,
-        s6 * s4 / 50.0, s3, s3 * s6, s3 * s4 / 3.0, s3 * s4 * s6 / 5.0, s4 ** 2 / 100.0, s4 ** 3 / 1000.0,
-        u1 ** 2, u1 ** 3])
 
 
 def _samples(n, seed=0):
