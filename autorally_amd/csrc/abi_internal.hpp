@@ -159,14 +159,12 @@ struct mppi_handle {
   float *d_cap = nullptr;
   bool capture = false, cap_valid = false, cap_explicit = false;
   double wait_timeout_s = 30.0;  // mppi_set_wait_timeout
-  // chained control ticks (mppi_control_ticks, abi_solve.hip): the gate block of the solve enqueued one tick ahead --
+  // solve-ahead (mppi_arm, mppi_control_ticks, abi_solve.hip): the gate block of the solve enqueued one tick ahead --
   // kGateReplicas copies of [state[7], gate word], device memory the host stores into through the PCIe BAR where the
   // platform allows it (gate_bar), else host-mapped memory; gate_cpu is the pointer the host writes, d_gate what the kernel reads
   unsigned *gate_cpu = nullptr, *d_gate = nullptr;
   bool gate_bar = false;
   bool chain = true;   // mppi_debug_set_chained_ticks
-  bool ahead = false;  // a gated solve is enqueued behind the pending one
-  float *ahead_vbuf = nullptr;  // where that solve leaves its applied controls
   // The gate block is double-buffered (gate_blk: the block of the latest gated solve; gate_host / gate_dev below): the tail of a
   // gated solve still reads hist from its block after the host has seen its result, when the next gated solve's gate is written.
   int gate_blk = 0;
@@ -177,6 +175,7 @@ struct mppi_handle {
   unsigned seq_floor = 0;        // a called-off solve published under this number: every later solve takes a larger one
   int arm_in = 0;                // d_in_buf the armed solve's tail smooths into (its slid copy: the other one)
   float *arm_vbuf = nullptr;     // where the armed solve leaves its applied controls
+  bool arm_publish_only = false;  // its tail only publishes (inside mppi_control_ticks): the device copy of [U | hist] is stale
   int arm_n = 0;                 // > 0: armed in one launch together with arm_peers[0 .. arm_n) (mppi_arm_batch)
   mppi_handle *arm_peers[4] = {nullptr, nullptr, nullptr, nullptr};
   hipStream_t arm_stream = nullptr;  // the stream the armed solve went to (the handle's own, or the device's batch stream)

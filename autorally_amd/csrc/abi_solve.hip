@@ -77,7 +77,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.inline_noise = 0;
   a.gate = nullptr;
   a.gate_seq = 0;
-  a.gate_ticks = 10000000u;  // 100 ms (mppi_control_ticks); mppi_arm sets its own
+  a.gate_ticks = 10000000u;  // gated launches: armed_args sets it
   a.min_cost = nullptr;  // tag_min_cost
   a.min_cost_tag = 0;
   // roles 32-34 are waits of the streaming tail kernel (tail_launch): the rollout runs with its defaults
@@ -231,10 +231,35 @@ int prefetch_noise(mppi_handle *h)
 
 // the sequence number of the next solve: above every number a solve on this handle published under -- the last one, and a
 // solve called off (solve_ahead_disarm) whose tail kernel still publishes (poisoned) under its own
-static unsigned next_seq(mppi_handle *h)
+static unsigned next_seq(const mppi_handle *h)
 {
-  h->seq = (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
-  return h->seq;
+  return (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
+}
+
+// the tag of the next tail launch's granules (many-chunk solves; never 0)
+static void next_tail_epoch(mppi_handle *h)
+{
+  if (++h->tail_epoch == 0) h->tail_epoch = 1;
+}
+
+// the rollout kernel's noise wavefront draws eps itself, from the generator state the handle is at, and leaves the next one
+static void use_inline_noise(mppi_handle *h, RolloutArgs &a)
+{
+  a.inline_noise = 1;
+  a.rng_in = h->d_rng[h->rng_cur];
+  a.rng_out = h->d_rng[1 - h->rng_cur];
+  h->rng_cur = 1 - h->rng_cur;
+}
+
+// the first batched launch after work on the handle's own streams: that work finishes first
+static int hand_over(mppi_handle *h, hipStream_t batch)
+{
+  if (h->order_stream == batch) return MPPI_OK;
+  hipError_t e = hipStreamSynchronize(work_stream(h));
+  if (e == hipSuccess) e = hipStreamSynchronize(h->gstream);
+  if (e != hipSuccess) return fail(h, MPPI_ERR_HIP, "stream hand-over to the batch stream", e);
+  h->order_stream = batch;
+  return MPPI_OK;
 }
 
 int upload_controls_if_dirty(mppi_handle *h, hipStream_t stream)
@@ -460,7 +485,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
   const bool timed = h->timing && (h->timing_count++ % (unsigned)h->timing_every) == 0;
   const bool explicit_noise = h->explicit_iters > 0;
   const size_t slot_sz = (size_t)K * T * 2;
-  next_seq(h);
+  h->seq = next_seq(h);
   for (int it = 0; it < iters; it++) {
     Events *ev = timed ? &h->ev[it] : nullptr;
     if (ev) HIPCHK(h, hipEventRecord(ev->e[0], h->stream));
@@ -480,12 +505,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
     fill_rollout_args(h, state, noise, a);
     rc = tag_min_cost(h, a, h->stream);
     if (rc) return rc;
-    if (inline_noise) {  // the rollout kernel's noise wavefront draws eps itself
-      a.inline_noise = 1;
-      a.rng_in = h->d_rng[h->rng_cur];
-      a.rng_out = h->d_rng[1 - h->rng_cur];
-      h->rng_cur = 1 - h->rng_cur;
-    }
+    if (inline_noise) use_inline_noise(h, a);
 #ifdef MPPI_HOSTPROF
     HP(1, hp_t0);  // entry -> before the rollout launch
     const auto hp_t1 = std::chrono::steady_clock::now();
@@ -503,7 +523,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
     if (ev) HIPCHK(h, hipEventRecord(ev->e[2], h->stream));
     const bool last = (it == iters - 1);
     const bool want_slid = last && wants_slid_copy(h);
-    if (++h->tail_epoch == 0) h->tail_epoch = 1;  // the tag of this launch's granules
+    next_tail_epoch(h);
     HIPCHK(h, launch_solve_tail(tail_launch(h, noise, last), h->stream));
     if (last) h->slid_valid = want_slid;
     if (h->capture) {  // test hook: what this iteration left (the last iteration's raw U is in the result block)
@@ -534,25 +554,28 @@ int enqueue_solve(mppi_handle *h, const float *state)
   return MPPI_OK;
 }
 
-// ---- chained control ticks -------------------------------------------------------------------------------------------------
-// mppi_control_ticks knows that solve i+1 follows solve i at once.  Its launches -- 2.8 us of launch call and 1.5 us of
-// dispatch for the rollout kernel alone, on the step's critical path between "result i on the host" and "first instruction of
-// rollout i+1" -- are therefore made one tick AHEAD, while the host would otherwise only poll for result i: rollout i+1 (the
-// gated form of the row kernel, rollout_row.hip) and tail i+1 go onto the handle's stream behind tail i, with the buffers
-// solve i+1 will own after the slide (U: the slid copy tail i leaves; its own slid copy: the buffer solve i read).  The
-// rollout starts as soon as tail i has ended, loads its weights, draws its first noise -- and waits for the host's gate: the
-// state of solve i+1 and its sequence number, written into the gate block AFTER the host has seen, smoothed and slid result
-// i.  The step keeps its meaning: solve i+1 computes nothing from the state before the host has result i in hand.
-// tools/ub/gate_ub.hip (profiles/r05_c_gate_ub.txt): 46.3 -> 43.0 us per step for stand-in kernels of the headline's length
-// with the gate in device memory written through the BAR, 44.5 with a host-mapped gate; two streams with the next rollout
-// resident beside the tail: 54 (the cross-stream events cost more than the launches they hide).
-// Results are bit for bit those of the unchained loop (tests/test_api_gpu.py).  Only for the cases that gain: one handle, a
-// latency form with riders (the row form; the automatic m44 form of 64-wide nets) and its in-kernel generator, or the
-// automatic multi4-tree form with its prefetched generator kernel; one iteration, no stage events, no capture, stride =
-// optimization stride.
-// 1: a latency form with riders and its in-kernel generator (the row form, the automatic m44 form); 2: the automatic multi4-tree
-// form with the stand-alone generator kernel prefetched on a second stream; 0: not chained
-// (also the forms mppi_arm enqueues ahead: arm_kind)
+// ---- solve-ahead (mppi_arm, mppi_control_ticks) ----------------------------------------------------------------------------
+// The launches of a solve -- 2.8 us of launch call and 1.5 us of dispatch for the rollout kernel alone, on the step's critical
+// path between "result i on the host" and "first instruction of rollout i+1" -- are made one solve AHEAD, while the host would
+// otherwise only poll for result i: mppi_arm enqueues the handle's NEXT solve now, gated, behind a pending solve or on an idle
+// stream.  Its kernels start, load their weights, draw their first noise and wait; the next mppi_compute_control[_async] does
+// not launch: it writes ITS state, the host's U (smoothed and slid, as the reference uploads U_ with every computeControl,
+// mppi_controller.cu:608-610) and hist into the gate block and opens the gate.  The solve computes nothing from its inputs before
+// the host holds result i.  tools/ub/gate_ub.hip (profiles/r05_c_gate_ub.txt): 46.3 -> 43.0 us per step for stand-in kernels of
+// the headline's length with the gate in device memory written through the BAR, 44.5 with a host-mapped gate; two streams with
+// the next rollout resident beside the tail: 54 (the cross-stream events cost more than the launches they hide).
+// mppi_control_ticks (chained ticks) is a loop over the pair in which every armed solve but the last has a publish-only tail: no
+// workgroup smooths a device copy nobody reads, the kernel ends 2.5 us earlier, and the next rollout starts when it ends.
+// Results are bit for bit those of the same calls without mppi_arm.  What the armed solve changes before its gate opens is all
+// undone by solve_ahead_disarm: its costs / weights go to the second pair of vectors, its applied controls to the generator buffer
+// nobody reads, its generator draw (kind 1: the rng_cur flip; kind 2: the prefetched draws, regenerated) is put back, and the
+// sequence number it publishes under is never used again.  The device copy of [U | hist] is not kept up while armed (u_dirty:
+// slides are the host's alone); the armed tail rewrites both buffers (a publish-only one neither), and the gate's opening points
+// d_in at the one it smooths into.
+
+// The forms that have a gated rollout and gain from it (one iteration, no stage events, no capture): 1: a latency form with
+// riders (the row forms, the automatic m44 form) and its in-kernel generator; 2: the automatic multi4-tree form with the
+// stand-alone generator kernel prefetched on a second stream; 0: none
 static int arm_kind(const mppi_handle *h)
 {
   if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
@@ -565,150 +588,27 @@ static int arm_kind(const mppi_handle *h)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;
   return 0;
 }
-static int chain_kind(const mppi_handle *h, int n_ticks, int stride)
-{
-  if (!(h->chain && n_ticks >= 2 && stride == h->cfg.optimization_stride)) return 0;
-  return arm_kind(h);
-}
 
-// the gate block of solve `word`: its nominal sequence and history (the host's copies, smoothed and slid), its state in every
-// replica, then (fenced) the gate word in every replica
-static void write_gate(mppi_handle *h, const float *state, unsigned word)
+// the armed solve's gate block: its nominal sequence and history (the host's copies, smoothed and slid), its state in every
+// replica (memcpy: wide stores -- the block is write-combining memory behind the PCIe BAR where gate_bar is set)
+static void write_gate_payload(mppi_handle *h, const float *state)
 {
-  // (memcpy: wide stores -- the block is write-combining memory behind the PCIe BAR where gate_bar is set; the fences order the
-  // payload before the gate words and push both out)
   unsigned *g = gate_host(h);
   const int T = h->T;
   memcpy(g + kGateUOffset, h->U.data(), sizeof(float) * 2 * (size_t)T);
   memcpy(g + gate_hist_offset(T), h->hist.data(), sizeof(float) * 4);
   for (int r = 0; r < kGateReplicas; r++) memcpy(g + 16 * r, state, sizeof(float) * kStateDim);
+}
+
+// the gate word in every replica; the fences order whatever was written before in front of it and push it out
+static void write_gate_word(mppi_handle *h, unsigned word)
+{
+  unsigned *g = gate_host(h);
   asm volatile("" ::: "memory");
   __builtin_ia32_sfence();
   for (int r = 0; r < kGateReplicas; r++) __atomic_store_n(g + 16 * r + 7, word, __ATOMIC_RELAXED);
   __builtin_ia32_sfence();
 }
-
-// solve (h->seq + 1), gated, behind the pending solve h->seq.  Its rollout takes state AND nominal sequence from the gate
-// block (the host has both in hand when it opens the gate: U smoothed and slid, as the reference uploads U_ with every
-// computeControl, mppi_controller.cu:608-610).  Its tail: inside the chain only the publication (no workgroup smooths a device
-// copy nobody reads: the kernel ends 2.5 us earlier, and the next rollout starts when it ends); the LAST solve of the chain
-// smooths and leaves the slid copy as every ordinary solve does, with hist from the gate block, so that the handle's device
-// state after the chain is the unchained loop's.
-static int enqueue_ahead(mppi_handle *h, const float *state, bool last_of_chain, int kind)
-{
-  float *noise = h->d_gen[h->gen_cur];  // kind 1: the in-kernel generator's solves all leave their applied controls here
-  int rc = MPPI_OK;
-  if (kind == 2) {
-    // The generator-kernel forms: this solve's eps were prefetched on gstream (into the other buffer) when the host opened the
-    // gate of the solve before.  The NEXT prefetch is NOT enqueued ahead: it writes the buffer the pending solve's tail kernel
-    // still reads, and -- measured -- a generator launch that becomes ready together with the rollout (both behind the same
-    // tail kernel) takes the CUs first and costs its whole stand-alone time (config 4: 0.2651 -> 0.2834 ms, K = 16 384: 0.0978 ->
-    // 0.1071; behind the rollout: 0.2837 / 0.1143; lowest stream priority for the generator: 0.2781).  The host launches it
-    // when it opens this solve's gate (control_ticks_chained): a few microseconds behind the rollout's start, where it has
-    // always been, filling the dynamics waves' bubbles.
-    if (!h->prefetch_valid) return fail(h, MPPI_ERR_STATE, "chained ticks: no prefetched draws");
-    rc = acquire_noise(h, &noise);
-    if (rc) return rc;
-  }
-  h->gate_blk ^= 1;  // this solve's gate block; the pending solve's tail may still read its own
-  RolloutArgs a;
-  fill_rollout_args(h, state, noise, a);
-  rc = tag_min_cost(h, a, h->stream);
-  if (rc) return rc;
-  a.U = reinterpret_cast<const float *>(gate_dev(h)) + kGateUOffset;
-  if (kind == 1) {
-    a.inline_noise = 1;
-    a.rng_in = h->d_rng[h->rng_cur];
-    a.rng_out = h->d_rng[1 - h->rng_cur];
-    h->rng_cur = 1 - h->rng_cur;
-  }
-  a.gate = gate_dev(h);
-  a.gate_seq = h->seq + 1;
-  rc = launch_rollout(h, a);
-  if (rc) return rc;
-  if (kind == 2) HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));
-  if (++h->tail_epoch == 0) h->tail_epoch = 1;  // the tag of this tail launch's granules (many-chunk solves)
-  TailLaunch l = tail_launch(h, noise, true);
-  l.seq = h->seq + 1;
-  l.hist = reinterpret_cast<const float *>(gate_dev(h)) + gate_hist_offset(h->T);
-  if (last_of_chain) {
-    l.U = h->d_in;
-    l.hist_out = h->d_in + 2 * h->T;
-    l.slid = h->d_in_buf[1 - h->in_cur];
-  } else {
-    l.no_device_copy = 1;
-    l.slid = nullptr;
-  }
-  HIPCHK(h, launch_solve_tail(l, h->stream));
-  h->ahead = true;
-  h->ahead_vbuf = noise;
-  return MPPI_OK;
-}
-
-// the solve enqueued ahead is called off: its gate opens with the cancel bit (the kernels run through, poisoned); nothing on
-// the device can be trusted afterwards -- the host copies are uploaded again by the next solve
-static void cancel_ahead(mppi_handle *h, const float *state)
-{
-  write_gate(h, state, (h->seq + 1) | kGateCancel);
-  (void)hipStreamSynchronize(h->stream);
-  h->seq++;  // the called-off solve's tail kernel has published (poisoned) entries under that number: it is spent
-  h->ahead = false;
-  h->u_dirty = true;
-  h->slid_valid = false;
-}
-
-static int control_ticks_chained(mppi_handle *h, const float *state, int n_ticks, int stride, int kind)
-{
-  HIPCHK(h, ensure_device(h->cfg.device));
-  int rc = enqueue_solve(h, state);
-  if (rc) return rc;
-  for (int i = 0; i < n_ticks; i++) {
-    const bool ahead = i + 1 < n_ticks, ahead_is_last = i + 2 == n_ticks;
-    if (ahead) {
-      rc = enqueue_ahead(h, state, ahead_is_last, kind);
-      if (rc) {
-        (void)wait_pending(h);
-        return rc;
-      }
-    }
-    rc = wait_pending(h);
-    if (rc == MPPI_OK) {
-      // inside the chain the device copy of U is not kept up (the next solve reads the host's through the gate block): the
-      // slide is the host's alone; the last solve's tail restores it, and the slide behind it swaps to its slid copy as usual
-      if (ahead) { h->u_dirty = true; h->slid_valid = false; }
-      rc = mppi_slide_control_seq(h, stride);
-    }
-    if (rc) {
-      if (ahead) cancel_ahead(h, state);
-      return rc;
-    }
-    if (ahead) {  // the host has result i, smoothed and slid: solve i+1 may start
-      h->seq++;
-      write_gate(h, state, h->seq);
-      if (kind == 2) {  // the draws of the solve after it, behind the opened gate (enqueue_solve: prefetch_noise behind the tail launch)
-        rc = prefetch_noise(h);
-        if (rc) return rc;
-      }
-      h->ahead = false;
-      h->pending = true;
-      h->pending_timed = false;
-      h->v_buf = h->ahead_vbuf;
-      if (ahead_is_last) { h->u_dirty = false; h->slid_valid = true; }  // its tail smooths h->d_in and leaves the slid copy
-    }
-  }
-  return MPPI_OK;
-}
-
-// ---- solve-ahead (mppi_arm) ------------------------------------------------------------------------------------------------
-// The chained ticks' mechanism for any caller: mppi_arm enqueues the handle's NEXT solve now, gated (enqueue_ahead's rollout and
-// the ordinary tail -- smoothing and the slid copy, as the last solve of a chain), behind a pending solve or on an idle stream.
-// Its kernels start, load their weights, draw their first noise and wait; the next mppi_compute_control[_async] does not launch:
-// it writes ITS state, the host's U and hist into the gate block and opens the gate.  Results are bit for bit those of the same
-// calls without mppi_arm.  What the armed solve changes before its gate opens is all undone by solve_ahead_disarm: its costs /
-// weights go to the second pair of vectors, its applied controls to the generator buffer nobody reads, its generator draw
-// (kind 1: the rng_cur flip; kind 2: the prefetched draws, regenerated) is put back, and the sequence number it publishes under is
-// never used again.  The device copy of [U | hist] is not kept up while armed (u_dirty: slides are the host's alone); the
-// armed tail rewrites both buffers, and the gate's opening points d_in at the one it smooths into.
 
 // max_wait_s in 100 MHz ticks; the host opens the gate only inside a margin of that (the kernels' clock starts when they do,
 // which is after the arming call): a gate opened in time is never one the kernels have given up on
@@ -740,7 +640,7 @@ static void armed_args(mppi_handle *h, float *noise, RolloutArgs &a, TailLaunch 
 }
 
 // the handle's bookkeeping once its armed solve is on a stream
-static void mark_armed(mppi_handle *h, int kind, float *vbuf, hipStream_t stream, double max_wait_s)
+static void mark_armed(mppi_handle *h, int kind, float *vbuf, hipStream_t stream, double max_wait_s, bool publish_only)
 {
   h->armed = kind;
   h->arm_in = h->in_cur;
@@ -748,18 +648,19 @@ static void mark_armed(mppi_handle *h, int kind, float *vbuf, hipStream_t stream
   h->arm_stream = stream;
   h->arm_until = arm_deadline(max_wait_s);
   h->arm_n = 0;
+  h->arm_publish_only = publish_only;
   h->u_dirty = true;  // slides until the gate opens are the host's alone (a device slide would queue behind the gated kernel)
   h->slid_valid = false;
 }
 
-static int arm_one(mppi_handle *h, double max_wait_s)
+// One handle's armed solve, everything but its launches on `stream` (mppi_arm, mppi_arm_batch, the chained ticks).  Two facts
+// only the chained ticks set: publish_only -- the tail publishes the result and leaves the device copy alone (every armed solve of
+// a run but the last); mark -- ev_arm in front of the solve, for the result getters while armed (none runs inside the ticks).
+static int arm_handle(mppi_handle *h, int kind, hipStream_t stream, double max_wait_s, bool publish_only, bool mark,
+                      RolloutArgs &a, TailLaunch &l)
 {
-  const int kind = arm_kind(h);
-  if (!kind) return fail(h, MPPI_ERR_UNSUPPORTED, "this handle's form / configuration has no gated form (mppi_arm)");
-  HIPCHK(h, ensure_device(h->cfg.device));
-  OWN(h);  // behind a pending batched solve: the batch stream hands over first (as a solve on the handle's own stream does)
-  h->arm_seq = (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
-  h->gate_blk ^= 1;
+  h->arm_seq = next_seq(h);
+  h->gate_blk ^= 1;  // this solve's gate block; the pending solve's tail may still read its own
   float *noise = h->d_gen[1 - h->gen_cur];  // kind 1: the in-kernel generator's applied controls go to the buffer nobody reads
   if (kind == 2) {
     // the draws prefetched for this solve (or, if none are, generated now behind the stream's work); solve_ahead_disarm puts
@@ -767,25 +668,34 @@ static int arm_one(mppi_handle *h, double max_wait_s)
     int rc = acquire_noise(h, &noise);
     if (rc) return rc;
   }
-  HIPCHK(h, hipEventRecord(h->ev_arm, h->stream));
-  RolloutArgs a;
-  TailLaunch l;
+  if (mark) HIPCHK(h, hipEventRecord(h->ev_arm, stream));
   armed_args(h, noise, a, l, max_wait_s);
-  int rc = tag_min_cost(h, a, h->stream);
+  int rc = tag_min_cost(h, a, stream);
   if (rc) return rc;
   l.min_cost_tag = h->min_cost_tag;
-  if (kind == 1) {
-    a.inline_noise = 1;
-    a.rng_in = h->d_rng[h->rng_cur];
-    a.rng_out = h->d_rng[1 - h->rng_cur];
-    h->rng_cur = 1 - h->rng_cur;
+  if (publish_only) {
+    l.no_device_copy = 1;
+    l.slid = nullptr;
   }
-  // from here on the handle is armed (a launch error below is called off like any armed solve)
-  mark_armed(h, kind, noise, h->stream, max_wait_s);
+  if (kind == 1) use_inline_noise(h, a);
+  next_tail_epoch(h);
+  l.epoch = h->tail_epoch;
+  // from here on the handle is armed (a launch error is called off like any armed solve)
+  mark_armed(h, kind, noise, stream, max_wait_s, publish_only);
+  return MPPI_OK;
+}
+
+static int arm_one(mppi_handle *h, double max_wait_s, bool publish_only, bool mark)
+{
+  const int kind = arm_kind(h);
+  if (!kind) return fail(h, MPPI_ERR_UNSUPPORTED, "this handle's form / configuration has no gated form (mppi_arm)");
+  OWN(h);  // behind a pending batched solve: the batch stream hands over first (as a solve on the handle's own stream does)
+  RolloutArgs a;
+  TailLaunch l;
+  int rc = arm_handle(h, kind, h->stream, max_wait_s, publish_only, mark, a, l);
+  if (rc) return rc;
   rc = launch_rollout(h, a);
   if (rc == MPPI_OK) {
-    if (++h->tail_epoch == 0) h->tail_epoch = 1;
-    l.epoch = h->tail_epoch;
     const hipError_t e = launch_solve_tail(l, h->stream);
     if (e != hipSuccess) rc = fail(h, MPPI_ERR_HIP, "armed tail launch", e);
   }
@@ -800,9 +710,7 @@ static int disarm_one(mppi_handle *h)
   const int kind = h->armed;
   h->armed = 0;
   h->arm_n = 0;
-  unsigned *g = gate_host(h);
-  for (int r = 0; r < kGateReplicas; r++) __atomic_store_n(g + 16 * r + 7, h->arm_seq | kGateCancel, __ATOMIC_RELAXED);
-  __builtin_ia32_sfence();
+  write_gate_word(h, h->arm_seq | kGateCancel);
   // its tail publishes (poisoned) under arm_seq and rewrites both device copies of [U | hist]
   h->seq_floor = h->arm_seq;
   h->u_dirty = true;
@@ -860,7 +768,8 @@ static int open_armed(mppi_handle *h, const float *state)
   h->armed = 0;
   h->arm_n = 0;
   h->seq = h->arm_seq;
-  write_gate(h, state, h->seq);
+  write_gate_payload(h, state);
+  write_gate_word(h, h->seq);
   h->order_stream = h->arm_stream;
   std::swap(h->d_costs, h->d_costs_alt);
   std::swap(h->d_w, h->d_w_alt);
@@ -868,9 +777,14 @@ static int open_armed(mppi_handle *h, const float *state)
   if (kind == 1) h->gen_cur = h->arm_vbuf == h->d_gen[0] ? 0 : 1;
   h->in_cur = h->arm_in;
   h->d_in = h->d_in_buf[h->in_cur];
-  h->u_dirty = false;  // the armed tail smooths into d_in and leaves the slid copy in the other buffer
-  h->slid_valid = true;
-  if (kind == 2) {  // the draws of the solve after it, behind the opened gate (as the chained ticks do)
+  // the armed tail smooths into d_in and leaves the slid copy in the other buffer; a publish-only tail neither
+  h->u_dirty = h->arm_publish_only;
+  h->slid_valid = !h->arm_publish_only;
+  if (kind == 2) {
+    // the draws of the solve after it, behind the opened gate, NOT at arming: a generator launch that becomes ready together with
+    // the gated rollout (both behind the same tail kernel) takes the CUs first and costs its whole stand-alone time (config 4:
+    // 0.2651 -> 0.2834 ms, K = 16 384: 0.0978 -> 0.1071; behind the rollout: 0.2837 / 0.1143; lowest stream priority for the
+    // generator: 0.2781).  Here it is a few microseconds behind the rollout's start, filling the dynamics waves' bubbles.
     const int rc = prefetch_noise(h);
     if (rc) {
       h->pending = true;
@@ -897,47 +811,20 @@ static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
   if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
   const hipStream_t S = h0->batch_s;
   if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    if (h->order_stream != S) {  // the hand-over to the batch stream, as mppi_compute_control_batch_async makes it
-      hipError_t e = hipStreamSynchronize(h->order_stream ? h->order_stream : h->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(h->gstream);
-      if (e != hipSuccess) return fail(h, MPPI_ERR_HIP, "armed batch: stream hand-over", e);
-      h->order_stream = S;
-    }
-  }
+  for (int i = 0; i < n; i++)
+    if (int rc = hand_over(hs[i], S)) return rc;
   QuadBatchArgs qb;
   TailLaunch tl[kMaxBatch];
   qb.n = n;
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    h->arm_seq = (h->seq_floor - h->seq < 0x80000000u ? h->seq_floor : h->seq) + 1;
-    h->gate_blk ^= 1;
-    float *noise = h->d_gen[1 - h->gen_cur];
-    HIPCHK(h, hipEventRecord(h->ev_arm, S));
-    RolloutArgs &a = qb.inst[i];
-    armed_args(h, noise, a, tl[i], max_wait_s);
-    if (int trc = tag_min_cost(h, a, S)) return trc;
-    tl[i].min_cost_tag = h->min_cost_tag;
-    a.inline_noise = 1;
-    a.rng_in = h->d_rng[h->rng_cur];
-    a.rng_out = h->d_rng[1 - h->rng_cur];
-    h->rng_cur = 1 - h->rng_cur;
-    mark_armed(h, 1, noise, S, max_wait_s);
-  }
+  for (int i = 0; i < n; i++)
+    if (int rc = arm_handle(hs[i], 1, S, max_wait_s, false, true, qb.inst[i], tl[i])) return rc;
   for (int i = 0; i < n; i++) {
     hs[i]->arm_n = n;
     for (int q = 0; q < n; q++) hs[i]->arm_peers[q] = hs[q];
   }
   for (int i = n; i < kMaxBatch; i++) qb.inst[i] = qb.inst[0];
   hipError_t e = launch_rollout_row_batch(qb, form_of(h0) == Form::RowTree, S);
-  if (e == hipSuccess) {
-    for (int i = 0; i < n; i++) {
-      if (++hs[i]->tail_epoch == 0) hs[i]->tail_epoch = 1;
-      tl[i].epoch = hs[i]->tail_epoch;
-    }
-    e = launch_solve_tail_batch(tl, n, S);
-  }
+  if (e == hipSuccess) e = launch_solve_tail_batch(tl, n, S);
   if (e != hipSuccess) {
     const int rc = fail(h0, MPPI_ERR_HIP, "armed batched launch", e);
     (void)solve_ahead_disarm(h0);
@@ -1099,16 +986,10 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
   HB(3);  // wait_pending of every handle
   for (int i = 0; i < n; i++) {
     mppi_handle *h = hs[i];
-    int rc = MPPI_OK;
-    if (h->order_stream != S) {  // first batched solve after work on the handle's own streams: let that finish
-      hipError_t e = hipStreamSynchronize(h->order_stream ? h->order_stream : h->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(h->gstream);
-      if (e != hipSuccess) return poison(fail(h, MPPI_ERR_HIP, "batched solve: stream hand-over", e));
-      h->order_stream = S;
-    }
-    rc = upload_controls_if_dirty(h, S);
+    int rc = hand_over(h, S);
+    if (rc == MPPI_OK) rc = upload_controls_if_dirty(h, S);
     if (rc) return poison(rc);
-    next_seq(h);
+    h->seq = next_seq(h);
   }
   for (int it = 0; it < iters; it++) {
     QuadBatchArgs qb;
@@ -1124,12 +1005,7 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
       RolloutArgs &a = qb.inst[i];
       fill_rollout_args(h, states + (size_t)MPPI_STATE_DIM * i, noise, a);
       if (int trc = tag_min_cost(h, a, S)) return trc;
-      if (!explicit_noise) {
-        a.inline_noise = 1;
-        a.rng_in = h->d_rng[h->rng_cur];
-        a.rng_out = h->d_rng[1 - h->rng_cur];
-        h->rng_cur = 1 - h->rng_cur;
-      }
+      if (!explicit_noise) use_inline_noise(h, a);
       tl[i] = tail_launch(h, noise, last);
       if (last) h->slid_valid = wants_slid_copy(h);
     }
@@ -1183,8 +1059,20 @@ int mppi_control_ticks(mppi_handle *h, const float state[MPPI_STATE_DIM], int n_
 {
   if (!h || n_ticks < 0 || stride < 0) return MPPI_ERR_INVALID;
   DISARM(h);
-  const int kind = state ? chain_kind(h, n_ticks, stride) : 0;
-  if (kind) return control_ticks_chained(h, state, n_ticks, stride, kind);
+  if (state && h->chain && n_ticks >= 2 && stride == h->cfg.optimization_stride && arm_kind(h)) {
+    // chained: tick i+1 is armed behind solve i (kernel deadline 100 ms), its gate opened once the host holds result i, slid
+    HIPCHK(h, ensure_device(h->cfg.device));
+    int rc = enqueue_solve(h, state);
+    for (int i = 0; i < n_ticks && rc == MPPI_OK; i++) {
+      const bool ahead = i + 1 < n_ticks;
+      if (ahead) rc = arm_one(h, 0.1, i + 2 < n_ticks, false);
+      if (rc == MPPI_OK) rc = wait_pending(h);
+      if (rc == MPPI_OK) rc = mppi_slide_control_seq(h, stride);
+      if (rc == MPPI_OK && ahead) rc = enqueue_solve(h, state);
+    }
+    if (rc) (void)solve_ahead_disarm(h);  // never blocks
+    return rc;
+  }
   for (int i = 0; i < n_ticks; i++) {
     int rc = mppi_compute_control(h, state);
     if (rc) return rc;
@@ -1271,12 +1159,7 @@ int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
   h->v_buf = noise;
   RolloutArgs a;
   fill_rollout_args(h, state, noise, a);
-  if (inline_noise) {
-    a.inline_noise = 1;
-    a.rng_in = h->d_rng[h->rng_cur];
-    a.rng_out = h->d_rng[1 - h->rng_cur];
-    h->rng_cur = 1 - h->rng_cur;
-  }
+  if (inline_noise) use_inline_noise(h, a);
   rc = launch_rollout(h, a);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(costs, h->d_costs, sizeof(float) * h->K, hipMemcpyDeviceToHost, h->stream));
@@ -1345,7 +1228,8 @@ int mppi_arm(mppi_handle *h, double max_wait_s)
   if (!h || !(max_wait_s > 0.0 && max_wait_s <= 0.1)) return MPPI_ERR_INVALID;
   if (h->armed && h->arm_n == 0) return MPPI_OK;  // already armed
   DISARM(h);  // (armed as part of a batch)
-  return arm_one(h, max_wait_s);
+  HIPCHK(h, ensure_device(h->cfg.device));
+  return arm_one(h, max_wait_s, false, true);
 }
 
 int mppi_arm_batch(mppi_handle *const *hs, int n, double max_wait_s)

@@ -394,6 +394,7 @@ def test_chained_control_ticks_equal_the_unchained_loop_bit_for_bit(K, T, varian
     sols[1].debug_set_chained_ticks(0)
     n = 23
     sols[0].control_ticks(st, n, opt)   # chained
+    assert not sols[0].is_armed()       # the ticks never leave the handle armed
     sols[1].control_ticks(st, n, opt)   # every solve launched when its turn comes
     for _ in range(n):                  # one ABI call per step
         sols[2].compute_control(st)
@@ -413,6 +414,7 @@ def test_chained_control_ticks_equal_the_unchained_loop_bit_for_bit(K, T, varian
     # a second chained call on the same handle, after an ordinary solve in between
     sols[0].slide_control_seq(opt); sols[1].slide_control_seq(opt)
     sols[0].control_ticks(st, 5, opt); sols[1].control_ticks(st, 5, opt)
+    assert not sols[0].is_armed()
     np.testing.assert_array_equal(sols[0].get_control_seq().view(np.uint32), sols[1].get_control_seq().view(np.uint32))
     for sol in sols:
         sol.close()
@@ -537,6 +539,7 @@ def test_an_error_inside_chained_ticks_calls_the_solve_ahead_off(K, T):
         sol.control_ticks(st, 6, 1)
     assert e.value.status == capi.ERR_HIP and "timed out" in str(e.value)
     assert time.perf_counter() - t0 < 0.05  # the solve ahead was called off at once, not left to its deadline
+    assert not sol.is_armed()
     sol.set_wait_timeout(30.0)
     U, hist = sol.get_control_seq().copy(), sol.get_control_hist().copy()
     deadline = time.perf_counter() + 5.0
