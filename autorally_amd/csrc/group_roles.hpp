@@ -198,6 +198,9 @@ __device__ __forceinline__ void group_control_wave(const RolloutArgs &a, SH &sh,
     float2 e = (live && !inl) ? noise[(size_t)tl * K + k] : make_float2(0.0f, 0.0f);
     // the last slot of the chunk: slot t % kGRing held step t - kGRing -- the dynamics waves read it during step
     // t - kGRing - 1 (done once all of them published the first swap of step t - kGRing), the cost wave in step t - kGRing
+    // (the row forms publish xseq once per aligned chunk of four steps, rollout_row.hip: the test then passes up to three
+    // steps later, this wave leads the dynamics waves by 13 steps instead of 16; it still publishes through step 12
+    // without looking at xseq, so nobody waits in a circle)
     const int tm = min(t0 + n, T) - 1;
     const int need_x = (tm >= kGRing) ? (tm - kGRing) * NSW + 1 : 0;
     const int need_c = tm - kGRing + 1;

@@ -21,7 +21,9 @@
 //   * lanes 0 and 1 of a row hold the state pair (s3, s4) / (s5, s6) (every even / odd lane computes the same two
 //     outputs), so layer 0 of the next step reads the new state through four of the same moves;
 //   * state records, controls, texels, noise: the rings and riders of group_roles.hpp, one rider per SIMD beside one
-//     dynamics wave.
+//     dynamics wave.  The riders work in chunks of four steps, so the dynamics waves hand over per chunk too: one sequence
+//     word and one look at the control wave's count per four steps, ring slots as instruction offsets (row_step,
+//     row_dynamics: the invariants are written down there).
 #include "group_roles.hpp"
 #include "mppi_kernels.hpp"
 
@@ -196,10 +198,112 @@ __device__ __forceinline__ float row_out_tree(const f32x2 *w3, f32x2 a)
   return v0;
 }
 
+// One network step of a dynamics wave, at position Q of its aligned chunk of four steps [t0, t0 + 4) -- the T loop of
+// row_dynamics below is this body four times.  What a step does besides the network is wired to Q at compile time:
+//   * ring slots: slot (t0 + Q) % kGRing = (t0 % kGRing) + Q never wraps inside an aligned chunk, so the state record goes to
+//     the chunk's address a_rec plus Q slots and the controls of step t + 1 come from the chunk's pointer pu plus Q + 1
+//     slots, both in the `offset:` field of the LDS instruction.  Only the read of Q = 3 leaves the chunk: it moves pu on
+//     to the next chunk (the one address add of a chunk besides a_rec's);
+//   * the sequence word is published by Q = 3 only, with value t0 + 4 (see the hand-over invariants at row_dynamics);
+//   * the control wave's count is READ by Q = 0 only, into the SGPR cp every step of the chunk tests.
+template <int H, bool TREE, int Q>
+__device__ __forceinline__ void row_step(const RolloutArgs &a, const RowWeights<H, TREE> &W, f32x2 &sp, f32x2 &un, const int t0,
+                                         const uint32_t a_rec, const uint32_t a_myseq, const volatile int __attribute__((address_space(3))) *p_pub,
+                                         const volatile f32x2 __attribute__((address_space(3))) *&pu,
+                                         const volatile f32x2 __attribute__((address_space(3))) *p_u0, int &cp, int &budget)
+{
+  constexpr int kSlotF2 = kRolloutsPerWave * 2;  // f32x2 per ring slot of ctl_rec (and of rec)
+  constexpr uint32_t kRecStride = sizeof(float) * kRolloutsPerWave * 4;
+  const int t = t0 + Q;
+  const f32x2 u = un;
+  const f32x2 slo = TREE ? f32x2{row_bc<0>(sp.x), row_bc<4>(sp.x)} : f32x2{row_bc<0>(sp.x), row_bc<0>(sp.y)};    // (s3, s4)
+  const f32x2 shi = TREE ? f32x2{row_bc<8>(sp.x), row_bc<12>(sp.x)} : f32x2{row_bc<1>(sp.x), row_bc<1>(sp.y)};  // (s5, s6)
+  // record for the pose / cost waves: the state BEFORE the update (the ring slot is free: see the end of the step);
+  // behind the chunk's last record the publication -- which also says: this wave is done with the control records of
+  // steps <= t
+  if constexpr (TREE) asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(a_rec), "v"(sp.x), "n"(Q * kRecStride) : "memory");
+  else asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(a_rec), "v"(sp), "n"(Q * kRecStride) : "memory");
+  if constexpr (Q == 3) lds_publish(a_myseq, t + 1);
+  // layer 0: [s3, s4, s5, s6, u0, u1]
+  f32x2 z = {0.0f, 0.0f};
+  z = __builtin_elementwise_fma(W.w1[0], f32x2{slo.x, slo.x}, z);
+  z = __builtin_elementwise_fma(W.w1[1], f32x2{slo.y, slo.y}, z);
+  z = __builtin_elementwise_fma(W.w1[2], f32x2{shi.x, shi.x}, z);
+  z = __builtin_elementwise_fma(W.w1[3], f32x2{shi.y, shi.y}, z);
+  z = __builtin_elementwise_fma(W.w1[4], f32x2{u.x, u.x}, z);
+  z = __builtin_elementwise_fma(W.w1[5], f32x2{u.y, u.y}, z);
+  // Requested now, used at the end of the step: (Q = 0) the control wave's count, then this rollout's controls of step
+  // t+1 as ONE 8-B read into the pair the packed multiply-adds of layer 0 take them from (valid if the count read before
+  // them is >= t+2).  In FRONT of layer 1: the chains below have no LDS wait of their own to hide these reads behind, and a
+  // read that is still in flight when a chain starts stalls it (the packed multiply-adds formally read the odd halves of
+  // the move registers, which is where the register allocator puts pending results: rollout 55.0 -> 52.4 us with the
+  // reads moved here).
+  int cp_v = 0;
+  if constexpr (Q == 0) cp_v = *p_pub;
+  if constexpr (Q == 3) pu = p_u0 + ((t + 1) & (kGRing - 1)) * kSlotF2;  // the next chunk's slots
+  constexpr int kUn = (Q == 3) ? 0 : (Q + 1) * kSlotF2;
+  un = pu[kUn];
+  const f32x2 a0 = tanh_bias2(z, W.b1s);
+  const f32x2 a1 = tanh_bias2(row_dot_bc(W.w2, a0), W.b2s);
+  // Step t+1 may start when the control wave has published it (it runs ahead).  That also says that the ring slot of
+  // the state record of step t+1 is free -- it held step t+1 - kGRing, consumed once cost_done >= t+2 - kGRing: the
+  // control wave publishes a chunk that ends with step tm >= t+1 only after it has seen cost_done >= tm+1 - kGRing
+  // (group_control_wave: need_c; the control record of a step shares the slot index of its state record), so this wave
+  // does not look at the cost wave's word itself.
+  // (A shorter leash for the riders -- waiting when the cost wave is more than 2 / 3 / 5 steps behind instead of a full
+  // ring -- was measured: 124 / 72.6 / 58.0 us against 55.2 us; the riders need the slack.)
+  // The control wave publishes whole chunks (1, 5, 9, ..., T), so the count Q = 0 has read covers the chunk's other
+  // steps as a rule: they test the SGPR and read nothing.
+  // The scalar side of the test in front of the output layer's chain, the (cold) wait behind it.
+  const int want = t + 2;
+  if constexpr (Q == 0) cp = __builtin_amdgcn_readfirstlane(cp_v);
+  asm volatile("" : "+v"(un));  // the wait for the reads sits HERE (long arrived), not behind the next step's LDS stores
+  if constexpr (TREE) {
+    const float d = row_out_tree(W.w3, a1) + W.b3.x;
+    sp.x = fmaf(d, a.dt, sp.x);  // incrementState, neural_net_model.cu:334-344
+    asm volatile("" : "+v"(sp.x));
+  } else {
+    const f32x2 d = row_dot_bc(W.w3, a1) + W.b3;
+    sp = __builtin_elementwise_fma(d, f32x2{a.dt, a.dt}, sp);  // incrementState, neural_net_model.cu:334-344
+    asm volatile("" : "+v"(sp));  // the chain stays here (otherwise it is sunk below the wait, away from its moves)
+  }
+  if (__builtin_expect(cp < want, 0)) {  // any Q: the per-step test-and-poll, one unit of the budget per poll
+    while (cp < want && --budget > 0) {
+      cp = __builtin_amdgcn_readfirstlane(*p_pub);
+      un = pu[kUn];
+    }
+    asm volatile("" : "+v"(un));  // (its wait too: otherwise the merge of the two paths puts one behind the next step's stores)
+  }
+}
+
+// The dynamics wave w of a group: T - 1 network steps in aligned chunks of four, the state record of every step.
+//
+// Hand-over with the riders (group_roles.hpp), per CHUNK of four steps -- the riders work in chunks of four, so a word per
+// step told nobody anything:
+//   * xseq[w] = t0 + 4 is published once per chunk, behind the record of step t0 + 3 (and T behind the record of step
+//     T - 1, which also closes a shorter last chunk).  xseq[w] >= s + 1 still means: the records of steps <= s are written,
+//     and the control records of steps <= s are read (the controls of step t0 + 3 were read during step t0 + 2).
+//   (a) The pose wave (and through pose_pub the cost wave) waits for the LAST record of its chunk, need = tend: it sees a
+//       chunk exactly when it did with a word per step.
+//   (b) The control wave tests xseq only for the reuse of a ring slot, need_x = tm - kGRing + 1 for a chunk that ends with
+//       step tm = 4 m: with xseq a multiple of four that is xseq >= tm - 12, i.e. the record of step tm - 13 is out -- the
+//       control wave leads the slowest dynamics wave by up to 13 steps where it led by 16.
+//   (c) No cycle: the control wave publishes through step 12 without looking at xseq (need_x = 0 while tm < kGRing), which
+//       lets the dynamics waves publish 4, 8, 12; from then on chunk tm needs the record of step tm - 13, which needs
+//       ctl_pub >= tm - 12, published with chunk tm - 12.
+//   (d) Every wait is one unit of the wave's poll budget, as before; a wave whose budget ran out (or that was started with
+//       none: a.fault_wave) stops waiting, runs to its end and raises fail through spin_finish.
+//   * ctl_pub is read once per chunk, by the chunk's first step in the shadow of layer 1, into an SGPR; the control wave
+//     publishes 1, 5, 9, ..., T, so a count that lets step t0 + 1 start (>= t0 + 2) lets the whole chunk run.  Every step
+//     still tests the SGPR (scalar compare and branch) and falls back to the poll if the count is short.
+// Unrolled four times, not sixteen: two address adds per chunk remain (the record address, and the control pointer moved
+// on by the chunk's last step, whose read is the only one that can wrap the ring); sixteen steps would remove them for
+// four times the loop's code -- ~3 KB per chunk of the tree form.
 template <int H, bool TREE, bool GATED = false>
 __device__ __forceinline__ void row_dynamics(const RolloutArgs &a, RowShared<H> &sh, const int w)
 {
   static_assert(H == 32, "row_dot_bc: 32 activations, two per lane of a 16-lane row");
+  static_assert(kGRing % 4 == 0, "aligned chunks of four steps inside the ring");
   const int lane = threadIdx.x & 63;
   const int r = lane >> 4, p = lane & 15;
   const int jr = 4 * w + r;  // rollout of the group
@@ -217,8 +321,11 @@ __device__ __forceinline__ void row_dynamics(const RolloutArgs &a, RowShared<H> 
   typedef const volatile int __attribute__((address_space(3))) *lds_int_p;
   typedef const volatile f32x2 __attribute__((address_space(3))) *lds_f2_p;
   const lds_int_p p_pub = (lds_int_p)&sh.ctl_pub[0];
-  const lds_f2_p p_u = (lds_f2_p)&sh.ctl_rec[0][jr][0];  // clamped (u0, u1) of this lane's rollout (control wave), ring slot 0
-  constexpr int kSlotF2 = kRolloutsPerWave * 2;          // f32x2 per ring slot of ctl_rec (and of rec)
+  // clamped (u0, u1) of this lane's rollout (control wave), ring slot 0; as a finished address in a register (left as
+  // base + constant the compiler re-adds the constant every time the pointer moves on)
+  uint32_t a_u0 = lds_addr(&sh.ctl_rec[0][jr][0]);
+  asm volatile("" : "+v"(a_u0));
+  const lds_f2_p p_u = (lds_f2_p)a_u0;
   // The state record of a step is stored by EVERY lane: lanes 0, 1 of a row into the record, the others into a dump row
   // nobody reads -- no exec masking on the recurrence; both move along with the ring slot (one address add for all lanes).
   // (tree form: one component per lane -- quad q of the row holds s[3 + q], lanes 0, 4, 8, 12 write the record)
@@ -241,73 +348,29 @@ __device__ __forceinline__ void row_dynamics(const RolloutArgs &a, RowShared<H> 
     sp = TREE ? f32x2{a.state[3 + (p >> 2)], 0.0f} : odd ? f32x2{a.state[5], a.state[6]} : f32x2{a.state[3], a.state[4]};
   }
   if (w == 0) RSTAMP(2);  // weights in registers
-  while (__builtin_amdgcn_readfirstlane(*p_pub) < 1 && --budget > 0) __builtin_amdgcn_s_sleep(1);
+  int cp = 0;  // steps the control wave has published, as far as this wave knows (SGPR)
+  while ((cp = __builtin_amdgcn_readfirstlane(*p_pub)) < 1 && --budget > 0) __builtin_amdgcn_s_sleep(1);
   if (w == 0) RSTAMP(3);  // first controls published: the T loop starts
-  f32x2 un = p_u[0];
+  lds_f2_p pu = p_u;  // the control records of the chunk: slot t0 % kGRing
+  f32x2 un = pu[0];
   asm volatile("" : "+v"(un));  // pinned: the wait for this read sits here, not inside the loop
 
   // Steps 0 .. T-2 in full; of step T-1 only the state record goes out (its update feeds nothing: the cost is the
-  // running mean over the states BEFORE the updates of steps 1..T-1, mppi_controller.cu:160-177)
-  for (int t = 0; t < T - 1; t++) {
-    const int slot = t & (kGRing - 1);
-    const f32x2 u = un;
-    const f32x2 slo = TREE ? f32x2{row_bc<0>(sp.x), row_bc<4>(sp.x)} : f32x2{row_bc<0>(sp.x), row_bc<0>(sp.y)};    // (s3, s4)
-    const f32x2 shi = TREE ? f32x2{row_bc<8>(sp.x), row_bc<12>(sp.x)} : f32x2{row_bc<1>(sp.x), row_bc<1>(sp.y)};  // (s5, s6)
-    // record for the pose / cost waves: the state BEFORE the update (the ring slot is free: see the end of the step);
-    // then the publication -- which also says: this wave is done with the control record of step t
-    if constexpr (TREE) asm volatile("ds_write_b32 %0, %1" ::"v"(a_rec0 + (uint32_t)slot * kRecStride), "v"(sp.x) : "memory");
-    else asm volatile("ds_write_b64 %0, %1" ::"v"(a_rec0 + (uint32_t)slot * kRecStride), "v"(sp) : "memory");
-    lds_publish(a_myseq, t + 1);
-    // layer 0: [s3, s4, s5, s6, u0, u1]
-    f32x2 z = {0.0f, 0.0f};
-    z = __builtin_elementwise_fma(W.w1[0], f32x2{slo.x, slo.x}, z);
-    z = __builtin_elementwise_fma(W.w1[1], f32x2{slo.y, slo.y}, z);
-    z = __builtin_elementwise_fma(W.w1[2], f32x2{shi.x, shi.x}, z);
-    z = __builtin_elementwise_fma(W.w1[3], f32x2{shi.y, shi.y}, z);
-    z = __builtin_elementwise_fma(W.w1[4], f32x2{u.x, u.x}, z);
-    z = __builtin_elementwise_fma(W.w1[5], f32x2{u.y, u.y}, z);
-    // Requested now, used at the end of the step: the control wave's count, then this rollout's controls of step t+1 as
-    // ONE 8-B read into the pair the packed multiply-adds of layer 0 take them from (valid if the count read before them
-    // is >= t+2).  In FRONT of layer 1: the chains below have no LDS wait of their own to hide these reads behind, and a
-    // read that is still in flight when a chain starts stalls it (the packed multiply-adds formally read the odd halves of
-    // the move registers, which is where the register allocator puts pending results: rollout 55.0 -> 52.4 us with the
-    // reads moved here).
-    const int sn = ((t + 1) & (kGRing - 1)) * kSlotF2;
-    const int cp_v = *p_pub;
-    un = p_u[sn];
-    const f32x2 a0 = tanh_bias2(z, W.b1s);
-    const f32x2 a1 = tanh_bias2(row_dot_bc(W.w2, a0), W.b2s);
-    // Step t+1 may start when the control wave has published it (it runs ahead).  That also says that the ring slot of
-    // the state record of step t+1 is free -- it held step t+1 - kGRing, consumed once cost_done >= t+2 - kGRing: the
-    // control wave publishes a chunk that ends with step tm >= t+1 only after it has seen cost_done >= tm+1 - kGRing
-    // (group_control_wave: need_c; the control record of a step shares the slot index of its state record), so this wave
-    // does not look at the cost wave's word itself.
-    // (A shorter leash for the riders -- waiting when the cost wave is more than 2 / 3 / 5 steps behind instead of a full
-    // ring -- was measured: 124 / 72.6 / 58.0 us against 55.2 us; the riders need the slack.)
-    // The scalar side of the test in front of the output layer's chain, the (cold) wait behind it.
-    const int want = t + 2;
-    const int cp_e = __builtin_amdgcn_readfirstlane(cp_v);
-    asm volatile("" : "+v"(un));  // the wait for the two reads sits HERE (long arrived), not behind the next step's LDS stores
-    if constexpr (TREE) {
-      const float d = row_out_tree(W.w3, a1) + W.b3.x;
-      sp.x = fmaf(d, a.dt, sp.x);  // incrementState, neural_net_model.cu:334-344
-      asm volatile("" : "+v"(sp.x));
-    } else {
-      const f32x2 d = row_dot_bc(W.w3, a1) + W.b3;
-      sp = __builtin_elementwise_fma(d, f32x2{a.dt, a.dt}, sp);  // incrementState, neural_net_model.cu:334-344
-      asm volatile("" : "+v"(sp));  // the chain stays here (otherwise it is sunk below the wait, away from its moves)
-    }
-    if (__builtin_expect(cp_e < want, 0)) {
-      int cp = cp_e;
-      while (cp < want && --budget > 0) {
-        cp = __builtin_amdgcn_readfirstlane(*p_pub);
-        un = p_u[sn];
-      }
-      asm volatile("" : "+v"(un));  // (its wait too: otherwise the merge of the two paths puts one behind the next step's stores)
-    }
+  // running mean over the states BEFORE the updates of steps 1..T-1, mppi_controller.cu:160-177).  One copy of the step
+  // per position of the chunk; a last chunk of fewer steps leaves it early.
+  const int NS = T - 1;
+  for (int t0 = 0; t0 < NS; t0 += 4) {
+    const uint32_t a_rec = a_rec0 + (uint32_t)(t0 & (kGRing - 1)) * kRecStride;
+    row_step<H, TREE, 0>(a, W, sp, un, t0, a_rec, a_myseq, p_pub, pu, p_u, cp, budget);
+    if (t0 + 1 >= NS) break;
+    row_step<H, TREE, 1>(a, W, sp, un, t0, a_rec, a_myseq, p_pub, pu, p_u, cp, budget);
+    if (t0 + 2 >= NS) break;
+    row_step<H, TREE, 2>(a, W, sp, un, t0, a_rec, a_myseq, p_pub, pu, p_u, cp, budget);
+    if (t0 + 3 >= NS) break;
+    row_step<H, TREE, 3>(a, W, sp, un, t0, a_rec, a_myseq, p_pub, pu, p_u, cp, budget);
   }
   if (w == 0) RSTAMP(4);  // T loop done
-  {  // the record of step T-1
+  {  // the record of step T-1, and the publication that closes the last chunk
     const int t = T - 1;
     if constexpr (TREE) asm volatile("ds_write_b32 %0, %1" ::"v"(a_rec0 + (uint32_t)(t & (kGRing - 1)) * kRecStride), "v"(sp.x) : "memory");
     else asm volatile("ds_write_b64 %0, %1" ::"v"(a_rec0 + (uint32_t)(t & (kGRing - 1)) * kRecStride), "v"(sp) : "memory");
