@@ -49,6 +49,8 @@ enum class Form : int {
   Row64R16,                         // rollout_row64.hip: 64-wide nets on the vector ALU, 16 rollouts per group
   M44, M44Chain,                    // rollout_m44.hip: 64-wide nets on v_mfma_f32_4x4x1 with A-broadcast; hidden layers as two
                                     // accumulation chains (the automatic form) / Chain: one, the reference's order
+  Lds44,                            // rollout_lds44.hip: any layer list up to 64 wide on v_mfma_f32_4x4x1, weights from LDS, every
+                                    // layer one chain in the reference's order; by name only ("lds44")
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
 };
@@ -141,6 +143,7 @@ struct mppi_handle {
   float *d_rowpack = nullptr;  // 6-32-32-4: the weights in the register order of the row form (rollout_row.hip)
   float *d_row64pack = nullptr;  // 64-wide nets: register + LDS image of rollout_row64.hip
   float *d_m44pack = nullptr;    // 64-wide nets: image of rollout_m44.hip
+  float *d_lds44pack = nullptr;  // any layer list with hidden widths <= 64: image of rollout_lds44.hip
   bool valu_reg_ok = false;
   double *d_invt = nullptr;
   uint32_t *d_rng[2] = {nullptr, nullptr};
@@ -222,6 +225,7 @@ std::vector<float> pack_mfma_weights(const std::vector<float> &theta, int H, int
 std::vector<float> pack_row_weights(const std::vector<float> &theta);
 std::vector<float> pack_row64_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID);
+std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
 int upload_rng_tables(mppi_handle *h);
 bool use_mfma(const mppi_handle *h);

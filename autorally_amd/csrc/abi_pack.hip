@@ -231,6 +231,34 @@ std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID)
   return out;
 }
 
+// Image of the LDS form on the 4x4x1 MFMA (rollout_lds44.hip), any layer list with hidden widths <= 64: float4 q of lane l at
+// float4 index q * 64 + l.  First kLds44BiasQuads quads: float e of lane l = bias of layer e (hidden layers: b[l] x kTanhScale;
+// output layer: b_out[l >> 4]).  Then per layer ceil(nin / 4) quads, quad q' = (W[l][4 q'] .. W[l][4 q' + 3]) -- lane l is neuron
+// l, the B operand of k steps 4 q' .. 4 q' + 3 -- with the output layer's row c at lane 16 c.  Then kLds44Ahead quads the
+// kernel's read-ahead may touch.  Every entry without a weight (k >= nin, l >= nout, the other lanes of the output layer) is 0.
+std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  std::vector<float> out((size_t)lds44_pack_floats(net), 0.0f);
+  const int n_w = net.n_layers - 1;
+  const float *p = theta.data();
+  int q0 = kLds44BiasQuads;
+  for (int j = 0; j < n_w; j++) {
+    const int nin = net.layers[j], nout = net.layers[j + 1];
+    const float *W = p, *B = p + (size_t)nout * nin;
+    const bool last = j == n_w - 1;
+    for (int l = 0; l < 64; l++) {
+      auto at = [&](int e) -> float & { return out[((size_t)(e >> 2) * 64 + l) * 4 + (e & 3)]; };
+      const int n = last ? ((l & 15) == 0 ? (l >> 4) : -1) : (l < nout ? l : -1);  // the neuron whose row lane l holds
+      at(j) = last ? B[l >> 4] : (n >= 0 ? B[n] * kTanhScale : 0.0f);
+      if (n >= 0)
+        for (int k = 0; k < nin; k++) at(4 * q0 + k) = W[(size_t)n * nin + k];
+    }
+    q0 += (nin + 3) / 4;
+    p += (size_t)nout * nin + nout;
+  }
+  return out;
+}
+
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)
 {
   // base state: L'Ecuyer's default 12345 x 6, scrambled by the seed (DESIGN.md noise spec)

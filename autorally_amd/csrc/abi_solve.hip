@@ -59,7 +59,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.costs = h->d_costs;
   const Form f = form_of(h);
   a.wpack = form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
-            : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
+            : f == Form::Lds44 ? h->d_lds44pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
   a.inv_t = h->d_invt;
   a.K = h->K;
   a.T = h->T;
@@ -122,6 +122,7 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
     case Form::Oct: e = launch_rollout_oct(h->hidden, h->n_hidden, a, h->stream); break;
     case Form::M44: e = launch_rollout_m44(h->hidden, h->n_hidden, a, true, h->stream); break;
     case Form::M44Chain: e = launch_rollout_m44(h->hidden, h->n_hidden, a, false, h->stream); break;
+    case Form::Lds44: e = launch_rollout_lds44(h->net, a, h->stream); break;
     case Form::Row64R16: e = launch_rollout_row64(h->hidden, h->n_hidden, a, 16, h->stream); break;
     case Form::Row: case Form::RowTree: e = launch_rollout_row(h->hidden, h->n_hidden, a, f == Form::RowTree, h->stream); break;
     case Form::Quad: case Form::Fused64: case Form::Fused256:
@@ -574,7 +575,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
 // d_in at the one it smooths into.
 
 // The forms that have a gated rollout and gain from it (one iteration, no stage events, no capture): 1: a latency form with
-// riders (the row forms, the automatic m44 form) and its in-kernel generator; 2: the automatic multi4-tree form with the
+// riders (the row forms, the automatic m44 form, the lds44 form) and its in-kernel generator; 2: the automatic multi4-tree form with the
 // stand-alone generator kernel prefetched on a second stream; 0: none
 static int arm_kind(const mppi_handle *h)
 {
@@ -582,7 +583,7 @@ static int arm_kind(const mppi_handle *h)
         h->explicit_iters == 0 && !h->basis && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
     return 0;
   const Form f = form_of(h);
-  if ((form_is_row(f) || f == Form::M44) && has_noise_wave(h) && !h->prefetch_valid) return 1;
+  if ((form_is_row(f) || f == Form::M44 || f == Form::Lds44) && has_noise_wave(h) && !h->prefetch_valid) return 1;
   // (where the generator kernel runs beside the rollout.  Where it runs behind it -- 32-wide nets at K = 65 536 -- the phase
   // between two rollouts is the generator's own 41 us whatever the launches cost: chained 0.3139, unchained 0.3131 ms)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;

@@ -82,6 +82,16 @@ hipError_t launch_dynamics_valu(const NetDesc &net, const float *theta, const fl
                                 const float *controls, float *ders, int n, int negate_yaw_der,
                                 hipStream_t stream);
 
+// rollout_lds44.hip: the m44 group (four dynamics waves x four rollouts on v_mfma_f32_4x4x1 with A-matrix broadcast + the four
+// riders per 16 rollouts) for ANY layer list 6 -> hidden widths 1..64 -> 4: the layer list is a kernel argument, the weights of
+// all layers are read from LDS, every layer -- the output layer too -- is one k-ascending chain (the reference's order:
+// bit-identical to the other exact forms); a.wpack = pack_lds44_weights (abi_pack.hip)
+constexpr int kLds44BiasQuads = 2;  // float4 per lane in front of the weights: one bias per layer
+constexpr int kLds44Ahead = 3;      // float4 of weights requested ahead of their use (and zero quads behind the last layer)
+bool lds44_supported(const NetDesc &net);
+int lds44_pack_floats(const NetDesc &net);
+hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStream_t stream);
+
 // rollout_bf.hip (GeneralizedLinear basis-function dynamics, W[4][25] in a.wpack)
 hipError_t launch_rollout_bf(const RolloutArgs &a, int waves, hipStream_t stream);  // waves per 64 rollouts: 1, 2, 3
 // several instances of the three-wave form in one launch (grid: groups of 64 rollouts x instances)

@@ -39,6 +39,7 @@ extern "C" {
  *    "mfma" / "valu" / "valu_lds" drop a form forced by name; variants "multi1", "multi4u[_gen]", "row64_r8" removed;
  *    + mppi_debug_set_chained_ticks (mppi_control_ticks enqueues one solve ahead), + mppi_debug_min_cost;
  *    + mppi_arm, mppi_arm_batch, mppi_disarm, mppi_is_armed (solve-ahead for a new state every tick; compatible additions). */
+/*    (still 5) + rollout variant "lds44", name "mfma4x4x1_lds_l<N>_w<W>": no new export, nothing else changes. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -291,7 +292,11 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     basis functions    basis_funcs25_valu[_2w|_3w]        "fused" | "quad" | "bf3"
  *   the reference's summation order in EVERY layer (bit-identical to one another; "mfma" = the table restricted to them)
  *     "row_exact" (= "row") valu_row8w_h32_l2, "m44_chain" mfma4x4x1_*_m44_tree (hidden layers one chain; output a butterfly),
- *     "oct[_gen]" ..._oct8w, "quad", "multi2[_gen]", "multi4[_gen]", "fused" = "block256" | "block64" ..._fused_b256 / _b64
+ *     "oct[_gen]" ..._oct8w, "quad", "multi2[_gen]", "multi4[_gen]", "fused" = "block256" | "block64" ..._fused_b256 / _b64,
+ *     "lds44" mfma4x4x1_lds_l<hidden layers>_w<widest hidden layer>: ANY layer list 6 -> hidden widths 1..64 -> 4 (the standard
+ *     shapes included) in the latency regime -- the m44 group with the weights of every layer read from LDS and the output layer
+ *     as one more chain; by name only (never chosen automatically); has a gated form (mppi_arm, chained mppi_control_ticks);
+ *     MPPI_ERR_UNSUPPORTED for the basis-function model, a hidden width above 64, or a list without a hidden layer
  *   A/B arms and cross-checks (never chosen automatically)
  *     "valu" valu_reg_lds (lane = rollout, the independent implementation every parity test also runs; config 4's untuned
  *     vector-ALU reference), "valu_lds" (the generic kernel on a standard shape), "row64" = "row64_r16"

@@ -1,0 +1,58 @@
+"""Rollout-stage times of the "lds44" form against the forms it stands beside, K = 1920, T = 100:
+the kernel's own dispatch time (mppi_get_stage_times, every 8th solve timed), median of 50 samples per form, the forms
+alternating in blocks inside one process.
+    python tools/lds44_table.py [> profiles/<round>_lds44_rollout_times.txt]
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from autorally_amd import build as B  # noqa: E402
+from autorally_amd import capi  # noqa: E402
+from autorally_amd import synthetic as S  # noqa: E402
+
+K, T = 1920, 100
+ROWS = [([6, 32, 32, 32, 4], []), ([6, 64, 64, 64, 4], []), ([6, 48, 48, 4], []), ([6, 16, 24, 4], []),
+        ([6, 32, 32, 32, 32, 32, 32, 4], []), ([6, 64, 64, 4], ["m44_chain", "m44"]), ([6, 64, 64, 64, 64, 4], ["m44_chain", "m44"]),
+        ([6, 32, 32, 4], ["row_exact", "row_tree"])]
+
+
+def sample(sol, st):
+    sol.enable_stage_timing(8)
+    sol.reset_stage_times()
+    for _ in range(8):
+        sol.compute_control(st)
+        sol.slide_control_seq(1)
+    t = sol.get_stage_times()
+    sol.enable_stage_timing(0)
+    return 1e3 * t["rollout_ms"] / max(1, t["n_solves"])
+
+
+def main():
+    B.build()
+    print("rollout stage, K = %d, T = %d, us (median of 50 samples, min .. max)" % (K, T))
+    for layers, extra in ROWS:
+        cfg = S.make_config(K, T, layers=layers, track="oval")
+        st = cfg["start_state"]
+        sols = {}
+        for v in ["lds44", "valu_lds"] + extra:
+            sols[v] = capi.Solver(cfg)
+            sols[v].set_rollout_variant(v)
+            for _ in range(20):
+                sols[v].compute_control(st)
+        got = {v: [] for v in sols}
+        for _ in range(5):
+            for v, sol in sols.items():
+                got[v] += [sample(sol, st) for _ in range(10)]
+        line = ["%-22s" % "-".join(map(str, layers))]
+        for v, x in got.items():
+            line.append("%s (%s) %.1f (%.1f .. %.1f)" % (v, sols[v].rollout_variant(), np.median(x), min(x), max(x)))
+        print("  ".join(line), flush=True)
+        for sol in sols.values():
+            sol.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -11,7 +11,9 @@
 // Between layers the activations go from D's layout (VGPR = rollout, lane = neuron) to A's (lane-in-quad = rollout, VGPR =
 // neuron-in-quad): a 4x4 transpose inside every quad (quad_perm moves + selects), once per layer.
 // Part 1 probes the operand layouts (which A / B lane feeds D[v][lane], with and without the broadcast);
-// part 2 times the layer (+ tanh + transpose), `iters` layers per launch, and checks the bits against the fmaf chain.
+// part 2 times the layer (+ tanh + transpose), `iters` layers per launch, and checks the bits against the fmaf chain;
+// part 3 is the same layer with the B operand read from LDS (rollout_lds44.hip: ds_read_b128 = four k steps, kAhead reads in
+// flight, a wave-uniform exit every four steps), NIN = 32 and 64 inputs, one and four waves per CU.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/ub/mfma4x4_ub.hip -o mfma4x4_ub && ./mfma4x4_ub
 #include "../../autorally_amd/csrc/mppi_device.hpp"
 #include <cmath>
@@ -112,6 +114,66 @@ __global__ __launch_bounds__(64 * WAVES) void k_layer(const float *W, const floa
     for (int r = 0; r < 4; r++) out[r * 64 + lane] = act[r];
 }
 
+// The B operand from LDS: float4 q of lane l at wl[q * 64 + l] = W[l][4 q .. 4 q + 3]; nq is a kernel ARGUMENT as in the rollout
+// kernel, so the unrolled chain keeps its exits.
+constexpr int kAhead = 3;
+template <int Q>
+__device__ __forceinline__ void lds_chain(f32x4_t &d, const float (&T)[4], f32x4_t (&w)[kAhead], const f32x4_t *p, const int nq)
+{
+  if constexpr (Q < 16) {
+    if (Q > 0 && Q >= nq) return;
+    const f32x4_t x = w[Q % kAhead];
+    if constexpr (Q + kAhead < 16) w[Q % kAhead] = p[(Q + kAhead) * 64];
+    d = __builtin_amdgcn_mfma_f32_4x4x1f32(T[0], x[0], d, 4, Q, 0);
+    d = __builtin_amdgcn_mfma_f32_4x4x1f32(T[1], x[1], d, 4, Q, 0);
+    d = __builtin_amdgcn_mfma_f32_4x4x1f32(T[2], x[2], d, 4, Q, 0);
+    d = __builtin_amdgcn_mfma_f32_4x4x1f32(T[3], x[3], d, 4, Q, 0);
+    lds_chain<Q + 1>(d, T, w, p, nq);
+  }
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void k_layer_lds(const float *W, const float *B, float *out, unsigned long long *cyc, int iters,
+                                                          const int nin)
+{
+  __shared__ __attribute__((aligned(16))) f32x4_t wl[(16 + kAhead) * 64];  // + kAhead quads the read-ahead may touch
+  const int lane = threadIdx.x & 63, li = lane & 3;
+  for (int i = threadIdx.x; i < (16 + kAhead) * 64; i += 64 * WAVES) {
+    const int q = i >> 6, l = i & 63;
+    f32x4_t v = {0, 0, 0, 0};
+    for (int c = 0; c < 4; c++)
+      if (4 * q + c < nin) v[c] = W[l * nin + 4 * q + c];
+    wl[i] = v;
+  }
+  __syncthreads();
+  const float bs = B[lane] * kTanhScale;
+  const int nq = (nin + 3) >> 2;
+  const f32x4_t *p = wl + lane;
+  float act[4];
+#pragma unroll
+  for (int r = 0; r < 4; r++) act[r] = (0.01f * (float)lane - 0.3f) * (1.0f - 0.4f * (float)r);
+  f32x4_t wq[kAhead];
+#pragma unroll
+  for (int q = 0; q < kAhead; q++) wq[q] = p[q * 64];
+  const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+  for (int i = 0; i < iters; i++) {
+    float T[4];
+    quad_transpose(act, T, li);
+    f32x4_t d = {0, 0, 0, 0};
+    lds_chain<0>(d, T, wq, p, nq);
+    asm volatile("" ::: "memory");  // the next layer's first quads are read again, under the tanh (as in the rollout kernel)
+#pragma unroll
+    for (int q = 0; q < kAhead; q++) wq[q] = p[q * 64];
+    const f32x2 a01 = tanh_bias2(f32x2{d[0], d[1]}, f32x2{bs, bs});
+    const f32x2 a23 = tanh_bias2(f32x2{d[2], d[3]}, f32x2{bs, bs});
+    act[0] = a01.x; act[1] = a01.y; act[2] = a23.x; act[3] = a23.y;
+  }
+  const unsigned long long c1 = __builtin_amdgcn_s_memtime();
+  if (lane == 0) cyc[blockIdx.x * WAVES + (threadIdx.x >> 6)] = c1 - c0;
+  if (blockIdx.x == 0 && threadIdx.x < 64)
+    for (int r = 0; r < 4; r++) out[r * 64 + lane] = act[r];
+}
+
 static float tanh_dev(float z, float b)
 {
   const float y = fmaf(z, kTanhScale, b * kTanhScale);
@@ -198,6 +260,51 @@ int main()
     for (auto v : c) mx = fmax(mx, (double)v);
     printf("64x64 layer as 64 v_mfma_f32_4x4x1 (4 rollouts / wave) + tanh + quad transpose, %d wave(s) / SIMD: %8.1f ns / layer by events, "
            "%7.1f s_memtime ticks / layer   max |out - host| %.2e\n", waves / 4, 1e6 * ms / iters, mx / iters, worst);
+  }
+  // part 3: the B operand from LDS
+  for (int nin : {32, 64}) {
+    std::vector<float> Wn((size_t)H * nin);
+    for (int j = 0; j < H; j++)
+      for (int k = 0; k < nin; k++) Wn[(size_t)j * nin + k] = W[j * H + k];
+    for (int r = 0; r < 4; r++) {
+      float a[H], n[H];
+      for (int j = 0; j < H; j++) a[j] = (0.01f * (float)j - 0.3f) * (1.0f - 0.4f * (float)r);
+      for (int it = 0; it < iters; it++) {
+        for (int j = 0; j < H; j++) {
+          float z = 0.0f;
+          for (int k = 0; k < nin; k++) z = fmaf(Wn[(size_t)j * nin + k], a[k], z);
+          n[j] = tanh_dev(z, B[j]);
+        }
+        memcpy(a, n, sizeof(a));
+      }
+      for (int j = 0; j < H; j++) ref[r * 64 + j] = a[j];
+    }
+    CK(hipMemcpy(dW, Wn.data(), Wn.size() * 4, hipMemcpyHostToDevice));
+    for (int waves : {1, 4}) {
+      hipEvent_t e0, e1;
+      CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+      auto launch = [&]() {
+        if (waves == 1) hipLaunchKernelGGL((k_layer_lds<1>), dim3(blocks), dim3(64), 0, 0, dW, dB, d_out, d_cyc, iters, nin);
+        else hipLaunchKernelGGL((k_layer_lds<4>), dim3(blocks), dim3(256), 0, 0, dW, dB, d_out, d_cyc, iters, nin);
+      };
+      launch();
+      CK(hipDeviceSynchronize());
+      CK(hipEventRecord(e0));
+      launch();
+      CK(hipEventRecord(e1));
+      CK(hipDeviceSynchronize());
+      float ms = 0;
+      CK(hipEventElapsedTime(&ms, e0, e1));
+      std::vector<float> o(256);
+      std::vector<unsigned long long> c((size_t)blocks * waves);
+      CK(hipMemcpy(o.data(), d_out, 256 * 4, hipMemcpyDeviceToHost));
+      CK(hipMemcpy(c.data(), d_cyc, c.size() * 8, hipMemcpyDeviceToHost));
+      double mx = 0, worst = 0;
+      for (int i = 0; i < 256; i++) worst = fmax(worst, fabs((double)o[i] - (double)ref[i]));
+      for (auto v : c) mx = fmax(mx, (double)v);
+      printf("%dx64 layer, B operand from LDS (ds_read_b128, %d ahead) + tanh + quad transpose, %d wave(s) / CU: %8.1f ns / layer by events, "
+             "%7.1f s_memtime ticks / layer   max |out - host| %.2e\n", nin, kAhead, waves, 1e6 * ms / iters, mx / iters, worst);
+    }
   }
   return 0;
 }
