@@ -65,7 +65,7 @@ SYMBOLS = [
     "mppi_debug_inject_handover_fault", "mppi_compute_feedback_gains_pair", "mppi_set_host_threads",
     "mppi_debug_capture_iterations", "mppi_debug_get_iterations", "mppi_set_wait_timeout", "mppi_debug_form_candidates",
     "mppi_debug_set_chained_ticks", "mppi_debug_min_cost",
-    "mppi_arm", "mppi_arm_batch", "mppi_disarm", "mppi_is_armed",
+    "mppi_arm", "mppi_arm_batch", "mppi_disarm", "mppi_is_armed", "mppi_debug_launch_info",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -167,9 +167,11 @@ def lib():
             L.mppi_arm_batch.argtypes = [C.POINTER(hp), C.c_int, C.c_double]
             L.mppi_disarm.argtypes = [hp]
             L.mppi_is_armed.argtypes = [hp]
+        if hasattr(L, "mppi_debug_launch_info"):  # added without a version step: an older version-5 library lacks it
+            L.mppi_debug_launch_info.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         for s in SYMBOLS:  # every declared symbol of the library's ABI version must be there
             if (v2 or s not in ABI2_SYMBOLS) and (v3 or s not in ABI3_SYMBOLS) and (v4 or s not in ABI4_SYMBOLS) and \
-                    (v5 or s not in ABI5_SYMBOLS):
+                    (v5 or s not in ABI5_SYMBOLS) and s != "mppi_debug_launch_info":
                 getattr(L, s)
         _lib = L
     return _lib
@@ -358,6 +360,13 @@ class Solver:
 
     def is_armed(self):
         return bool(self.L.mppi_is_armed(self.h))
+
+    def debug_launch_info(self):
+        """mppi_debug_launch_info: (instances, gated) of the rollout launch of the most recently enqueued solve (an armed one
+        counts): instances 0 before any solve, 1 for a launch of its own, n for one shared by the n handles of a batch."""
+        n, g = C.c_int(-1), C.c_int(-1)
+        self._ck(self.L.mppi_debug_launch_info(self.h, C.byref(n), C.byref(g)))
+        return n.value, g.value
 
     def compute_control_async(self, state):
         self._ck(self.L.mppi_compute_control_async(self.h, _fp(_f32(state, (7,)))))

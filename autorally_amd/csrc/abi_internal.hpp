@@ -187,6 +187,10 @@ struct mppi_handle {
   // the armed solve writes its costs and weights into the second pair (swapped in when its gate opens): the last result's
   // vectors stay readable while it is armed, and a solve called off leaves them alone
   float *d_costs_alt = nullptr, *d_w_alt = nullptr;
+  // mppi_debug_launch_info: how many instances the rollout launch of the most recently enqueued solve served (an armed solve
+  // counts; 0: no solve yet) and whether it was a gated launch -- written where the launch is made
+  int launch_instances = 0;
+  bool launch_gated = false;
   bool timed_out = false;        // a wait ran out of time and that solve's device work may still run: recover_timed_out (abi_solve.hip)
   bool no_result = false;        // the last solve was lost (timeout): mppi_get_results refuses until a solve completes
   bool timing = false;

@@ -132,6 +132,8 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
     default: e = launch_rollout_valu(h->net, a, h->stream); break;
   }
   if (e != hipSuccess) return fail(h, MPPI_ERR_HIP, "rollout launch", e);
+  h->launch_instances = 1;
+  h->launch_gated = a.gate != nullptr;
   return MPPI_OK;
 }
 
@@ -800,12 +802,33 @@ static int open_armed(mppi_handle *h, const float *state)
   return MPPI_OK;
 }
 
-// mppi_arm_batch: one launch for the batch where mppi_compute_control_batch would use one (the row form's batched kernel, gated)
+// the rollout of a batch batch_together admits, in one launch on S; gated: every argument block carries its handle's gate block
+static hipError_t launch_rollout_batch(mppi_handle *const *hs, int n, const QuadBatchArgs &qb, bool gated, hipStream_t S)
+{
+  const mppi_handle *h0 = hs[0];
+  const Form f = form_of(h0);
+  const hipError_t e = h0->basis          ? launch_rollout_bf_batch(qb, S)
+                       : form_is_row(f)   ? launch_rollout_row_batch(qb, f == Form::RowTree, S)
+                       : f == Form::M44   ? launch_rollout_m44_batch(h0->n_hidden, qb, S)
+                       : f == Form::Lds44 ? launch_rollout_lds44_batch(h0->net, qb, S)
+                                          : launch_rollout_quad_batch(h0->hidden, h0->n_hidden, qb, S);
+  if (e != hipSuccess) return e;
+  for (int i = 0; i < n; i++) {
+    hs[i]->launch_instances = n;
+    hs[i]->launch_gated = gated;
+  }
+  return hipSuccess;
+}
+
+// mppi_arm_batch: one launch for the batch where mppi_compute_control_batch would use one and the form has a gated batched kernel
+// (the row forms; the pair of the automatic m44 form and of the lds44 form)
 static bool batch_together(mppi_handle *const *hs, int n);
 static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
 {
   mppi_handle *h0 = hs[0];
-  if (!form_is_row(form_of(h0))) return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
+  const Form f0 = form_of(h0);
+  if (!(form_is_row(f0) || f0 == Form::M44 || f0 == Form::Lds44))
+    return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
   for (int i = 0; i < n; i++)
     if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");
   HIPCHK(h0, ensure_device(h0->cfg.device));
@@ -824,7 +847,7 @@ static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
     for (int q = 0; q < n; q++) hs[i]->arm_peers[q] = hs[q];
   }
   for (int i = n; i < kMaxBatch; i++) qb.inst[i] = qb.inst[0];
-  hipError_t e = launch_rollout_row_batch(qb, form_of(h0) == Form::RowTree, S);
+  hipError_t e = launch_rollout_batch(hs, n, qb, true, S);
   if (e == hipSuccess) e = launch_solve_tail_batch(tl, n, S);
   if (e != hipSuccess) {
     const int rc = fail(h0, MPPI_ERR_HIP, "armed batched launch", e);
@@ -832,6 +855,18 @@ static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
     return rc;
   }
   return MPPI_OK;
+}
+
+// the next solve's controls are finite: no explicit noise waits, and the host's nominal sequence and history are finite numbers
+// (a pending solve replaces them by a weighted mean of clamped controls: not finite only where every cost already is NaN)
+static bool controls_finite(const mppi_handle *h)
+{
+  if (h->explicit_iters > 0) return false;
+  for (float u : h->U)
+    if (!std::isfinite(u)) return false;
+  for (float u : h->hist)
+    if (!std::isfinite(u)) return false;
+  return true;
 }
 
 // One launch for all instances where the quad form serves them together (every wave of every group still gets a
@@ -846,16 +881,26 @@ static bool batch_together(mppi_handle *const *hs, int n)
     const mppi_handle *h = hs[i];
     // network model: the four-wavefront form; basis-function model: its three-wavefront form (in-kernel generator)
     const Form f = form_of(h);
+    // the pair of a tick only (their batched kernels exist for two instances): the automatic m44 form of one network shape; the
+    // lds44 form (by name only: forced on every handle) of one WHOLE layer list -- one Lds44Net and one image size serve the launch
+    const bool wide = f == Form::M44 || f == Form::Lds44;
+    bool same_list = h->net.n_layers == h0->net.n_layers;
+    for (int l = 0; l < h->net.n_layers && same_list; l++) same_list = h->net.layers[l] == h0->net.layers[l];
     const bool form_ok = h->basis ? (h0->basis && f == Form::Bf3)
-                                  : (!h0->basis && (f == Form::Quad || form_is_row(f)) && f == form_of(h0) &&
-                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden);
+                                  : (!h0->basis && (f == Form::Quad || form_is_row(f) || (wide && n == 2)) && f == form_of(h0) &&
+                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden && (f != Form::Lds44 || same_list));
     // one kernel instance serves the whole batch: the instances must agree on what it is specialised for (affine / projective
     // costmap transform, control cost or none) -- a superset kernel would compute 0 * x where the single solve computes
-    // nothing, which differs for a non-finite x; such a pair is solved one by one
+    // nothing, which differs for a non-finite x; such a pair is solved one by one.
+    // The m44 / lds44 pair may differ in the control cost: the term of an instance without one is coeff * du * (u - du) / nu^2
+    // with coeff = 0 and a finite non-zero nu (fill_cost_args), exactly +0 while its controls are finite whatever the STATE is --
+    // and they are: clamped draws of the in-kernel generator around a finite nominal sequence (controls_finite).  The
+    // projective transform divides by a w computed from the state: that superset stays refused.
     CostArgs ci, c0;
     fill_cost_args(h, ci);
     fill_cost_args(h0, c0);
-    together = form_ok && ci.affine == c0.affine && ci.need_control_cost == c0.need_control_cost &&
+    const bool ctrl_ok = ci.need_control_cost == c0.need_control_cost || (wide && controls_finite(h) && controls_finite(h0));
+    together = form_ok && ci.affine == c0.affine && ctrl_ok &&
                h->cfg.device == h0->cfg.device && h->cfg.num_iters == h0->cfg.num_iters &&
                h->K <= 4096 && !h->timing && !h->capture && !h->prefetch_valid && h->have_nn && h->have_map && h->have_cost;
     // waves of a group that need a SIMD each: quad 4, row 4 dynamics waves (its riders ride), basis functions 3
@@ -1012,9 +1057,7 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     }
     for (int i = n; i < kMaxBatch; i++) qb.inst[i] = qb.inst[0];
     HB(4);  // uploads + argument blocks
-    hipError_t e = h0->basis ? launch_rollout_bf_batch(qb, S)
-                   : form_is_row(form_of(h0)) ? launch_rollout_row_batch(qb, form_of(h0) == Form::RowTree, S)
-                                                : launch_rollout_quad_batch(h0->hidden, h0->n_hidden, qb, S);
+    hipError_t e = launch_rollout_batch(hs, n, qb, false, S);
     HB(5);  // rollout launch
     if (e == hipSuccess) e = launch_solve_tail_batch(tl, n, S);
     HB(6);  // tail launch
@@ -1270,6 +1313,14 @@ int mppi_disarm(mppi_handle *h)
 int mppi_is_armed(const mppi_handle *h)
 {
   return (h && h->armed) ? 1 : 0;
+}
+
+int mppi_debug_launch_info(mppi_handle *h, int *instances, int *gated)
+{
+  if (!h || !instances || !gated) return MPPI_ERR_INVALID;
+  *instances = h->launch_instances;
+  *gated = h->launch_gated ? 1 : 0;
+  return MPPI_OK;
 }
 
 int mppi_set_wait_timeout(mppi_handle *h, double seconds)

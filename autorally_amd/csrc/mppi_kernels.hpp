@@ -65,6 +65,8 @@ hipError_t launch_rollout_row64(int hidden, int n_hidden, const RolloutArgs &a, 
 bool m44_variant_supported(int hidden, int n_hidden);
 int m44_pack_floats(int n_hidden);
 hipError_t launch_rollout_m44(int hidden, int n_hidden, const RolloutArgs &a, bool split, hipStream_t stream);  // split: two chains per hidden layer
+// the split form for the two controllers of a tick in one launch: b.n == 2, grid (groups of the larger instance, 2)
+hipError_t launch_rollout_m44_batch(int n_hidden, const QuadBatchArgs &b, hipStream_t stream);
 
 // rollout_valu.hip (generic vector-ALU kernel, any layer list)
 struct NetDesc {
@@ -91,6 +93,8 @@ constexpr int kLds44Ahead = 3;      // float4 of weights requested ahead of thei
 bool lds44_supported(const NetDesc &net);
 int lds44_pack_floats(const NetDesc &net);
 hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStream_t stream);
+// two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
+hipError_t launch_rollout_lds44_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
 
 // rollout_bf.hip (GeneralizedLinear basis-function dynamics, W[4][25] in a.wpack)
 hipError_t launch_rollout_bf(const RolloutArgs &a, int waves, hipStream_t stream);  // waves per 64 rollouts: 1, 2, 3

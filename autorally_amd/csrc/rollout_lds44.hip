@@ -180,15 +180,15 @@ __device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44
   spin_finish(budget, lds_addr(&sh.fail[0]), lds_addr(&sh.fin[w]));
 }
 
+// one group (workgroup): the four dynamics waves and the four riders; smem: the group's dynamic LDS (Lds44Shared, then the image)
 // GATED: enqueued one solve ahead (a.gate != nullptr), state and nominal sequence from the gate block: group_gate_wait
 template <bool AFFINE, bool CTRL, bool GATED>
-__global__ __launch_bounds__(512) void rollout_lds44_kernel(const RolloutArgs a, const Lds44Net net, const int img_f4)
+__device__ __forceinline__ void lds44_group(const RolloutArgs &a, const Lds44Net &net, const int img_f4, unsigned char *smem)
 {
   using SH = Lds44Shared;
   using RO = GroupRoles<SH>;
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds44_smem[];
-  SH &sh = *reinterpret_cast<SH *>(lds44_smem);
-  m44_f4 *img = reinterpret_cast<m44_f4 *>(lds44_smem + kLds44ImageOffset);
+  SH &sh = *reinterpret_cast<SH *>(smem);
+  m44_f4 *img = reinterpret_cast<m44_f4 *>(smem + kLds44ImageOffset);
   const int lane = threadIdx.x & 63;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   MrgHalf g0{0, 0, 0};
@@ -225,6 +225,31 @@ __global__ __launch_bounds__(512) void rollout_lds44_kernel(const RolloutArgs a,
   else group_rng_wave<SH, true>(a, sh, g0);
 }
 
+extern __shared__ __attribute__((aligned(16))) unsigned char lds44_smem[];
+
+template <bool AFFINE, bool CTRL, bool GATED>
+__global__ __launch_bounds__(512) void rollout_lds44_kernel(const RolloutArgs a, const Lds44Net net, const int img_f4)
+{
+  lds44_group<AFFINE, CTRL, GATED>(a, net, img_f4, lds44_smem);
+}
+
+// The two controllers of a tick in one launch (mppi_compute_control_batch, mppi_arm_batch): grid (groups of the larger
+// instance, 2) -- workgroup (x, y) runs group x of instance y, whose argument block sits at a compile-time position of the
+// kernel-argument segment (MPPI_BATCH_DISPATCH, mppi_device.hpp).  All instances have the SAME layer list: one Lds44Net, one
+// image size and one dynamic-LDS size serve the launch; each instance copies its own image from its own a.wpack.  GATED: every
+// instance's block carries its own handle's gate block (replica blockIdx.x % kGateReplicas: the group index inside the instance).
+template <bool AFFINE, bool CTRL, bool GATED, int NB>
+__global__ __launch_bounds__(512) void rollout_lds44_batch_kernel(const QuadBatchArgsT<NB> b, const Lds44Net net, const int img_f4)
+{
+#define MPPI_L44_BODY(A)                                                                                   \
+  do {                                                                                                     \
+    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* the smaller instance of the two */         \
+    lds44_group<AFFINE, CTRL, GATED>((A), net, img_f4, lds44_smem);                                        \
+  } while (0)
+  MPPI_BATCH_DISPATCH(NB, b, MPPI_L44_BODY);
+#undef MPPI_L44_BODY
+}
+
 // every list 6 -> hidden widths 1..64 -> 4 with at least one hidden layer
 bool lds44_supported(const NetDesc &net)
 {
@@ -241,6 +266,18 @@ int lds44_pack_floats(const NetDesc &net)
   return q * 64 * 4;
 }
 
+// more dynamic LDS than the default limit: set once per kernel instance and device
+#define MPPI_L44_ATTR(KERN)                                                                                            \
+  do {                                                                                                                 \
+    static bool attr_set[64] = {};                                                                                     \
+    if (!attr_set[dev]) {                                                                                              \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&KERN), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                         160 * 1024);                                                                  \
+      if (e != hipSuccess) return e;                                                                                   \
+      attr_set[dev] = true;                                                                                            \
+    }                                                                                                                  \
+  } while (0)
+
 hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStream_t stream)
 {
   if (!lds44_supported(net) || a.K % kRolloutsPerWave != 0) return hipErrorInvalidValue;
@@ -255,13 +292,7 @@ hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStr
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
 #define MPPI_L44(AF, CT, GA)                                                                                          \
   do {                                                                                                                \
-    static bool attr_set[64] = {}; /* more dynamic LDS than the default limit: once per kernel instance and device */ \
-    if (!attr_set[dev]) {                                                                                             \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_lds44_kernel<AF, CT, GA>),           \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                     \
-      if (e != hipSuccess) return e;                                                                                  \
-      attr_set[dev] = true;                                                                                           \
-    }                                                                                                                 \
+    MPPI_L44_ATTR((rollout_lds44_kernel<AF, CT, GA>));                                                                \
     MPPI_LAUNCH_ROLLOUT((rollout_lds44_kernel<AF, CT, GA>), grid, block, lds, stream, a, nd, img_f4);                 \
   } while (0)
   if (gated) {
@@ -278,5 +309,48 @@ hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStr
 #undef MPPI_L44
   return hipGetLastError();
 }
+
+// two instances of ONE layer list (net) in one launch
+hipError_t launch_rollout_lds44_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream)
+{
+  if (b.n != 2 || !lds44_supported(net)) return hipErrorInvalidValue;
+  bool affine = true, ctrl = false;  // the general forms are exact supersets (rollout_mfma.hip)
+  int gmax = 0;
+  const bool gated = b.inst[0].gate != nullptr;  // mppi_arm_batch: every instance gated on its own block, or none
+  for (int i = 0; i < b.n; i++) {
+    if ((b.inst[i].gate != nullptr) != gated || b.inst[i].K % kRolloutsPerWave != 0) return hipErrorInvalidValue;
+    affine = affine && b.inst[i].cost.affine != 0;
+    ctrl = ctrl || b.inst[i].cost.need_control_cost != 0;
+    gmax = b.inst[i].K / kRolloutsPerWave > gmax ? b.inst[i].K / kRolloutsPerWave : gmax;
+  }
+  const QuadBatchArgsT<2> b2 = batch_args_prefix<2>(b);
+  const dim3 grid(gmax, 2), block(512);
+  const int img_f4 = lds44_pack_floats(net) / 4;
+  const size_t lds = kLds44ImageOffset + sizeof(m44_f4) * (size_t)img_f4;
+  Lds44Net nd;
+  nd.n_layers = net.n_layers;
+  for (int i = 0; i < 8; i++) nd.layers[i] = net.layers[i];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+#define MPPI_L44B(AF, CT, GA)                                                                                         \
+  do {                                                                                                                \
+    MPPI_L44_ATTR((rollout_lds44_batch_kernel<AF, CT, GA, 2>));                                                       \
+    hipLaunchKernelGGL((rollout_lds44_batch_kernel<AF, CT, GA, 2>), grid, block, lds, stream, b2, nd, img_f4);        \
+  } while (0)
+  if (gated) {
+    if (affine && !ctrl) MPPI_L44B(true, false, true);
+    else if (affine && ctrl) MPPI_L44B(true, true, true);
+    else if (!affine && !ctrl) MPPI_L44B(false, false, true);
+    else MPPI_L44B(false, true, true);
+  } else {
+    if (affine && !ctrl) MPPI_L44B(true, false, false);
+    else if (affine && ctrl) MPPI_L44B(true, true, false);
+    else if (!affine && !ctrl) MPPI_L44B(false, false, false);
+    else MPPI_L44B(false, true, false);
+  }
+#undef MPPI_L44B
+  return hipGetLastError();
+}
+#undef MPPI_L44_ATTR
 
 }  // namespace mppi

@@ -273,13 +273,13 @@ __device__ __forceinline__ void m44_dynamics(const RolloutArgs &a, M44Shared &sh
   spin_finish(budget, lds_addr(&sh.fail[0]), lds_addr(&sh.fin[w]));
 }
 
+// one group (workgroup): the four dynamics waves and the four riders
 // GATED: enqueued one solve ahead (a.gate != nullptr), state and nominal sequence from the gate block: group_gate_wait
-template <int NHID, bool AFFINE, bool CTRL, bool SPLIT, bool GATED = false>
-__global__ __launch_bounds__(512) void rollout_m44_kernel(const RolloutArgs a)
+template <int NHID, bool AFFINE, bool CTRL, bool SPLIT, bool GATED>
+__device__ __forceinline__ void m44_group(const RolloutArgs &a, M44Shared &sh)
 {
   using SH = M44Shared;
   using RO = GroupRoles<SH>;
-  __shared__ __attribute__((aligned(16))) SH sh;
   const int lane = threadIdx.x & 63;
   const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   MrgHalf g0{0, 0, 0};
@@ -317,6 +317,47 @@ __global__ __launch_bounds__(512) void rollout_m44_kernel(const RolloutArgs a)
   else group_rng_wave<SH, true>(a, sh, g0);
 }
 
+template <int NHID, bool AFFINE, bool CTRL, bool SPLIT, bool GATED = false>
+__global__ __launch_bounds__(512) void rollout_m44_kernel(const RolloutArgs a)
+{
+  __shared__ __attribute__((aligned(16))) M44Shared sh;
+  m44_group<NHID, AFFINE, CTRL, SPLIT, GATED>(a, sh);
+}
+
+// The two controllers of a tick in one launch (mppi_compute_control_batch; the split form only: the automatic one, and the one
+// that has a gated form): grid (groups of the larger instance, 2) -- workgroup (x, y) runs group x of instance y, whose argument
+// block sits at a compile-time position of the kernel-argument segment (MPPI_BATCH_DISPATCH, mppi_device.hpp: the body reads
+// its parameters as the single-instance kernel does, not through scratch).  Every block carries its own wpack and generator
+// state; the body is m44_group, unchanged: an instance's bits are those of its own launch.
+template <int NHID, bool AFFINE, bool CTRL, int NB>
+__global__ __launch_bounds__(512) void rollout_m44_batch_kernel(const QuadBatchArgsT<NB> b)
+{
+  __shared__ __attribute__((aligned(16))) M44Shared sh;
+#define MPPI_M44_BODY(A)                                                                                   \
+  do {                                                                                                     \
+    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* the smaller instance of the two */         \
+    m44_group<NHID, AFFINE, CTRL, true, false>((A), sh);                                                   \
+  } while (0)
+  MPPI_BATCH_DISPATCH(NB, b, MPPI_M44_BODY);
+#undef MPPI_M44_BODY
+}
+
+// the same enqueued one solve ahead (mppi_arm_batch): every instance's block carries its OWN handle's gate block, whose pose
+// wave polls replica blockIdx.x % kGateReplicas of it -- blockIdx.x is the group index inside the instance, as in the single
+// gated kernel
+template <int NHID, bool AFFINE, bool CTRL, int NB>
+__global__ __launch_bounds__(512) void rollout_m44_batch_gated_kernel(const QuadBatchArgsT<NB> b)
+{
+  __shared__ __attribute__((aligned(16))) M44Shared sh;
+#define MPPI_M44_BODY(A)                                                                                   \
+  do {                                                                                                     \
+    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* the smaller instance of the two */         \
+    m44_group<NHID, AFFINE, CTRL, true, true>((A), sh);                                                    \
+  } while (0)
+  MPPI_BATCH_DISPATCH(NB, b, MPPI_M44_BODY);
+#undef MPPI_M44_BODY
+}
+
 bool m44_variant_supported(int hidden, int n_hidden) { return hidden == 64 && (n_hidden == 2 || n_hidden == 4); }
 int m44_pack_floats(int n_hidden) { return (n_hidden == 2 ? m44_q_total<2>() : m44_q_total<4>()) * 64 * 4; }
 
@@ -350,5 +391,43 @@ hipError_t launch_rollout_m44(int hidden, int n_hidden, const RolloutArgs &a, bo
   if (n_hidden == 2) return split ? launch_m44<2, true>(a, stream) : launch_m44<2, false>(a, stream);
   return split ? launch_m44<4, true>(a, stream) : launch_m44<4, false>(a, stream);
 }
+
+template <int NHID>
+static hipError_t launch_m44_batch2(const QuadBatchArgsT<2> &b2, bool affine, bool ctrl, bool gated, dim3 grid, hipStream_t stream)
+{
+  const dim3 block(512);
+#define MPPI_M44_BATCH(KERN)                                                                                  \
+  do {                                                                                                        \
+    if (affine && !ctrl) hipLaunchKernelGGL((KERN<NHID, true, false, 2>), grid, block, 0, stream, b2);        \
+    else if (affine && ctrl) hipLaunchKernelGGL((KERN<NHID, true, true, 2>), grid, block, 0, stream, b2);     \
+    else if (!affine && !ctrl) hipLaunchKernelGGL((KERN<NHID, false, false, 2>), grid, block, 0, stream, b2); \
+    else hipLaunchKernelGGL((KERN<NHID, false, true, 2>), grid, block, 0, stream, b2);                        \
+  } while (0)
+  if (gated) MPPI_M44_BATCH(rollout_m44_batch_gated_kernel);
+  else MPPI_M44_BATCH(rollout_m44_batch_kernel);
+#undef MPPI_M44_BATCH
+  return hipGetLastError();
+}
+
+// the split form for the two controllers of a tick (two instances only: each (NHID, AFFINE, CTRL, gated) instance is a
+// 240-register kernel); every instance 6 -> 64 x n_hidden -> 4
+hipError_t launch_rollout_m44_batch(int n_hidden, const QuadBatchArgs &b, hipStream_t stream)
+{
+  if (b.n != 2 || !m44_variant_supported(kM44H, n_hidden)) return hipErrorInvalidValue;
+  bool affine = true, ctrl = false;  // the general forms are exact supersets (rollout_mfma.hip)
+  int gmax = 0;
+  const bool gated = b.inst[0].gate != nullptr;  // mppi_arm_batch: every instance gated on its own block, or none
+  for (int i = 0; i < b.n; i++) {
+    if ((b.inst[i].gate != nullptr) != gated || b.inst[i].K % kRolloutsPerWave != 0) return hipErrorInvalidValue;
+    affine = affine && b.inst[i].cost.affine != 0;
+    ctrl = ctrl || b.inst[i].cost.need_control_cost != 0;
+    gmax = b.inst[i].K / kRolloutsPerWave > gmax ? b.inst[i].K / kRolloutsPerWave : gmax;
+  }
+  const QuadBatchArgsT<2> b2 = batch_args_prefix<2>(b);
+  const dim3 grid(gmax, 2);
+  return n_hidden == 2 ? launch_m44_batch2<2>(b2, affine, ctrl, gated, grid, stream)
+                       : launch_m44_batch2<4>(b2, affine, ctrl, gated, grid, stream);
+}
+
 
 }  // namespace mppi

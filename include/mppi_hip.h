@@ -40,6 +40,8 @@ extern "C" {
  *    + mppi_debug_set_chained_ticks (mppi_control_ticks enqueues one solve ahead), + mppi_debug_min_cost;
  *    + mppi_arm, mppi_arm_batch, mppi_disarm, mppi_is_armed (solve-ahead for a new state every tick; compatible additions). */
 /*    (still 5) + rollout variant "lds44", name "mfma4x4x1_lds_l<N>_w<W>": no new export, nothing else changes. */
+/*    (still 5) + mppi_debug_launch_info (a debug hook; compatible addition); two handles of the automatic "m44" form or of
+ *    "lds44" share a launch in mppi_compute_control_batch / mppi_arm_batch: results unchanged. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -182,9 +184,12 @@ int mppi_synchronize(mppi_handle *h);
 /* The solves of n independent controllers enqueued together -- runControlLoop's tick
  * (PI/run_control_loop.cuh:218-219: actual-state and predicted-state controller, both of path_integral_main.cu:119-122)
  * -- states is [n][7], handles[i] solves from states + 7 i.  Where the handles' rollout kernels can share a launch
- * (network model, the four-wavefront form, same layer list and num_iters, all groups of 16 rollouts together at
- * most one per CU: 2 x K=1920 on 256 CUs) the n solves cost TWO kernel launches in all, on a stream of the library
- * shared by the device's handles; otherwise this is n calls of mppi_compute_control_async.  Either way every
+ * (network model, same layer list and num_iters, all groups of 16 rollouts together at most one per CU: 2 x K=1920 on
+ * 256 CUs; the forms that have a batched kernel: the four-wavefront form and the row forms for n <= 4, the automatic
+ * "m44" form of 64-wide nets and "lds44" -- forced on every handle, the whole layer list equal -- for n == 2; the
+ * basis-function model's three-wavefront form) the n solves cost TWO kernel launches in all, on a stream of the library
+ * shared by the device's handles; otherwise ("m44_chain", three m44 handles ...) this is n calls of
+ * mppi_compute_control_async.  mppi_debug_launch_info tells which it was.  Either way every
  * handle's results are bit for bit those of its own mppi_compute_control, collected per handle with
  * mppi_synchronize / mppi_get_results.  The blocking form waits for all of them. */
 int mppi_compute_control_batch_async(mppi_handle *const *handles, const float *states, int n);
@@ -205,7 +210,8 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
  * armed runs after that batch's gate opens. */
 int mppi_arm(mppi_handle *h, double max_wait_s);
 /* The same for the solves of one mppi_compute_control_batch[_async](handles, states, n) call: the shared one-launch form where
- * the batch would use it (the row form's batched kernel), otherwise each handle armed on its own where it can be
+ * the batch would use it and the form has a gated batched kernel (the row forms; two handles of the automatic "m44" form or of
+ * "lds44"), otherwise each handle armed on its own where it can be
  * (MPPI_ERR_UNSUPPORTED if one could not be; the others stay armed).  Only a batch call with the same handles in the same order
  * opens the gates; any other call on one of them calls the whole armed launch off first. */
 int mppi_arm_batch(mppi_handle *const *handles, int n, double max_wait_s);
@@ -361,6 +367,12 @@ int mppi_debug_set_chained_ticks(mppi_handle *h, int on);
  * LAST solve's tail kernel took beta from the rollout kernel (0 where the rollout form does not publish: by default every solve
  * of <= 8192 rollouts). */
 int mppi_debug_min_cost(mppi_handle *h, int on, int *from_rollout);
+
+/* Test / tooling hook: *instances = how many instances the rollout launch of this handle's most recently ENQUEUED solve served
+ * (an armed solve that is not yet opened counts; 1: a launch of its own; 2..4: shared with the other handles of a
+ * mppi_compute_control_batch / mppi_arm_batch call; 0: no solve yet), *gated = 1 if that launch was a gated one (mppi_arm,
+ * mppi_arm_batch, the chained mppi_control_ticks).  Recorded where the launch is made.  MPPI_ERR_INVALID for a NULL argument. */
+int mppi_debug_launch_info(mppi_handle *h, int *instances, int *gated);
 
 /* How long a blocking call (mppi_compute_control, mppi_synchronize, mppi_get_results ...) polls for a solve's result block
  * before it gives up with MPPI_ERR_HIP; default 30 s.  (The reference blocks in cudaStreamSynchronize without a limit,

@@ -11,7 +11,10 @@ fed through the per-tick calls a control loop makes: compute_async -> [arm] -> s
   batch_fresh  -- both controllers in one launch, unarmed (the predicted state: the actual one's nominal state one step on)
   batch_armed  -- both controllers, the next pair armed in one gated launch (mppi_arm_batch)
 Times are per tick (both solves + both slides), median of --repeats blocks of --ticks ticks, inside one library call
-per block where the library has one (one, batch)."""
+per block where the library has one (one, batch).
+The network is the shipped 6-32-32-4 model, or --model FILE.npz (e.g. tests/golden/models/wider_deeper_network_08_20_2020.npz),
+or a synthetic model of --layers 6,64,64,4; --variant forces a rollout form by name (e.g. lds44) on every handle.  Every mode's
+entry says how many instances its last rollout launch served (mppi_debug_launch_info): 2 where the pair shared a launch."""
 import ctypes as C
 import argparse
 import json
@@ -23,7 +26,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from autorally_amd import capi, synthetic as S  # noqa: E402
+from autorally_amd import capi, params as P, synthetic as S  # noqa: E402
 
 
 def main():
@@ -34,16 +37,31 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--modes", type=str, default="one,streams,batch")
     ap.add_argument("--max-wait", type=float, default=0.01, help="armed modes: mppi_arm's max_wait_s")
+    ap.add_argument("--layers", type=str, default=None, help="a synthetic model of this layer list, e.g. 6,64,64,4")
+    ap.add_argument("--model", type=str, default=None, help="a model file (.npz) instead of the shipped 6-32-32-4 one")
+    ap.add_argument("--variant", type=str, default=None, help="rollout form forced by name on every handle, e.g. lds44")
     a = ap.parse_args()
-    cfg = S.make_config(a.K, a.T, track="oval")
+    if a.model:
+        layers, theta = P.load_model_npz(a.model)
+        cfg = S.make_config(a.K, a.T, layers=list(layers), theta=theta, track="oval")
+    elif a.layers:
+        cfg = S.make_config(a.K, a.T, layers=[int(x) for x in a.layers.split(",")], track="oval")
+    else:
+        cfg = S.make_config(a.K, a.T, track="oval")
+
+    def solver():
+        s = capi.Solver(cfg)
+        if a.variant:
+            s.set_rollout_variant(a.variant)
+        return s
     st = cfg["start_state"]
     st2 = st.copy()
     st2[0] += 0.3
-    out = {"K": a.K, "T": a.T, "ticks": a.ticks}
+    out = {"K": a.K, "T": a.T, "ticks": a.ticks, "layers": list(cfg["layers"])}
     opt = int(cfg["opt_stride"])
     # the states of a control loop: each tick's state is the nominal trajectory's state at the optimization stride of the
     # tick before (recorded once; the timed blocks feed them again and again)
-    rec = capi.Solver(cfg)
+    rec = solver()
     seq, s_ = [], st.copy()
     for _ in range(a.ticks):
         ss, _ = rec.nominal_traj(s_)
@@ -56,7 +74,7 @@ def main():
     ptrs = [x.ctypes.data_as(fp) for x in seq]
     L = capi.lib()
     for mode in a.modes.split(","):
-        sols = [capi.Solver(cfg) for _ in range(1 if mode in ("one", "fresh", "armed") else 2)]
+        sols = [solver() for _ in range(1 if mode in ("one", "fresh", "armed") else 2)]
         hs = (C.c_void_p * len(sols))(*[x.h for x in sols])
 
         def ck(rc):
@@ -109,7 +127,7 @@ def main():
             block()
             ts.append(1e3 * (time.perf_counter() - t0) / a.ticks)
         out[mode] = {"ms_per_tick_median": float(np.median(ts)), "min": float(min(ts)), "max": float(max(ts)),
-                     "variant": sols[0].rollout_variant()}
+                     "variant": sols[0].rollout_variant(), "launch_instances": sols[0].debug_launch_info()[0]}
         if mode in ("armed", "batch_armed"):  # the armed path ran (every compute opened a gate): same results as unarmed
             out[mode]["U0"] = float(sols[0].get_control_seq()[0, 0])
         elif mode in ("fresh", "batch_fresh"):
