@@ -51,6 +51,8 @@ enum class Form : int {
                                     // accumulation chains (the automatic form) / Chain: one, the reference's order
   Lds44,                            // rollout_lds44.hip: any layer list up to 64 wide on v_mfma_f32_4x4x1, weights from LDS, every
                                     // layer one chain in the reference's order; by name only ("lds44")
+  Lds128,                           // rollout_lds128.hip: any layer list up to 128 wide, a layer as two halves of 64 neurons with an
+                                    // accumulator each, the reference's order; by name only ("lds128")
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
 };
@@ -144,6 +146,8 @@ struct mppi_handle {
   float *d_row64pack = nullptr;  // 64-wide nets: register + LDS image of rollout_row64.hip
   float *d_m44pack = nullptr;    // 64-wide nets: image of rollout_m44.hip
   float *d_lds44pack = nullptr;  // any layer list with hidden widths <= 64: image of rollout_lds44.hip
+  float *d_lds128pack = nullptr; // any layer list with hidden widths <= 128 whose image fits the LDS: image of rollout_lds128.hip
+  size_t lds128_bytes = 0;       // ... and its size
   bool valu_reg_ok = false;
   double *d_invt = nullptr;
   uint32_t *d_rng[2] = {nullptr, nullptr};
@@ -230,6 +234,7 @@ std::vector<float> pack_row_weights(const std::vector<float> &theta);
 std::vector<float> pack_row64_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
+std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
 int upload_rng_tables(mppi_handle *h);
 bool use_mfma(const mppi_handle *h);

@@ -259,6 +259,39 @@ std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const Net
   return out;
 }
 
+// Image of the two-half LDS form (rollout_lds128.hip), any layer list with hidden widths <= 128: float4 q of lane l at float4
+// index q * 64 + l.  First kLds128BiasQuads quads: float e = 2 j + h of lane l = bias of neuron 64 h + l of weight layer j (hidden
+// layers: b x kTanhScale, 0 where the neuron does not exist; output layer, e = 2 j: b_out[l >> 4]).  Then per weight layer
+// ceil(nin / 4) x H quads, H = ceil(nout / 64) halves (1 for the output layer), interleaved: quad q' H + h of the layer is
+// (W[64 h + l][4 q'] .. W[64 h + l][4 q' + 3]) -- lane l is neuron 64 h + l, the B operand of k steps 4 q' .. 4 q' + 3 of
+// accumulator h -- with the output layer's row c at lane 16 c.  Then kLds44Ahead quads the kernel's read-ahead may touch.  Every
+// entry without a weight (k >= nin, 64 h + l >= nout, the other lanes of the output layer) is 0.
+std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  std::vector<float> out((size_t)lds128_pack_floats(net), 0.0f);
+  const int n_w = net.n_layers - 1;
+  const float *p = theta.data();
+  int q0 = kLds128BiasQuads;
+  for (int j = 0; j < n_w; j++) {
+    const int nin = net.layers[j], nout = net.layers[j + 1];
+    const float *W = p, *B = p + (size_t)nout * nin;
+    const bool last = j == n_w - 1;
+    const int H = (!last && nout > 64) ? 2 : 1;
+    for (int h = 0; h < H; h++)
+      for (int l = 0; l < 64; l++) {
+        auto at = [&](int q, int c) -> float & { return out[((size_t)q * 64 + l) * 4 + c]; };
+        const int n = last ? ((l & 15) == 0 ? (l >> 4) : -1) : (64 * h + l < nout ? 64 * h + l : -1);  // the neuron whose row lane l holds
+        const int e = 2 * j + h;
+        at(e >> 2, e & 3) = last ? B[l >> 4] : (n >= 0 ? B[n] * kTanhScale : 0.0f);
+        if (n >= 0)
+          for (int k = 0; k < nin; k++) at(q0 + (k >> 2) * H + h, k & 3) = W[(size_t)n * nin + k];
+      }
+    q0 += ((nin + 3) / 4) * H;
+    p += (size_t)nout * nin + nout;
+  }
+  return out;
+}
+
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)
 {
   // base state: L'Ecuyer's default 12345 x 6, scrambled by the seed (DESIGN.md noise spec)

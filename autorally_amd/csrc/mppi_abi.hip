@@ -44,7 +44,7 @@ void free_all(mppi_handle *h)
 {
   if (!h) return;
   float *fp[] = {h->d_theta_s, h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
-                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_cap};
+                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_lds128pack, h->d_cap};
   for (float *p : fp)
     if (p) (void)hipFree(p);
   if (h->d_invt) (void)hipFree(h->d_invt);
@@ -240,6 +240,10 @@ int mppi_create(const mppi_config *cfg, mppi_handle **out)
   if (h->mfma_ok && m44_variant_supported(h->hidden, h->n_hidden))
     CR(hipMalloc(&h->d_m44pack, sizeof(float) * (size_t)m44_pack_floats(h->n_hidden)));
   if (!basis && lds44_supported(h->net)) CR(hipMalloc(&h->d_lds44pack, sizeof(float) * (size_t)lds44_pack_floats(h->net)));
+  if (!basis && lds128_supported(h->net)) {
+    h->lds128_bytes = sizeof(float) * (size_t)lds128_pack_floats(h->net);
+    CR(hipMalloc(&h->d_lds128pack, h->lds128_bytes));
+  }
   CR(hipMalloc(&h->d_rng[0], sizeof(uint32_t) * 6 * h->K));
   CR(hipMalloc(&h->d_rng[1], sizeof(uint32_t) * 6 * h->K));
   CR(hipMalloc(&h->d_jump, sizeof(uint32_t) * 18 * h->noise_C));
@@ -365,6 +369,11 @@ int mppi_set_nn_params(mppi_handle *h, const float *theta, size_t n)
   if (h->d_lds44pack) {
     const std::vector<float> pk = pack_lds44_weights(h->theta, h->net);
     HIPCHK(h, hipMemcpy(h->d_lds44pack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  if (h->d_lds128pack) {
+    const std::vector<float> pk = pack_lds128_weights(h->theta, h->net);
+    if (pk.size() * sizeof(float) != h->lds128_bytes) return fail(h, MPPI_ERR_INVALID, "lds128 image size");
+    HIPCHK(h, hipMemcpy(h->d_lds128pack, pk.data(), h->lds128_bytes, hipMemcpyHostToDevice));
   }
   h->have_nn = true;
   return MPPI_OK;

@@ -96,6 +96,18 @@ hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStr
 // two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
 hipError_t launch_rollout_lds44_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
 
+// rollout_lds128.hip: the lds44 group for ANY layer list 6 -> hidden widths 1..128 -> 4 whose image fits one workgroup's LDS:
+// a hidden layer is one or two halves of 64 neurons with an accumulator each, its inputs one or two transposed activation
+// sets walked k ascending (the reference's order: bit-identical to the other exact forms); a.wpack = pack_lds128_weights
+constexpr int kLds128BiasQuads = 4;  // float4 per lane in front of the weights: float 2 j + h = bias of half h of weight layer j
+bool lds128_supported(const NetDesc &net);
+int lds128_pack_floats(const NetDesc &net);
+size_t lds128_lds_bytes(const NetDesc &net);  // shared state + image of a list 6 -> 1..128 -> 4 (0 for any other list)
+size_t lds128_lds_limit();                    // the dynamic LDS a group may have
+hipError_t launch_rollout_lds128(const NetDesc &net, const RolloutArgs &a, hipStream_t stream);
+// two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
+hipError_t launch_rollout_lds128_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
+
 // rollout_bf.hip (GeneralizedLinear basis-function dynamics, W[4][25] in a.wpack)
 hipError_t launch_rollout_bf(const RolloutArgs &a, int waves, hipStream_t stream);  // waves per 64 rollouts: 1, 2, 3
 // several instances of the three-wave form in one launch (grid: groups of 64 rollouts x instances)

@@ -42,6 +42,8 @@ extern "C" {
 /*    (still 5) + rollout variant "lds44", name "mfma4x4x1_lds_l<N>_w<W>": no new export, nothing else changes. */
 /*    (still 5) + mppi_debug_launch_info (a debug hook; compatible addition); two handles of the automatic "m44" form or of
  *    "lds44" share a launch in mppi_compute_control_batch / mppi_arm_batch: results unchanged. */
+/*    (still 5) + rollout variant "lds128", name "mfma4x4x1_lds2h_l<N>_w<W>": hidden widths up to 128; no new export, nothing
+ *    else changes ("lds44" keeps refusing widths above 64). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -186,7 +188,7 @@ int mppi_synchronize(mppi_handle *h);
  * -- states is [n][7], handles[i] solves from states + 7 i.  Where the handles' rollout kernels can share a launch
  * (network model, same layer list and num_iters, all groups of 16 rollouts together at most one per CU: 2 x K=1920 on
  * 256 CUs; the forms that have a batched kernel: the four-wavefront form and the row forms for n <= 4, the automatic
- * "m44" form of 64-wide nets and "lds44" -- forced on every handle, the whole layer list equal -- for n == 2; the
+ * "m44" form of 64-wide nets and "lds44" / "lds128" -- forced on every handle, the whole layer list equal -- for n == 2; the
  * basis-function model's three-wavefront form) the n solves cost TWO kernel launches in all, on a stream of the library
  * shared by the device's handles; otherwise ("m44_chain", three m44 handles ...) this is n calls of
  * mppi_compute_control_async.  mppi_debug_launch_info tells which it was.  Either way every
@@ -211,7 +213,7 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
 int mppi_arm(mppi_handle *h, double max_wait_s);
 /* The same for the solves of one mppi_compute_control_batch[_async](handles, states, n) call: the shared one-launch form where
  * the batch would use it and the form has a gated batched kernel (the row forms; two handles of the automatic "m44" form or of
- * "lds44"), otherwise each handle armed on its own where it can be
+ * "lds44" or of "lds128"), otherwise each handle armed on its own where it can be
  * (MPPI_ERR_UNSUPPORTED if one could not be; the others stay armed).  Only a batch call with the same handles in the same order
  * opens the gates; any other call on one of them calls the whole armed launch off first. */
 int mppi_arm_batch(mppi_handle *const *handles, int n, double max_wait_s);
@@ -303,6 +305,12 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     shapes included) in the latency regime -- the m44 group with the weights of every layer read from LDS and the output layer
  *     as one more chain; by name only (never chosen automatically); has a gated form (mppi_arm, chained mppi_control_ticks);
  *     MPPI_ERR_UNSUPPORTED for the basis-function model, a hidden width above 64, or a list without a hidden layer
+ *     "lds128" mfma4x4x1_lds2h_l<hidden layers>_w<widest hidden layer>: the same for hidden widths 1..128 -- a layer is one or
+ *     two halves of 64 neurons with an accumulator each, its inputs walked k ascending over one or two activation sets; the
+ *     weight image must fit a workgroup's 160 KB of LDS beside 34 KB of rings (6-128-128-4: 141 KB; 6-128-128-128-4 does not);
+ *     by name only; gated form as "lds44"; lists up to 64 wide are accepted and give "lds44"'s bits, but belong to "lds44";
+ *     MPPI_ERR_UNSUPPORTED for the basis-function model, a hidden width above 128, a list without a hidden layer, or an
+ *     image that does not fit (the message states needed and available bytes)
  *   A/B arms and cross-checks (never chosen automatically)
  *     "valu" valu_reg_lds (lane = rollout, the independent implementation every parity test also runs; config 4's untuned
  *     vector-ALU reference), "valu_lds" (the generic kernel on a standard shape), "row64" = "row64_r16"
