@@ -109,41 +109,72 @@ class Ref64:
         return sd
 
     # ---------------------------------------------------------------- costs
-    def texel(self, x, y):
-        """Point-sampled, clamped, normalised-coordinate texture of channel 0 after the projective coorTransform
-        (PI/costs.cu:128-154, 351-357, 373-377)."""
+    def grid(self, x, y):
+        """The continuous texel coordinates (column, row) of a world point after the projective coorTransform
+        (PI/costs.cu:351-357, 373-377): u / w x W, v / w x H."""
         u = self.r_c1[0] * x + self.r_c2[0] * y + self.trs[0]
         v = self.r_c1[1] * x + self.r_c2[1] * y + self.trs[1]
         w = self.r_c1[2] * x + self.r_c2[2] * y + self.trs[2]
         H, W = self.map0.shape
         with np.errstate(invalid="ignore", divide="ignore"):
-            fi = np.floor(u / w * W)
-            fj = np.floor(v / w * H)
+            return u / w * W, v / w * H
+
+    def nearest(self, g):
+        """Point sampling of a normalised coordinate: the texel a continuous coordinate falls into."""
+        return np.floor(g)
+
+    def texel(self, x, y):
+        """Point-sampled, clamped, normalised-coordinate texture of channel 0 (PI/costs.cu:128-154)."""
+        gi, gj = self.grid(x, y)
+        H, W = self.map0.shape
+        fi, fj = self.nearest(gi), self.nearest(gj)
         fi = np.clip(np.where(fi >= 0, fi, 0.0), 0, W - 1).astype(np.int64)  # NaN -> 0 as the border clamp does
         fj = np.clip(np.where(fj >= 0, fj, 0.0), 0, H - 1).astype(np.int64)
         return self.map0[fj, fi]
 
-    def compute_cost(self, s, u, du, crash):
-        """MPPICosts::computeCost (PI/costs.cu:396-409) and what it calls (:307-393): u clamped, du unclamped.  `crash` [N]
-        (int) is updated in place by the boundary test."""
+    # the cost's branches, one method each: the mutants of tests/test_branch_scenes.py override one of them
+    def control_cost(self, u, du, v):
+        """u clamped, du unclamped (v, the control before the clamp, is not used)."""
         P = self.cost
-        control = P["steering_coeff"] * du[:, 0] * (u[:, 0] - du[:, 0]) / (self.nu[0] ** 2) + \
+        return P["steering_coeff"] * du[:, 0] * (u[:, 0] - du[:, 0]) / (self.nu[0] ** 2) + \
             P["throttle_coeff"] * du[:, 1] * (u[:, 1] - du[:, 1]) / (self.nu[1] ** 2)
+
+    def slop_zeroed(self, track):
+        return np.abs(track) < self.cost["track_slop"]
+
+    def on_boundary(self, tf, tb):
+        return (tf >= self.cost["boundary_threshold"]) | (tb >= self.cost["boundary_threshold"])
+
+    def slip_over(self, slip):
+        return np.abs(slip) > self.cost["max_slip_ang"]
+
+    def rolled(self, s):
+        """getCrash, costs.cu:301-305"""
+        return np.abs(s[:, 3]) > 1.57
+
+    def compute_cost(self, s, u, du, crash, v=None, out=None):
+        """MPPICosts::computeCost (PI/costs.cu:396-409) and what it calls (:307-393): u clamped, du unclamped.  `crash` [N]
+        (int) is updated in place by the boundary test.  out: a dict that receives the branch record of this step."""
+        P = self.cost
+        control = self.control_cost(u, du, v)
         c, sn = np.cos(s[:, 2]), np.sin(s[:, 2])
         tf = self.texel(s[:, 0] + 0.5 * c, s[:, 1] + 0.5 * sn)
         tb = self.texel(s[:, 0] - 0.5 * c, s[:, 1] - 0.5 * sn)
         track = (np.abs(tf) + np.abs(tb)) / 2.0
-        track = np.where(np.abs(track) < P["track_slop"], 0.0, P["track_coeff"] * track)
-        crash |= ((tf >= P["boundary_threshold"]) | (tb >= P["boundary_threshold"])).astype(crash.dtype)
+        zeroed = self.slop_zeroed(track)
+        track = np.where(zeroed, 0.0, P["track_coeff"] * track)
+        crash |= self.on_boundary(tf, tb).astype(crash.dtype)
         err = s[:, 4] - P["desired_speed"]
         speed = P["speed_coeff"] * (np.abs(err) if P.get("l1_cost") else err * err)
         crash_cost = (1.0 - P["discount"]) * np.where(crash > 0, P["crash_coeff"], 0.0)
         moving = np.abs(s[:, 4]) > 0.001
         with np.errstate(divide="ignore", invalid="ignore"):
             slip = -np.arctan(s[:, 5] / np.abs(s[:, 4]))
-        stab = np.where(moving, P["slip_penalty"] * slip * slip +
-                        np.where(np.abs(slip) > P["max_slip_ang"], P["crash_coeff"], 0.0), 0.0)
+        over = self.slip_over(slip)
+        stab = np.where(moving, P["slip_penalty"] * slip * slip + np.where(over, P["crash_coeff"], 0.0), 0.0)
         cost = control + speed + crash_cost + track + stab
+        if out is not None:
+            out.update(tf=tf, tb=tb, zeroed=zeroed, slip=slip, over=over & moving)
         return np.where((cost > 1e12) | np.isnan(cost), 1e12, cost)
 
     # ---------------------------------------------------------------- rollouts
@@ -162,19 +193,77 @@ class Ref64:
         return V, du
 
     def rollouts(self, state, U, eps):
-        """Returns (costs [K], V [K, T, 2], crash [K]); the running mean of the cost from t = 1 on, terminal cost 0."""
+        """Returns (costs [K], V [K, T, 2], crash [K]); the running mean of the cost from t = 1 on, terminal cost 0.  The one
+        loop over the steps is trace()'s."""
+        tr = self.trace(state, U, eps)
+        return tr["costs"], tr["V"], tr["crash"]
+
+    def after_update(self, s, crash):
+        """The sticky flag after the state update: the cost of the NEXT step is the first to see it."""
+        crash |= self.rolled(s).astype(crash.dtype)
+
+    def trace(self, state, U, eps):
+        """rollouts() with the record of every branch of the cost, over the steps that enter it (t = 1 .. T-1; arrays [K, T]
+        hold +inf / False / 0 at t = 0):
+          margins -- the distance to every discontinuity:
+            m_texel  metres from the front or the back point to the nearest texel edge, along both axes of the projective grid
+            m_roll   | |roll| - 1.57 | of the state after update t-1, the one step t's flag is taken from ([K, T + 1]: the entry
+                     T is the final update's, which no cost sees)
+            m_slip   | |slip| - max_slip_ang |
+          events:
+            first [K] the step whose cost is the first to see the crash flag (-1: never), source [K] what set it there
+            (bits: 1 front point, 2 back point, 4 roll);
+            roll_first [K] the update (0 .. T-1) after which |roll| first exceeds 1.57 (-1: never);
+            roll_over [K, T + 1] |roll| > 1.57 after update t-1, indexed as m_roll;
+            front, back [K, T] the point is on the boundary; zeroed [K, T] the track cost is zeroed by the slop;
+            over [K, T] beyond the slip limit;
+            clamp [K, T, 2] -1 / +1 where a control is cut at its lower / upper limit (t = 0 included: the dynamics see it);
+            min_ux [K] the smallest u_x of the rollout."""
         K, T = self.K, self.T
         V, du = self.controls(U, eps)
         s = np.tile(np.asarray(state, np.float32).astype(f64).reshape(1, 7), (K, 1))
+        H, W = self.map0.shape
+        # metres per texel along a grid axis: 1 / (W |grad(u / w)|), at w ~ 1 (the third row is a few 1e-4 per metre)
+        mx = 1.0 / (W * np.hypot(self.r_c1[0], self.r_c2[0]))
+        my = 1.0 / (H * np.hypot(self.r_c1[1], self.r_c2[1]))
         crash = np.zeros(K, np.int64)
         running = np.zeros(K, f64)
+        rec = dict(m_texel=np.full((K, T), np.inf), m_roll=np.full((K, T + 1), np.inf), m_slip=np.full((K, T), np.inf),
+                   front=np.zeros((K, T), bool), back=np.zeros((K, T), bool), zeroed=np.zeros((K, T), bool),
+                   over=np.zeros((K, T), bool), clamp=np.zeros((K, T, 2), np.int8), first=np.full(K, -1), source=np.zeros(K, np.int64),
+                   roll_first=np.full(K, -1), min_ux=np.full(K, np.inf), roll_over=np.zeros((K, T + 1), bool))
+        roll_flag = np.zeros(K, bool)
         for t in range(T):
-            u = np.clip(V[:, t], self.u_lo, self.u_hi)  # enforceConstraints, neural_net_model.cu:311-323
+            u = np.clip(V[:, t], self.u_lo, self.u_hi)
+            rec["clamp"][:, t] = (V[:, t] > self.u_hi).astype(np.int8) - (V[:, t] < self.u_lo).astype(np.int8)
+            rec["min_ux"] = np.minimum(rec["min_ux"], s[:, 4])
             if t > 0:
-                running += (self.compute_cost(s, u, du[:, t], crash) - running) / t
+                before = crash > 0
+                out = {}
+                running += (self.compute_cost(s, u, du[:, t], crash, V[:, t], out) - running) / t
+                c, sn = np.cos(s[:, 2]), np.sin(s[:, 2])
+                d = []
+                for sg in (0.5, -0.5):
+                    gi, gj = self.grid(s[:, 0] + sg * c, s[:, 1] + sg * sn)
+                    fi, fj = gi - np.floor(gi), gj - np.floor(gj)
+                    d += [np.minimum(fi, 1.0 - fi) * mx, np.minimum(fj, 1.0 - fj) * my]
+                rec["m_texel"][:, t] = np.min(d, axis=0)
+                rec["m_slip"][:, t] = np.abs(np.abs(out["slip"]) - self.cost["max_slip_ang"])
+                rec["front"][:, t] = out["tf"] >= self.cost["boundary_threshold"]
+                rec["back"][:, t] = out["tb"] >= self.cost["boundary_threshold"]
+                rec["zeroed"][:, t], rec["over"][:, t] = out["zeroed"], out["over"]
+                new = (crash > 0) & (rec["first"] < 0)
+                rec["first"][new] = t
+                rec["source"][new] = (rec["front"][new, t] * 1 + rec["back"][new, t] * 2 + (roll_flag & before)[new] * 4)
             s = s + self.state_deriv(s, u) * self.dt
-            crash |= (np.abs(s[:, 3]) > 1.57).astype(np.int64)  # getCrash, costs.cu:301-305
-        return running, V, crash
+            self.after_update(s, crash)
+            rec["m_roll"][:, t + 1] = np.abs(np.abs(s[:, 3]) - 1.57)
+            now = self.rolled(s)
+            rec["roll_over"][:, t + 1] = now
+            rec["roll_first"][now & ~roll_flag] = t
+            roll_flag |= now
+        rec.update(costs=running, V=V, crash=crash)
+        return rec
 
     # ---------------------------------------------------------------- the tail stages
     def weights(self, costs):

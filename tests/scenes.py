@@ -8,7 +8,8 @@ Here:
     of a rollout moves its cost by less than RAMP_FLIP_BOUND relative (a tenth of the 1e-5 bar), far below
     boundary_threshold, with track_slop = 0, behind a projective transform (w != 1).  For the same reason the texel lookup
     and the projective division are EXERCISED here, not verified: dropping the division or reading the next texel moves a
-    cost by less than the bar.  The lookup is pinned elsewhere (the debug cost raster and the oval-track parity tests);
+    cost by less than the bar.  The lookup and the division are VERIFIED on the patchwork scene below (patchwork_config: coarse
+    texels whose neighbours differ by 0.03 or more, held to float64 rollout by rollout by tests/test_branch_rollouts_gpu.py);
   * max_slip_ang >= pi/2 (|atan| never exceeds it), the roll and u_x stay well inside (checked by the CPU tests: no crash
     flag, u_x > 1 on every step of every rollout);
   * the start pose and its front and back points lie at least a fifth of a texel from every texel edge, and the control-cost
@@ -54,23 +55,22 @@ def ramp_transform():
     return r_c1, r_c2, trs
 
 
-def ramp_start(x=1.0, y=-2.0, heading=0.4, speed=6.0):
+def ramp_start(x=1.0, y=-2.0, heading=0.4, speed=6.0, roll=0.0, u_y=0.0, n=2 * MAP_HALF * MAP_PPM, step=0.01):
     """A start pose whose front and back points (+-0.5 m along the heading) fall inside texels: the position is moved until
-    both are at least a fifth of a texel from every edge of the projective grid."""
+    both are at least a fifth of a texel from every edge of the projective grid (n texels across the map)."""
     r_c1, r_c2, trs = ramp_transform()
-    n = 2 * MAP_HALF * MAP_PPM
 
     def frac(px, py):
         w = r_c1[2] * px + r_c2[2] * py + trs[2]
         return [((r_c1[0] * px + r_c2[0] * py + trs[0]) / w * n) % 1.0, ((r_c1[1] * px + r_c2[1] * py + trs[1]) / w * n) % 1.0]
 
     c, s = np.cos(heading), np.sin(heading)
-    for i in range(40):  # over a texel (0.2 m) in x and in y, 0.01 m apart
+    for i in range(40):  # over a texel (0.2 m on the ramp) in x and in y, step (0.01 m) apart
         for j in range(40):
-            px, py = x + 0.01 * i, y + 0.01 * j
+            px, py = x + step * i, y + step * j
             fr = frac(px + 0.5 * c, py + 0.5 * s) + frac(px - 0.5 * c, py - 0.5 * s) + frac(px, py)
             if all(0.2 < f < 0.8 for f in fr):
-                return np.array([px, py, heading, 0.0, speed, 0.0, 0.0], np.float32)
+                return np.array([px, py, heading, roll, speed, u_y, 0.0], np.float32)
     raise AssertionError("no start pose off the texel edges")
 
 
@@ -82,6 +82,52 @@ def gentle_model(layers, seed=4, out_scale=0.25):
     n_out = layers[-2] * layers[-1] + layers[-1]
     theta[-n_out:] *= np.float32(out_scale)
     return layers, theta
+
+
+IN_ROLL, IN_UX, IN_UY, IN_YAW_RATE, IN_STEER, IN_THROTTLE = range(6)   # the network's inputs: state[3 .. 6], then the controls
+OUT_ROLL, OUT_UX, OUT_UY, OUT_YAW_RATE = range(4)                       # its outputs: the derivatives of state[3 .. 6]
+
+
+def family(layers, bf_W):
+    """Which dynamics a problem has: the basis-function model, the shipped network, or a synthetic wired one."""
+    return "bf" if bf_W is not None else "shipped" if layers is None else "wired"
+
+
+def wired_model(layers, wires, bias=None, seed=4, out_scale=0.25, wire_only=()):
+    """gentle_model with a few wires laid through it, so that a control moves one state derivative by a chosen amount
+    (the generic weights alone answer a control with millimetres over a hundred steps): wire i = (input, offset, output, gain)
+    takes hidden unit i of every hidden layer -- its row is replaced by a single 1 on the input (first layer, bias -offset) or
+    on unit i of the layer before (bias 0) -- and adds gain x tanh(.. tanh(input - offset)) to the output.  bias: {output:
+    value added to its bias}; wire_only: outputs whose generic row and bias are zeroed first, so that only wires drive them.
+    The other rows keep their generic dense values."""
+    return lay_wires(*gentle_model(layers, seed=seed, out_scale=out_scale), wires, bias, wire_only)
+
+
+def lay_wires(layers, theta, wires, bias=None, wire_only=()):
+    """wired_model's wires through a given packed network."""
+    assert len(wires) <= min(layers[1:-1])
+    theta = theta.astype(np.float64)
+    off = 0
+    last = len(layers) - 2
+    for l, (nin, nout) in enumerate(zip(layers[:-1], layers[1:])):
+        W = theta[off:off + nout * nin].reshape(nout, nin)   # views: the edits land in theta
+        b = theta[off + nout * nin:off + nout * nin + nout]
+        if l == last:
+            for out in wire_only:
+                W[out, :] = 0.0
+                b[out] = 0.0
+        for i, (inp, offset, out, gain) in enumerate(wires):
+            if l < last:
+                W[i, :] = 0.0
+                W[i, inp if l == 0 else i] = 1.0
+                b[i] = -offset if l == 0 else 0.0
+            else:
+                W[out, i] += gain
+        if l == last:
+            for out, v in (bias or {}).items():
+                b[out] += v
+        off += nout * nin + nout
+    return layers, theta.astype(np.float32)
 
 
 def ramp_config(K, T, layers=None, theta=None, bf_W=None, **over):
@@ -108,3 +154,159 @@ def ramp_U(cfg, seed=7):
     rng = np.random.RandomState(seed)
     U = np.stack([0.08 * np.sin(t / 11.0 + rng.uniform(0, 1)), 0.35 + 0.05 * np.cos(t / 13.0)], axis=1)
     return U.astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The two branch scenes (tests/test_branch_scenes.py on the CPU, tests/test_branch_rollouts_gpu.py on the GPU): the cost's
+# discontinuities FIRE here, and a rollout is held to float64 with no allowance wherever ref64 says it is DECIDED: every one of
+# its margins (ref64.Ref64.trace) at least the DELTA of its class away from the discontinuity.
+PATCH_TEXEL_M = 2.0      # texel edge of the patchwork map, metres: 64 x 64 texels over the ramp's bounds
+PATCH_SLOP = 0.05
+PATCH_LOW, PATCH_PLAIN, PATCH_HIGH = (0.005, 0.04), (0.1, 0.6), (0.7, 1.0)   # value classes: under the slop, plain, boundary
+PATCH_SHARES = (0.3, 0.55, 0.15)
+PATCH_MAP_SEED = 3
+PATCH_STEER_GAIN = 12.0     # the steering wire of a synthetic network: yaw acceleration, rad / s^2, per tanh(.. tanh(steering))
+# start poses per model family and horizon (up to 17 steps, up to 37, beyond), found by search: the stem of the fan of rollouts
+# runs over texels off the boundary, the fan itself over boundary texels in part (the coverage tests of test_branch_scenes.py).
+# At 17 steps the fan is 0.2 m wide and long: a boundary texel's edge cuts it during the last three steps
+PATCH_START = {("shipped", 17): dict(x=8.51, y=2.37, heading=1.82), ("bf", 17): dict(x=2.89, y=9.05, heading=2.49),
+               ("wired", 17): dict(x=5.56, y=0.73, heading=-1.29),
+               ("shipped", 37): dict(x=-5.4, y=-13.2, heading=-2.97), ("shipped", 100): dict(x=14.9, y=-14.1, heading=2.29),
+               ("bf", 37): dict(x=-5.4, y=-13.2, heading=-2.97), ("bf", 100): dict(x=15.9, y=-6.4, heading=2.62),
+               ("wired", 37): dict(x=4.4, y=6.9, heading=-1.17), ("wired", 100): dict(x=-3.0, y=6.0, heading=-0.82)}
+PATCH_START_2 = {("wired", 37): dict(x=-6.7, y=1.5, heading=0.7), ("wired", 100): dict(x=-4.8, y=14.2, heading=-0.57)}   # a second handle
+PATCH_NEIGHBOUR_MIN = 0.03   # edge-sharing texels differ by at least this: a wrong texel moves the step's track cost by >= 3
+                             # (track_coeff x 0.03 / 2), unless the slop zeroes the pair's average with either texel
+
+
+def patch_horizon(T):
+    """The key of PATCH_START a horizon falls under."""
+    return 17 if T <= 17 else 37 if T <= 37 else 100
+
+
+def patchwork_map(texel_m=PATCH_TEXEL_M, seed=PATCH_MAP_SEED):
+    """Random values of three classes from a fixed seed; a texel closer than PATCH_NEIGHBOUR_MIN to its left or upper
+    neighbour is drawn again."""
+    n = int(round(2 * MAP_HALF / texel_m))
+    rng = np.random.RandomState(seed)
+    ranges = (PATCH_LOW, PATCH_PLAIN, PATCH_HIGH)
+
+    def draw():
+        lo, hi = ranges[rng.choice(3, p=PATCH_SHARES)]
+        return rng.uniform(lo, hi)
+
+    ch0 = np.zeros((n, n), np.float64)
+    for j in range(n):
+        for i in range(n):
+            while True:
+                v = draw()
+                if (i == 0 or abs(v - ch0[j, i - 1]) >= PATCH_NEIGHBOUR_MIN) and (j == 0 or abs(v - ch0[j - 1, i]) >= PATCH_NEIGHBOUR_MIN):
+                    break
+            ch0[j, i] = v
+    return S.map_rgba_from_channel0(ch0.astype(np.float32))
+
+
+def check_patchwork_map(cfg):
+    """The two conditions that leave the threshold compares to the texel alone: no value within 0.01 of boundary_threshold,
+    no pair average (|a| + |b|) / 2 of two map values within 1e-3 of track_slop; and the neighbour rule of patchwork_map."""
+    v = np.unique(np.abs(cfg["map_rgba"][:, :, 0].astype(np.float64)))
+    assert np.all(np.abs(v - float(np.float32(cfg["cost"]["boundary_threshold"]))) >= 0.01)
+    avg = (v[:, None] + v[None, :]) / 2.0
+    assert np.all(np.abs(avg - float(np.float32(cfg["cost"]["track_slop"]))) >= 1e-3)
+    m = cfg["map_rgba"][:, :, 0].astype(np.float64)
+    assert np.all(np.abs(np.diff(m, axis=0)) >= PATCH_NEIGHBOUR_MIN - 1e-6) and np.all(np.abs(np.diff(m, axis=1)) >= PATCH_NEIGHBOUR_MIN - 1e-6)
+    shares = [np.mean((m >= lo) & (m <= hi)) for lo, hi in (PATCH_LOW, PATCH_PLAIN, PATCH_HIGH)]
+    assert abs(sum(shares) - 1.0) < 1e-12 and min(shares) > 0.1, shares
+
+
+def patchwork_config(K, T, layers=None, bf_W=None, texel_m=PATCH_TEXEL_M, map_seed=PATCH_MAP_SEED, start=None, **over):
+    """The TRACK branches: ramp_config (its projective transform, control-cost coefficients and stride) on a coarse random
+    costmap whose texels are under the slop, plain, or on the boundary.  A wrong texel or a dropped division by w moves a
+    step's cost far beyond the bar; the slop and the boundary compares are decided by the texel alone (check_patchwork_map).
+    A synthetic network gets a steering wire into the yaw rate (wired_model), so that the rollouts fan out over the texels as
+    those of the shipped models do."""
+    theta = None
+    if bf_W is None and layers is not None:
+        layers, theta = wired_model(layers, [(IN_STEER, 0.0, OUT_YAW_RATE, PATCH_STEER_GAIN)])
+    cfg = ramp_config(K, T, layers=layers, theta=theta, bf_W=bf_W)
+    n = int(round(2 * MAP_HALF / texel_m))
+    st = dict(PATCH_START[family(layers, bf_W), patch_horizon(T)], **(start or {}))
+    cfg.update(map_rgba=patchwork_map(texel_m, map_seed), cost=dict(cfg["cost"], track_slop=PATCH_SLOP), track="patchwork",
+               start_state=ramp_start(n=n, step=texel_m / 40.0, **st))
+    cfg.update(over)
+    return cfg
+
+
+TILT_U_LO, TILT_U_HI = (-0.3, 0.1), (0.3, 0.6)   # both controls clamp on both sides (nu = 0.275, 0.3 about ramp_U)
+TILT_SLIP = 0.25                                  # max_slip_ang
+TILT_COSTS = {"l2": dict(l1_cost=False, discount=0.25), "l1": dict(l1_cost=True, discount=0.4)}   # the default discount is 0.1
+TILT_ROLL_GAIN, TILT_UY_GAIN = 5.0, 10.0
+TILT_ROLL_BELOW = 1.0   # the start roll under 1.57, in sigmas of the roll's random walk
+
+
+# DELTA per margin class: ten times the largest margin at which ANY rollout of the fp32 oracle (modes 1 and 0) differs from
+# ref64 by more than TOL64, over every case of tests/branch_cases.py (3 scenes x 13 layer lists x 3 shapes), rounded up; measured
+# on the CPU by tests/measure_branch_deltas.py before any GPU run.  The factor stands for the device's tanh / sincos / atan
+# against libm, as TOL64's own headroom does.
+#   texel: 6.1e-6 m (27 such rollouts; patchwork, 6-32x4-4, K = 1984, T = 100, rollout 1042) -- fp32 positions within 20 m of the
+#          origin carry 1e-6 m per ulp, a hundred state updates add up a few of them.  With start poses 40 m out the same
+#          measurement gave 2.2e-5 m: the start poses stay within 20 m of the origin.
+#   slip:  3.25e-8 rad (4 such rollouts; tilt-slide l2, 6-33-97-66-4, K = 1984, T = 100, rollout 90); an fp32 ulp of 0.25 is 3e-8
+#   roll:  no oracle rollout beyond TOL64 has the roll as its nearest margin, so there is no measured figure.  From the number
+#          format instead: the roll is a sum of up to 100 fp32 updates near 1.57, each rounded to half an ulp of 1.2e-7; a
+#          hundred roundings of one sign would add up to 6e-6, their random sum to 6e-7: DELTA_ROLL = 1e-6, eight ulps.
+# On the decided rollouts the oracle then agrees with ref64 to 1.5e-6 relative at most (the bar of the CPU tests: 2e-6).
+DELTA_TEXEL, DELTA_ROLL, DELTA_SLIP = 7e-5, 1e-6, 5e-7   # metres, radians, radians
+UNDECIDED_CAP = 0.10     # of K
+
+
+def decided(cfg, tr):
+    """[K] bool: the rollouts of a ref64 trace (ref64.Ref64.trace) whose every margin is at least the DELTA of its class, over
+    the steps that enter the cost.  The texel class counts on the patchwork only (on the ramp a wrong texel moves a cost by
+    less than RAMP_FLIP_BOUND); the roll class up to the first update after which |roll| exceeds 1.57 by DELTA_ROLL or more:
+    the flag is sticky, no later roll reaches a cost."""
+    T = int(cfg["T"])
+    ok = tr["m_slip"][:, 1:T].min(axis=1) >= DELTA_SLIP if T > 1 else np.ones(int(cfg["K"]), bool)
+    if cfg["track"] == "patchwork":
+        ok &= tr["m_texel"][:, 1:T].min(axis=1) >= DELTA_TEXEL
+    m, over = tr["m_roll"][:, 1:T], tr["roll_over"][:, 1:T]    # after the updates 0 .. T-2: what the costs of 1 .. T-1 see
+    sure = over & (m >= DELTA_ROLL)
+    open_yet = np.cumsum(sure, axis=1) - sure == 0             # no decisive firing before this update
+    ok &= np.where(open_yet, m, np.inf).min(axis=1) >= DELTA_ROLL
+    return ok
+
+
+def tilt_slide_config(K, T, layers=None, bf_W=None, variant="l2", roll_below=None, **over):
+    """The STATE branches on the ramp map (the track stays flip-free): the start roll sits a little under 1.57 and the model's
+    roll rate follows the steering, so that part of the rollouts tip over -- the sticky flag getCrash sets after the state
+    update; the start lateral velocity puts the slip angle a little under max_slip_ang = TILT_SLIP and the lateral
+    acceleration follows the throttle, so that |slip| goes over the limit and comes back (not sticky).  variant: the key of
+    TILT_COSTS (speed cost l2 / l1, two discounts); roll_below: the start roll under 1.57 in sigmas of the roll's random walk,
+    if not TILT_ROLL_BELOW (2.9: one or two rollouts in a hundred tip over)."""
+    theta = None
+    speed = 6.0
+    sigma = 0.004 * np.sqrt(T)   # dt x the clamped steering noise through the wire (about 0.2), summed over T steps
+    wires = [(IN_STEER, 0.0, OUT_ROLL, TILT_ROLL_GAIN), (IN_THROTTLE, 0.35, OUT_UY, TILT_UY_GAIN)]   # ramp_U's throttle: about 0.35
+    if bf_W is not None:
+        # the shipped weights at 3 % of their strength: a roll of 1.5 and a slide of 1.5 m/s are far outside what they were
+        # fitted on (at a tenth the yaw rate still runs away within 100 steps); roll and u_y are driven by their wires alone
+        bf_W = np.array(bf_W, np.float32).reshape(4, 25).copy() * np.float32(0.03)
+        bf_W[OUT_UY, :] = 0.0
+        bf_W[OUT_ROLL, :] = 0.0
+        bf_W[OUT_ROLL, 8] += TILT_ROLL_GAIN    # basis function 8: sin(steering)
+        bf_W[OUT_UY, 0] += TILT_UY_GAIN        # basis function 0: the throttle, less its 0.35 through function 1, u_x / 10
+        bf_W[OUT_UY, 1] -= TILT_UY_GAIN * 0.35 / (0.1 * speed)
+    elif layers is None:   # the shipped hidden layers, the output layer a tenth as strong (as above), and the wires
+        layers, theta = S.default_model()
+        theta = theta.copy()
+        n_out = layers[-2] * layers[-1] + layers[-1]
+        theta[-n_out:] *= np.float32(0.1)
+        layers, theta = lay_wires(layers, theta, wires, wire_only=(OUT_ROLL, OUT_UY))
+    else:
+        layers, theta = wired_model(layers, wires, wire_only=(OUT_ROLL, OUT_UY))
+    cfg = ramp_config(K, T, layers=layers, theta=theta, bf_W=bf_W)
+    cfg.update(cost=dict(cfg["cost"], max_slip_ang=TILT_SLIP, **TILT_COSTS[variant]), track="tilt_slide", u_lo=TILT_U_LO, u_hi=TILT_U_HI,
+               start_state=ramp_start(speed=speed, roll=1.57 - TILT_ROLL_GAIN * (roll_below or TILT_ROLL_BELOW) * sigma,
+                                      u_y=speed * np.tan(TILT_SLIP - 0.005)))
+    cfg.update(over)
+    return cfg

@@ -297,7 +297,8 @@ def test_chained_control_ticks_equal_the_unchained_loop(net, K, T, opt):
 
 @pytest.mark.parametrize("armed", [False, True])
 def test_a_batch_of_two_handles_keeps_each_handle_its_own_bits(armed):
-    """The form has no shared launch: a batch is n asynchronous solves and mppi_arm_batch arms each handle on its own."""
+    """Two handles with two DIFFERENT layer lists do not share a launch (two handles of one list do: tests/test_batch_wide_gpu.py):
+    this batch falls back to n asynchronous solves and mppi_arm_batch arms each handle on its own."""
     nets, Ks, T = ([6, 32, 32, 32, 4], [6, 16, 24, 4]), (1920, 512), 33
     cfgs = [S.make_config(K, T, layers=list(net), track="oval", opt_stride=1, instance=i) for i, (net, K) in enumerate(zip(nets, Ks))]
     solo = []
