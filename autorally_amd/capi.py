@@ -66,6 +66,7 @@ SYMBOLS = [
     "mppi_debug_capture_iterations", "mppi_debug_get_iterations", "mppi_set_wait_timeout", "mppi_debug_form_candidates",
     "mppi_debug_set_chained_ticks", "mppi_debug_min_cost",
     "mppi_arm", "mppi_arm_batch", "mppi_disarm", "mppi_is_armed", "mppi_debug_launch_info",
+    "mppi_trace_rollouts", "mppi_top_rollouts",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -75,6 +76,9 @@ ABI3_SYMBOLS = ("mppi_compute_feedback_gains_pair", "mppi_set_host_threads")
 ABI4_SYMBOLS = ("mppi_debug_capture_iterations", "mppi_debug_get_iterations", "mppi_set_wait_timeout", "mppi_debug_form_candidates")
 ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost", "mppi_arm", "mppi_arm_batch", "mppi_disarm",
                 "mppi_is_armed")
+
+# added to version 5 as compatible additions: an older version-5 library (a kernel A/B through MPPI_LIB_PATH) lacks them
+UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_top_rollouts")
 
 _lib = None
 
@@ -169,9 +173,13 @@ def lib():
             L.mppi_is_armed.argtypes = [hp]
         if hasattr(L, "mppi_debug_launch_info"):  # added without a version step: an older version-5 library lacks it
             L.mppi_debug_launch_info.argtypes = [hp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        if hasattr(L, "mppi_trace_rollouts"):  # added without a version step, like mppi_debug_launch_info
+            ip = C.POINTER(C.c_int)
+            L.mppi_trace_rollouts.argtypes = [hp, ip, C.c_int, fp, fp, fp, fp, ip]
+            L.mppi_top_rollouts.argtypes = [hp, C.c_int, ip]
         for s in SYMBOLS:  # every declared symbol of the library's ABI version must be there
             if (v2 or s not in ABI2_SYMBOLS) and (v3 or s not in ABI3_SYMBOLS) and (v4 or s not in ABI4_SYMBOLS) and \
-                    (v5 or s not in ABI5_SYMBOLS) and s != "mppi_debug_launch_info":
+                    (v5 or s not in ABI5_SYMBOLS) and s not in UNVERSIONED_SYMBOLS:
                 getattr(L, s)
         _lib = L
     return _lib
@@ -388,6 +396,28 @@ class Solver:
         V = np.zeros((self.K, self.T, 2), dtype=np.float32)
         self._ck(self.L.mppi_get_applied_controls(self.h, _fp(V), V.size))
         return V
+
+    def trace_rollouts(self, ks, with_costs=True):
+        """mppi_trace_rollouts: the rollouts ks of the last solve replayed on the device.  dict(states [n, T, 7] before the
+        update of step t, controls [n, T, 2] after the clamp, first_crash [n]; with_costs: step_costs [n, T], costs [n]).
+        With a control cost on the cost outputs are refused (ERR_UNSUPPORTED): pass with_costs=False."""
+        ks = np.ascontiguousarray(ks, dtype=np.int32).reshape(-1)
+        n = ks.size
+        out = dict(states=np.zeros((n, self.T, 7), np.float32), controls=np.zeros((n, self.T, 2), np.float32),
+                   first_crash=np.zeros(n, np.int32))
+        if with_costs:
+            out.update(step_costs=np.zeros((n, self.T), np.float32), costs=np.zeros(n, np.float32))
+        ip = C.POINTER(C.c_int)
+        self._ck(self.L.mppi_trace_rollouts(self.h, ks.ctypes.data_as(ip), n, _fp(out["states"]), _fp(out["controls"]),
+                                            _fp(out["step_costs"]) if with_costs else None,
+                                            _fp(out["costs"]) if with_costs else None, out["first_crash"].ctypes.data_as(ip)))
+        return out
+
+    def top_rollouts(self, n):
+        """mppi_top_rollouts: indices of the n largest weights of the last solve, descending, ties to the lower index."""
+        ks = np.zeros(int(n), np.int32)
+        self._ck(self.L.mppi_top_rollouts(self.h, int(n), ks.ctypes.data_as(C.POINTER(C.c_int))))
+        return ks
 
     def rollout_only(self, state):
         costs = np.zeros(self.K, dtype=np.float32)

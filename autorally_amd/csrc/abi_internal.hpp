@@ -2,7 +2,7 @@
 // functions of one another.  mppi_abi.hip: handle life cycle, setters, getters; abi_forms.hip: which kernel form runs
 // (selection table, names); abi_pack.hip: weight images and generator tables; abi_solve.hip: the solve pipeline (noise,
 // rollout + tail launches, result polling, batched solves); abi_host.hip: the host-side halves of a tick (nominal replays,
-// DDP feedback gains, the helper thread).
+// DDP feedback gains, the helper thread); abi_trace.hip: chosen rollouts of the last solve replayed with their records.
 #pragma once
 // mppi_abi.hip -- host side of libmppi_hip.so: the C ABI of include/mppi_hip.h.
 //
@@ -148,6 +148,16 @@ struct mppi_handle {
   float *d_lds44pack = nullptr;  // any layer list with hidden widths <= 64: image of rollout_lds44.hip
   float *d_lds128pack = nullptr; // any layer list with hidden widths <= 128 whose image fits the LDS: image of rollout_lds128.hip
   size_t lds128_bytes = 0;       // ... and its size
+  float *d_tracepack = nullptr;  // network model: k-major image of rollout_trace.hip (every layer's W transposed)
+  // mppi_trace_rollouts: the records of one chunk of trace_chunk rollouts -- states [c][T][7], controls [c][T][2], step costs
+  // [c][T], costs [c], first_crash [c] (int) -- allocated with the handle (nothing is allocated or freed while armed); the
+  // chunk's rollout indices reach the kernel through host-mapped memory (h_trace_ks / d_trace_ks: no upload on the stream)
+  float *d_trace = nullptr;
+  int *h_trace_ks = nullptr, *d_trace_ks = nullptr;
+  int trace_chunk = 0;
+  float solve_state[7] = {0, 0, 0, 0, 0, 0, 0};  // the vehicle state of the most recent solve (what v_buf and d_costs belong to)
+  bool have_solve = false;     // solve_state, v_buf and d_costs belong together (cleared where a solve starts to repoint v_buf)
+  bool have_weights = false;   // ... and d_w too: a whole solve, not mppi_rollout_only
   bool valu_reg_ok = false;
   double *d_invt = nullptr;
   uint32_t *d_rng[2] = {nullptr, nullptr};
@@ -235,6 +245,7 @@ std::vector<float> pack_row64_weights(const std::vector<float> &theta, int NHID)
 std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
+std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
 int upload_rng_tables(mppi_handle *h);
 bool use_mfma(const mppi_handle *h);
@@ -282,6 +293,18 @@ int solve_ahead_disarm(mppi_handle *h);
 
 // where small follow-up work (upload of U, the slide kernel) goes: behind the handle's latest work, wherever it is
 inline hipStream_t work_stream(const mppi_handle *h) { return h->order_stream ? h->order_stream : h->stream; }
+
+// the vehicle state a solve (or mppi_rollout_only) runs from, kept for mppi_trace_rollouts
+// forget_solve_state where a solve starts to repoint v_buf, note_solve_state once it is enqueued: a solve whose launch failed
+// leaves nothing to trace instead of an old state beside a new buffer.
+inline void forget_solve_state(mppi_handle *h) { h->have_solve = h->have_weights = false; }
+inline void note_solve_state(mppi_handle *h, const float *state, bool with_weights)
+{
+  memcpy(h->solve_state, state, sizeof(h->solve_state));
+  h->have_solve = true;
+  h->have_weights = with_weights;
+}
+constexpr int kTraceChunk = 1024;  // rollouts per launch of mppi_trace_rollouts
 
 // abi_host.hip: the helper thread of the paired host work (mppi_set_host_threads)
 extern std::atomic<int> g_host_threads;

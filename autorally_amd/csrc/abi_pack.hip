@@ -349,4 +349,20 @@ int upload_rng_tables(mppi_handle *h)
   return MPPI_OK;
 }
 
+// Image of rollout_trace.hip: theta's own layout [W1|b1|W2|b2|...] with every W transposed to k-major [nin][nout], so that
+// the lanes of a wavefront (one neuron each) read contiguous floats for one k; biases as they are.
+std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mppi::NetDesc &net)
+{
+  std::vector<float> img(theta.size());
+  size_t off = 0;
+  for (int l = 0; l + 1 < net.n_layers; l++) {
+    const size_t nin = net.layers[l], nout = net.layers[l + 1];
+    for (size_t j = 0; j < nout; j++)
+      for (size_t k = 0; k < nin; k++) img[off + k * nout + j] = theta[off + j * nin + k];
+    for (size_t j = 0; j < nout; j++) img[off + nin * nout + j] = theta[off + nin * nout + j];
+    off += nin * nout + nout;
+  }
+  return img;
+}
+
 }  // namespace mppi_abi

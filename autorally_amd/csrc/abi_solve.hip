@@ -490,6 +490,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
   const bool explicit_noise = h->explicit_iters > 0;
   const size_t slot_sz = (size_t)K * T * 2;
   h->seq = next_seq(h);
+  forget_solve_state(h);
   for (int it = 0; it < iters; it++) {
     Events *ev = timed ? &h->ev[it] : nullptr;
     if (ev) HIPCHK(h, hipEventRecord(ev->e[0], h->stream));
@@ -552,6 +553,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
   }
   h->explicit_iters = 0;
   h->pending = true;
+  note_solve_state(h, state, true);
   h->pending_timed = timed;
   h->cap_valid = h->capture;
   h->cap_explicit = explicit_noise;
@@ -772,6 +774,7 @@ static int open_armed(mppi_handle *h, const float *state)
   h->armed = 0;
   h->arm_n = 0;
   h->seq = h->arm_seq;
+  note_solve_state(h, state, true);
   write_gate_payload(h, state);
   write_gate_word(h, h->seq);
   h->order_stream = h->arm_stream;
@@ -1040,6 +1043,7 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     if (rc == MPPI_OK) rc = upload_controls_if_dirty(h, S);
     if (rc) return poison(rc);
     h->seq = next_seq(h);
+    forget_solve_state(h);
   }
   for (int it = 0; it < iters; it++) {
     QuadBatchArgs qb;
@@ -1070,6 +1074,7 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
   for (int i = 0; i < n; i++) {
     hs[i]->explicit_iters = 0;
     hs[i]->pending = true;
+    note_solve_state(hs[i], states + (size_t)MPPI_STATE_DIM * i, true);
     hs[i]->pending_timed = false;
   }
 #ifdef MPPI_HOSTPROF
@@ -1204,12 +1209,14 @@ int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
     noise = h->d_gen[h->gen_cur];
   }
   h->explicit_iters = 0;
+  forget_solve_state(h);
   h->v_buf = noise;
   RolloutArgs a;
   fill_rollout_args(h, state, noise, a);
   if (inline_noise) use_inline_noise(h, a);
   rc = launch_rollout(h, a);
   if (rc) return rc;
+  note_solve_state(h, state, false);
   HIPCHK(h, hipMemcpyAsync(costs, h->d_costs, sizeof(float) * h->K, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MPPI_OK;

@@ -115,6 +115,30 @@ hipError_t launch_rollout_bf_batch(const QuadBatchArgs &b, hipStream_t stream);
 hipError_t launch_dynamics_bf(const float *W, const float *states, const float *controls, float *ders, int n,
                               hipStream_t stream);
 
+// rollout_trace.hip: chosen rollouts of a finished solve replayed with their records (mppi_trace_rollouts) -- one wavefront per
+// rollout and one lane per neuron for ANY layer list (every neuron the reference's chain: costs bit-identical to the exact
+// forms), one lane per rollout for the basis-function model
+struct TraceArgs {
+  float state[kStateDim];
+  const float *V;       // [T][K][2] the solve's applied controls, before the clamp
+  const int *ks;        // [n] rollout indices, each in [0, K)
+  const float *wimg;    // network: pack_trace_weights (abi_pack.hip); basis functions: W[4][25]
+  const double *inv_t;  // as RolloutArgs::inv_t
+  // outputs, slot i = rollout ks[i]; any may be nullptr
+  float *states;        // [n][T][7] the state before the update of step t
+  float *controls;      // [n][T][2] after the clamp
+  float *step_costs;    // [n][T]    computeCost of step t (0 at t = 0)
+  float *costs;         // [n]       the running mean
+  int *first_crash;     // [n]       the first step whose cost saw the crash flag, -1: never
+  int n, K, T;
+  float nu[2], u_lo[2], u_hi[2], dt;
+  int negate_yaw_der;
+  CostArgs cost;
+};
+bool trace_image_in_lds(const NetDesc &net);  // the k-major image and the waves' tiles fit the kernel's LDS budget
+hipError_t launch_rollout_trace(const NetDesc &net, const TraceArgs &a, hipStream_t stream);
+hipError_t launch_rollout_trace_bf(const TraceArgs &a, hipStream_t stream);
+
 // solve_kernels.hip
 // everything of one solve iteration after the rollout (solve_tail_kernel up to 4096 rollouts, solve_tail_stream_kernel beyond)
 struct TailLaunch {

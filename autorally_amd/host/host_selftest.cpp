@@ -1,5 +1,6 @@
-// host_selftest.cpp -- CPU-only checks of the host layer (no GPU; libmppi_hip is linked because the
-// controller classes' headers name its entry points, but no handle is ever created here):
+// host_selftest.cpp -- checks of the host layer that need no GPU (libmppi_hip is linked because the
+// controller classes' headers name its entry points; the one handle created here -- the sampled-trajectory calls at the
+// end -- is created only where a gfx950 device is present):
 //   npz reader against a numpy-written model file and a round trip of the writer,
 //   launch-XML loader against a launch file in the reference's format,
 //   the headless plant's feedback law, the live-pose half of runControlLoop with a scripted pose clock and a
@@ -294,6 +295,39 @@ int main(int argc, char **argv)
     const size_t mid = (size_t)c.width_ * (c.height_ / 2) + c.width_ / 3;
     printf("costmap4 sums=[%.9g %.9g %.9g %.9g] texel%zu=[%.9g %.9g %.9g %.9g]\n", cs[0], cs[1], cs[2], cs[3], mid,
            c.track_costs_[4 * mid], c.track_costs_[4 * mid + 1], c.track_costs_[4 * mid + 2], c.track_costs_[4 * mid + 3]);
+  }
+  // --- traceRollouts / getSampledTrajectories (mppi_trace_rollouts, mppi_top_rollouts): the C entries refuse a NULL handle
+  //     anywhere; where a gfx950 device is present (this program needs none) one small controller solves once and both are
+  //     called once ---
+  {
+    int k0 = 0;
+    REQUIRE(mppi_trace_rollouts(nullptr, &k0, 1, nullptr, nullptr, nullptr, nullptr, nullptr) == MPPI_ERR_INVALID);
+    REQUIRE(mppi_top_rollouts(nullptr, 1, &k0) == MPPI_ERR_INVALID);
+    if (argc > 4 && mppi_device_count() >= 1) {
+      const float2_ rng[2] = {{-0.99f, 0.99f}, {-0.99f, 0.65f}};
+      NeuralNetModel model({6, 32, 32, 4}, 0.02f, rng);
+      model.loadParams(argv[1]);
+      MPPICosts costs(1, 1);
+      costs.loadTrackData(argv[4]);
+      const float nu[2] = {0.275f, 0.3f}, init_u[2] = {0.0f, 0.0f};
+      const int K = 64, T = 10, n = 8;
+      MPPIController ctl(&model, &costs, nu, init_u, 50, T, 1, 0.15f, 1, K);
+      const float state[7] = {0.0f, 0.0f, 0.3f, 0.0f, 4.0f, 0.1f, 0.0f};
+      ctl.computeControl(state);
+      const MPPIController::RolloutTrace top = ctl.getSampledTrajectories(n);
+      REQUIRE(top.ks.size() == (size_t)n && top.weights.size() == (size_t)n && top.states.size() == (size_t)n * T * 7);
+      for (int i = 0; i + 1 < n; i++) REQUIRE(top.weights[i] >= top.weights[i + 1]);
+      const MPPIController::RolloutTrace tr = ctl.traceRollouts(top.ks);
+      REQUIRE(tr.costs.size() == (size_t)n && tr.step_costs.size() == (size_t)n * T && tr.first_crash.size() == (size_t)n);
+      REQUIRE(memcmp(tr.states.data(), top.states.data(), sizeof(float) * tr.states.size()) == 0);
+      for (int i = 0; i < n; i++) {
+        REQUIRE(memcmp(&tr.states[(size_t)i * T * 7], state, sizeof(state)) == 0 && tr.step_costs[(size_t)i * T] == 0.0f);
+        REQUIRE(top.ks[i] >= 0 && top.ks[i] < K && std::isfinite(tr.costs[i]));
+      }
+      printf("sampled trajectories: best rollout %d, weight %.6g, cost %.6g\n", top.ks[0], top.weights[0], tr.costs[0]);
+    } else {
+      printf("sampled trajectories: no gfx950 device, controller calls not run\n");
+    }
   }
   printf("host selftest OK (%zu params)\n", p.size());
   return 0;

@@ -722,6 +722,53 @@ class MPPIControllerT {
     ck(mppi_debug_cost_raster(h_, x, y, heading, width_m, height_m, ppm, img.data(), img.size()));
     return img;
   }
+  // Chosen rollouts of the last solve, replayed on the device (mppi_trace_rollouts): what a sampled rollout did, step by step.
+  // The cost fields stay empty where the library refuses them (MPPI_ERR_UNSUPPORTED: a control cost is on) or with_costs is false.
+  struct RolloutTrace {
+    std::vector<int> ks;            // [n] the rollout indices asked for
+    std::vector<float> weights;     // [n] their weights (getSampledTrajectories only)
+    std::vector<float> states;      // [n][T][7] the state before the update of step t
+    std::vector<float> controls;    // [n][T][2] after the clamp
+    std::vector<float> step_costs;  // [n][T]
+    std::vector<float> costs;       // [n]
+    std::vector<int> first_crash;   // [n] first step whose cost saw the crash flag, -1: never
+  };
+  RolloutTrace traceRollouts(const std::vector<int> &ks, bool with_costs = true)
+  {
+    RolloutTrace r;
+    const size_t n = ks.size(), T = (size_t)numTimesteps_;
+    r.ks = ks;
+    r.states.resize(n * T * STATE_DIM);
+    r.controls.resize(n * T * CONTROL_DIM);
+    r.first_crash.resize(n);
+    int rc = MPPI_ERR_UNSUPPORTED;
+    if (with_costs) {
+      r.step_costs.resize(n * T);
+      r.costs.resize(n);
+      rc = mppi_trace_rollouts(h_, ks.data(), (int)n, r.states.data(), r.controls.data(), r.step_costs.data(), r.costs.data(),
+                               r.first_crash.data());
+    }
+    if (rc == MPPI_ERR_UNSUPPORTED) {  // the library's own decision (a control cost, an unusable exploration_std): no cost fields
+      r.step_costs.clear();
+      r.costs.clear();
+      rc = mppi_trace_rollouts(h_, ks.data(), (int)n, r.states.data(), r.controls.data(), nullptr, nullptr, r.first_crash.data());
+    }
+    ck(rc);
+    return r;
+  }
+  // The n best-weighted samples of the last solve (mppi_top_rollouts, then the trace): indices, weights and state sequences --
+  // the usual companion of the nominal path on an MPPI display.
+  RolloutTrace getSampledTrajectories(int n)
+  {
+    std::vector<int> ks((size_t)n);
+    ck(mppi_top_rollouts(h_, n, ks.data()));
+    RolloutTrace r = traceRollouts(ks, false);
+    std::vector<float> w((size_t)NUM_ROLLOUTS);
+    ck(mppi_get_results(h_, nullptr, nullptr, nullptr, w.data()));
+    r.weights.resize((size_t)n);
+    for (int i = 0; i < n; i++) r.weights[(size_t)i] = w[(size_t)ks[(size_t)i]];
+    return r;
+  }
   std::vector<float> getControlSeq() { return control_solution_; }
   std::vector<float> getStateSeq() { return state_solution_; }
   float getComputedTrajectoryCost() { return trajectory_cost_; }

@@ -44,6 +44,8 @@ extern "C" {
  *    "lds44" share a launch in mppi_compute_control_batch / mppi_arm_batch: results unchanged. */
 /*    (still 5) + rollout variant "lds128", name "mfma4x4x1_lds2h_l<N>_w<W>": hidden widths up to 128; no new export, nothing
  *    else changes ("lds44" keeps refusing widths above 64). */
+/*    (still 5) + mppi_trace_rollouts, mppi_top_rollouts (chosen rollouts of the last solve replayed with their states, clamped
+ *    controls and step costs; compatible additions, no kernel form or launch path changes). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -229,6 +231,36 @@ int mppi_control_ticks_batch(mppi_handle *const *handles, const float *states, i
 int mppi_get_results(mppi_handle *h, float *U, float *traj_cost, float *costs, float *weights);
 /* The rewritten du_d buffer of the last iteration, [K][T][2] (applied, unclamped controls, Q3). */
 int mppi_get_applied_controls(mppi_handle *h, float *V, size_t n);
+/* The rollouts ks[0..n) of the most recent completed solve (last iteration), replayed on the device from that solve's
+ * vehicle state and its applied controls (the buffer mppi_get_applied_controls reads), with the handle's current model, cost
+ * parameters, costmap and control limits.  Any output may be NULL.
+ *   states      [n][T][7]  state BEFORE the update of step t (states[i][0] = the solve's state): what the cost of step t saw
+ *   controls    [n][T][2]  the controls after the clamp (what the dynamics saw)
+ *   step_costs  [n][T]     computeCost of step t (0 at t = 0, which is never costed, Q5)
+ *   costs       [n]        the running mean the rollout kernel stores in traj_costs_
+ *   first_crash [n]        the first step whose cost saw the crash flag set, -1: never
+ * Every neuron is summed in the reference's order: costs[i] is costs[ks[i]] of mppi_get_results bit for bit on every rollout
+ * form that keeps that order in every layer (not the forms that sum a layer as a butterfly -- "row_tree", "m44", "m44_chain",
+ * "multi4_tree", "row64" --, whose costs differ by their re-association only).  Valid wherever mppi_get_applied_controls is:
+ * a pending solve is waited for first; MPPI_ERR_HIP after a lost solve; mppi_slide_control_seq / mppi_set_control_seq
+ * afterwards change nothing it returns.  While armed the handle stays armed and the trace is enqueued on the generator stream
+ * in FRONT of the armed kernels, not behind them -- but its workgroups (four wavefronts of 160 / 192 VGPRs, up to 64 KB of LDS)
+ * still need room on the chip beside the gated kernels, which hold theirs until the gate opens: there is room on every CU
+ * beside an armed row launch; an armed "m44" / "lds44" / "lds128" launch fills the SIMDs of the CUs it occupies, and the trace
+ * runs on the CUs it left free (16 of 256 for the pair of K = 1920).  Where an armed launch occupies every CU the trace ends
+ * only once the gate opens or max_wait_s runs out: trace before arming there.
+ * Duplicate indices are allowed, n == 0 does nothing.  MPPI_ERR_STATE before the first solve (mppi_rollout_only counts: its
+ * state, controls and costs are what is traced) and after a solve whose launch failed; MPPI_ERR_INVALID for ks == NULL with
+ * n > 0, n < 0, an index outside [0, K).  With a control cost on (steering_coeff or throttle_coeff non-zero, or an
+ * exploration_std whose square is zero or not finite) du = eps nu cannot be had back from the applied controls bit for bit:
+ * step_costs != NULL or costs != NULL is then MPPI_ERR_UNSUPPORTED (reason in mppi_last_error); states, controls and
+ * first_crash are served.  (csrc/rollout_trace.hip: one wavefront per rollout, one lane per neuron.) */
+int mppi_trace_rollouts(mppi_handle *h, const int *ks, int n, float *states, float *controls,
+                        float *step_costs, float *costs, int *first_crash);
+/* ks[0..n) = indices of the n largest weights of the last solve, descending, ties to the lower index (host work);
+ * MPPI_ERR_INVALID for n < 0 or n > K or ks == NULL with n > 0, MPPI_ERR_STATE before the first solve (mppi_rollout_only
+ * computes no weights: it does not count). */
+int mppi_top_rollouts(mppi_handle *h, int n, int *ks);
 /* Stage-level entry: noise (or explicit noise) + rolloutKernel only; costs[K]. */
 int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *costs);
 /* computeNominalTraj (mppi_controller.cu:501-519), host replay of U_ like the reference:
