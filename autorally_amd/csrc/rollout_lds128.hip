@@ -133,6 +133,9 @@ __device__ __forceinline__ void lds128_dynamics(const RolloutArgs &a, const Lds1
   const m44_f4 w0a = pw0[0], w0b = two0 ? pw0[2 * 64] : pw0[64];
   const m44_f4 w0c = two0 ? pw0[64] : zero4, w0d = two0 ? pw0[3 * 64] : zero4;  // the second half's two quads
   const float bs0 = pb[0], bs0h = pb[1];
+  // a lane beyond the first hidden layer's width holds no neuron: its zero weights times an infinite state entry are NaN, which
+  // the next layer's padded k steps (zero weights again) would spread to every neuron; the reference multiplies real weights only
+  const bool pad0 = lane >= net.layers[1], pad0h = lane + 64 >= net.layers[1];
   const float bo = pb[((n_w - 1) >> 1) * 256 + (((n_w - 1) & 1) << 1)];
   const m44_f4 *const p1 = pw0 + (two0 ? 4 : 2) * 64;  // layer 1
 
@@ -200,7 +203,11 @@ __device__ __forceinline__ void lds128_dynamics(const RolloutArgs &a, const Lds1
     const int cp_v = *p_pub;
     un = p_u[sn];
     m44_tanh(d0, bs0, act0);
-    if (two) m44_tanh(d1, bs0h, act1);
+    if (pad0) act0[0] = act0[1] = act0[2] = act0[3] = 0.0f;
+    if (two) {
+      m44_tanh(d1, bs0h, act1);
+      if (pad0h) act1[0] = act1[1] = act1[2] = act1[3] = 0.0f;
+    }
     const m44_f4 *p = p1;
     for (int j = 1;; j++) {
       const int lay = (int)(lay_all >> (8 * j));

@@ -84,6 +84,9 @@ __device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44
   // layer 0 (6 inputs, two quads) and the first and the last bias stay in registers
   const m44_f4 w0a = pk[kLds44BiasQuads * 64], w0b = pk[(kLds44BiasQuads + 1) * 64];
   const float bs0 = pb[0];
+  // a lane beyond the first hidden layer's width holds no neuron: its zero weights times an infinite state entry are NaN, which
+  // the next layer's padded k steps (zero weights again) would spread to every neuron; the reference multiplies real weights only
+  const bool pad0 = lane >= net.layers[1];
   const float bo = pb[((n_w - 1) >> 2) * 256 + ((n_w - 1) & 3)];
   const m44_f4 *const p1 = pk + (kLds44BiasQuads + 2) * 64;  // layer 1
   // quads of layer l in bits 5 l .. 5 l + 4 of a scalar: the T loop reads no kernel argument
@@ -139,6 +142,7 @@ __device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44
     un = p_u[sn];
     float act[4], Tr[4];
     m44_tanh(d, bs0, act);
+    if (pad0) act[0] = act[1] = act[2] = act[3] = 0.0f;
     const m44_f4 *p = p1;
     for (int l = 1;; l++) {
       const int nq = (int)(nq_all >> (5 * l)) & 31;

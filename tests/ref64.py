@@ -29,11 +29,12 @@ def _np_basis(s, u):
         u1 ** 2, u1 ** 3])
 
 
-def basis_k(s, u):
-    """_np_basis over K rows at once: s [K, 7], u [K, 2] -> phi [K, 25] (the u_x > .1 switch per row)."""
+def basis_k(s, u, big=None):
+    """_np_basis over K rows at once: s [K, 7], u [K, 2] -> phi [K, 25] (the u_x > .1 switch per row; big: the switch, if
+    another one is to be stated)."""
     s3, s4, s5, s6 = s[:, 3], s[:, 4], s[:, 5], s[:, 6]
     u0, u1 = u[:, 0], u[:, 1]
-    big = s4 > .1
+    big = s4 > .1 if big is None else big
     with np.errstate(divide="ignore", invalid="ignore"):
         A = np.where(big, np.tan(np.arctan(s5 / s4 + .45 * s6 / s4) - u0), np.tan(-u0))
         B = np.where(big, s5 / s4 - .35 * s6 / s4, 0.0)
@@ -89,9 +90,15 @@ class Ref64:
         a = np.asarray(x, f64)
         for i, (W, b) in enumerate(zip(self.Ws, self.bs)):
             a = a @ W.T + b
+            if i == 0 and getattr(self, "pre_probe", None) is not None:   # the first layer's pre-activations, if asked for
+                self.pre_probe.append(a.copy())
             if i < len(self.Ws) - 1:
                 a = np.tanh(a)
         return a
+
+    def bf_big(self, ux):
+        """the basis functions' switch, car_bfs.cuh"""
+        return ux > .1
 
     def state_deriv(self, s, u):
         """computeKinematics (neural_net_model.cu:346-355, generalized_linear.cu:207-217) + the model's derivative of
@@ -102,7 +109,7 @@ class Ref64:
         sd[:, 1] = sn * s[:, 4] + c * s[:, 5]
         if self.bf_W is not None:
             sd[:, 2] = -s[:, 6]  # GeneralizedLinear negates the yaw rate always (generalized_linear.cu:216)
-            sd[:, 3:] = basis_k(s, u) @ self.bf_W.T
+            sd[:, 3:] = basis_k(s, u, self.bf_big(s[:, 4])) @ self.bf_W.T
         else:
             sd[:, 2] = -s[:, 6] if self.negate_yaw_der else s[:, 6]
             sd[:, 3:] = self.nn(np.concatenate([s[:, 3:7], u], axis=1))
@@ -123,14 +130,23 @@ class Ref64:
         """Point sampling of a normalised coordinate: the texel a continuous coordinate falls into."""
         return np.floor(g)
 
+    def clamp_index(self, f, n):
+        """The border clamp of one axis (cudaAddressModeClamp): a floored coordinate to a texel index 0 .. n-1; NaN -> 0."""
+        return np.clip(np.where(f >= 0, f, 0.0), 0, n - 1).astype(np.int64)
+
+    def clamp_sizes(self):
+        """(columns, rows) the clamp works with"""
+        H, W = self.map0.shape
+        return W, H
+
+    def fetch(self, fi, fj):
+        return self.map0[fj, fi]
+
     def texel(self, x, y):
         """Point-sampled, clamped, normalised-coordinate texture of channel 0 (PI/costs.cu:128-154)."""
         gi, gj = self.grid(x, y)
-        H, W = self.map0.shape
-        fi, fj = self.nearest(gi), self.nearest(gj)
-        fi = np.clip(np.where(fi >= 0, fi, 0.0), 0, W - 1).astype(np.int64)  # NaN -> 0 as the border clamp does
-        fj = np.clip(np.where(fj >= 0, fj, 0.0), 0, H - 1).astype(np.int64)
-        return self.map0[fj, fi]
+        W, H = self.clamp_sizes()
+        return self.fetch(self.clamp_index(self.nearest(gi), W), self.clamp_index(self.nearest(gj), H))
 
     # the cost's branches, one method each: the mutants of tests/test_branch_scenes.py override one of them
     def control_cost(self, u, du, v):
@@ -152,6 +168,18 @@ class Ref64:
         """getCrash, costs.cu:301-305"""
         return np.abs(s[:, 3]) > 1.57
 
+    def moving(self, ux):
+        """the guard of getStabilizingCost, costs.cu:340"""
+        return np.abs(ux) > 0.001
+
+    def cap(self, cost):
+        """costs.cu:404-407, on the step's cost"""
+        return np.where((cost > 1e12) | np.isnan(cost), 1e12, cost)
+
+    def accumulate(self, running, cost, t):
+        """the running mean of the rollout kernel, mppi_controller.cu:165"""
+        return running + (cost - running) / t
+
     def compute_cost(self, s, u, du, crash, v=None, out=None):
         """MPPICosts::computeCost (PI/costs.cu:396-409) and what it calls (:307-393): u clamped, du unclamped.  `crash` [N]
         (int) is updated in place by the boundary test.  out: a dict that receives the branch record of this step."""
@@ -167,15 +195,15 @@ class Ref64:
         err = s[:, 4] - P["desired_speed"]
         speed = P["speed_coeff"] * (np.abs(err) if P.get("l1_cost") else err * err)
         crash_cost = (1.0 - P["discount"]) * np.where(crash > 0, P["crash_coeff"], 0.0)
-        moving = np.abs(s[:, 4]) > 0.001
+        moving = self.moving(s[:, 4])
         with np.errstate(divide="ignore", invalid="ignore"):
             slip = -np.arctan(s[:, 5] / np.abs(s[:, 4]))
         over = self.slip_over(slip)
         stab = np.where(moving, P["slip_penalty"] * slip * slip + np.where(over, P["crash_coeff"], 0.0), 0.0)
         cost = control + speed + crash_cost + track + stab
         if out is not None:
-            out.update(tf=tf, tb=tb, zeroed=zeroed, slip=slip, over=over & moving)
-        return np.where((cost > 1e12) | np.isnan(cost), 1e12, cost)
+            out.update(tf=tf, tb=tb, zeroed=zeroed, slip=slip, over=over & moving, raw=cost)
+        return self.cap(cost)
 
     # ---------------------------------------------------------------- rollouts
     def controls(self, U, eps):
@@ -202,14 +230,28 @@ class Ref64:
         """The sticky flag after the state update: the cost of the NEXT step is the first to see it."""
         crash |= self.rolled(s).astype(crash.dtype)
 
+    @staticmethod
+    def edge_distance(g, n):
+        """Texels from a continuous grid coordinate to the nearest texel edge that IS a discontinuity of the clamped lookup:
+        the edges 1 .. n-1.  The edges 0 and n and everything beyond them are none -- the clamp reads the border texel on both
+        sides -- so a point outside the map along an axis is as far from that axis's edges as it is from the border texel's
+        inner edge, and only the edges of the other (tangential) axis count."""
+        fr = g - np.floor(g)
+        d = np.minimum(fr, 1.0 - fr)
+        return np.where(g < 1.0, 1.0 - g, np.where(g > n - 1.0, g - (n - 1.0), d))
+
     def trace(self, state, U, eps):
         """rollouts() with the record of every branch of the cost, over the steps that enter it (t = 1 .. T-1; arrays [K, T]
         hold +inf / False / 0 at t = 0):
           margins -- the distance to every discontinuity:
             m_texel  metres from the front or the back point to the nearest texel edge, along both axes of the projective grid
+                     (edge_distance: an edge outside the map along its normal is none)
             m_roll   | |roll| - 1.57 | of the state after update t-1, the one step t's flag is taken from ([K, T + 1]: the entry
                      T is the final update's, which no cost sees)
             m_slip   | |slip| - max_slip_ang |
+            m_ux     | |u_x| - 0.001 |, the guard of the stabilizing cost
+            m_bf     | u_x - 0.1 |, the basis functions' switch, of the state the dynamics of step t read (t = 0 included)
+            m_cap    | cost - 1e12 | / 1e12 of the step's cost before the cap
           events:
             first [K] the step whose cost is the first to see the crash flag (-1: never), source [K] what set it there
             (bits: 1 front point, 2 back point, 4 roll);
@@ -218,7 +260,12 @@ class Ref64:
             front, back [K, T] the point is on the boundary; zeroed [K, T] the track cost is zeroed by the slop;
             over [K, T] beyond the slip limit;
             clamp [K, T, 2] -1 / +1 where a control is cut at its lower / upper limit (t = 0 included: the dynamics see it);
-            min_ux [K] the smallest u_x of the rollout."""
+            min_ux [K] the smallest u_x of the rollout;
+            slow [K, T] |u_x| <= 0.001: the stabilizing cost is switched off; reversed [K, T] u_x < 0;
+            fast [K, T] u_x > .1 in the state the dynamics of step t read (t = 0 included);
+            capped [K, T] the step's cost is replaced by 1e12;
+            out_w, out_e, out_s, out_n [K, T] the front or the back point is beyond the map's column 0 / last column / row 0 /
+            last row; out_sw, out_ne [K, T] one point is beyond two borders at once; inside [K, T] both points on the map."""
         K, T = self.K, self.T
         V, du = self.controls(U, eps)
         s = np.tile(np.asarray(state, np.float32).astype(f64).reshape(1, 7), (K, 1))
@@ -228,27 +275,42 @@ class Ref64:
         my = 1.0 / (H * np.hypot(self.r_c1[1], self.r_c2[1]))
         crash = np.zeros(K, np.int64)
         running = np.zeros(K, f64)
+        flags = ("front", "back", "zeroed", "over", "slow", "reversed", "capped", "out_w", "out_e", "out_s", "out_n", "out_sw",
+                 "out_ne", "inside", "fast")
         rec = dict(m_texel=np.full((K, T), np.inf), m_roll=np.full((K, T + 1), np.inf), m_slip=np.full((K, T), np.inf),
-                   front=np.zeros((K, T), bool), back=np.zeros((K, T), bool), zeroed=np.zeros((K, T), bool),
-                   over=np.zeros((K, T), bool), clamp=np.zeros((K, T, 2), np.int8), first=np.full(K, -1), source=np.zeros(K, np.int64),
+                   m_ux=np.full((K, T), np.inf), m_bf=np.full((K, T), np.inf), m_cap=np.full((K, T), np.inf),
+                   clamp=np.zeros((K, T, 2), np.int8), first=np.full(K, -1), source=np.zeros(K, np.int64),
                    roll_first=np.full(K, -1), min_ux=np.full(K, np.inf), roll_over=np.zeros((K, T + 1), bool))
+        rec.update({f: np.zeros((K, T), bool) for f in flags})
         roll_flag = np.zeros(K, bool)
         for t in range(T):
             u = np.clip(V[:, t], self.u_lo, self.u_hi)
             rec["clamp"][:, t] = (V[:, t] > self.u_hi).astype(np.int8) - (V[:, t] < self.u_lo).astype(np.int8)
             rec["min_ux"] = np.minimum(rec["min_ux"], s[:, 4])
+            if self.bf_W is not None:
+                rec["m_bf"][:, t] = np.abs(s[:, 4] - .1)
+            rec["fast"][:, t] = s[:, 4] > .1
             if t > 0:
                 before = crash > 0
                 out = {}
-                running += (self.compute_cost(s, u, du[:, t], crash, V[:, t], out) - running) / t
+                running = self.accumulate(running, self.compute_cost(s, u, du[:, t], crash, V[:, t], out), t)
                 c, sn = np.cos(s[:, 2]), np.sin(s[:, 2])
                 d = []
+                inside = np.ones(K, bool)
                 for sg in (0.5, -0.5):
                     gi, gj = self.grid(s[:, 0] + sg * c, s[:, 1] + sg * sn)
-                    fi, fj = gi - np.floor(gi), gj - np.floor(gj)
-                    d += [np.minimum(fi, 1.0 - fi) * mx, np.minimum(fj, 1.0 - fj) * my]
+                    d += [self.edge_distance(gi, W) * mx, self.edge_distance(gj, H) * my]
+                    w_, e_, s_, n_ = gi < 0, gi >= W, gj < 0, gj >= H
+                    for f, v in (("out_w", w_), ("out_e", e_), ("out_s", s_), ("out_n", n_), ("out_sw", w_ & s_), ("out_ne", e_ & n_)):
+                        rec[f][:, t] |= v
+                    inside &= ~(w_ | e_ | s_ | n_)
+                rec["inside"][:, t] = inside
                 rec["m_texel"][:, t] = np.min(d, axis=0)
                 rec["m_slip"][:, t] = np.abs(np.abs(out["slip"]) - self.cost["max_slip_ang"])
+                rec["m_ux"][:, t] = np.abs(np.abs(s[:, 4]) - 0.001)
+                rec["m_cap"][:, t] = np.abs(out["raw"] - 1e12) / 1e12
+                rec["slow"][:, t], rec["reversed"][:, t] = np.abs(s[:, 4]) <= 0.001, s[:, 4] < 0
+                rec["capped"][:, t] = (out["raw"] > 1e12) | np.isnan(out["raw"])
                 rec["front"][:, t] = out["tf"] >= self.cost["boundary_threshold"]
                 rec["back"][:, t] = out["tb"] >= self.cost["boundary_threshold"]
                 rec["zeroed"][:, t], rec["over"][:, t] = out["zeroed"], out["over"]
