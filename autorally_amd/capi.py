@@ -317,6 +317,11 @@ class Solver:
         self._ck(self.L.mppi_generate_noise(self.h, _fp(e), e.size))
         return e
 
+    def set_nn_params(self, theta):
+        """mppi_set_nn_params: the packed [W1|b1|W2|b2|..] of the handle's layer list, live."""
+        theta = _f32(theta)
+        self._ck(self.L.mppi_set_nn_params(self.h, _fp(theta), theta.size))
+
     def update_model(self, description, data):
         d = (C.c_int * len(description))(*[int(x) for x in description])
         data = _f32(data)

@@ -83,6 +83,7 @@ Form form_of(const mppi_handle *h)
   }
   if (h->forced == Form::Lds44) return Form::Lds44;  // by name only, for every layer list it serves (the standard shapes too)
   if (h->forced == Form::Lds128) return Form::Lds128;  // by name only, as lds44
+  if (h->forced == Form::Lds16) return Form::Lds16;    // by name only, as lds44
   if (!use_mfma(h)) return use_valu_reg(h) ? Form::ValuReg : Form::ValuLds;
   if (h->forced != Form::Auto) return h->forced;
   const int groups = h->K / kRolloutsPerWave, cus = h->num_simds / 4;
@@ -162,6 +163,12 @@ const char *mppi_rollout_variant(const mppi_handle *h)
       snprintf(buf, sizeof(buf), "mfma4x4x1_lds2h_l%d_w%d", h->net.n_layers - 2, wmax);
       break;
     }
+    case Form::Lds16: {
+      int wmax = 0;  // the widest hidden layer
+      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
+      snprintf(buf, sizeof(buf), "mfma16x16x4_lds_l%d_w%d", h->net.n_layers - 2, wmax);
+      break;
+    }
     case Form::Oct: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_oct8w%s", h->hidden, h->n_hidden, gen); break;
     case Form::Quad: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_quad4w", h->hidden, h->n_hidden); break;
     case Form::Fused256: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_fused_b256", h->hidden, h->n_hidden); break;
@@ -216,6 +223,19 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
     }
     if ((rc = need(h->d_lds128pack != nullptr, "lds128 form: this handle has no image"))) return rc;
     h->forced = Form::Lds128;
+  }
+  else if (strcmp(name, "lds16") == 0) {  // the throughput form of any layer list up to 128 wide whose image fits one workgroup's LDS
+    if ((rc = need(!h->basis, "lds16 is a form of the network model"))) return rc;
+    const size_t bytes = lds16_lds_bytes(h->net);
+    if ((rc = need(bytes != 0, "lds16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer"))) return rc;
+    if (bytes > lds16_lds_limit()) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "lds16 form: the weights of this layer list need %zu bytes of LDS per workgroup, %zu are available",
+               bytes, lds16_lds_limit());
+      return fail(h, MPPI_ERR_UNSUPPORTED, msg);
+    }
+    if ((rc = need(h->d_lds16pack != nullptr, "lds16 form: this handle has no image"))) return rc;
+    h->forced = Form::Lds16;
   }
   else if (strcmp(name, "row64") == 0 || strcmp(name, "row64_r16") == 0) {  // the vector-ALU arm of the 64-wide A/B
     if ((rc = need(h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden), "row64 form exists for 6-64x2-4 and 6-64x4-4"))) return rc;

@@ -53,6 +53,8 @@ enum class Form : int {
                                     // layer one chain in the reference's order; by name only ("lds44")
   Lds128,                           // rollout_lds128.hip: any layer list up to 128 wide, a layer as two halves of 64 neurons with an
                                     // accumulator each, the reference's order; by name only ("lds128")
+  Lds16,                            // rollout_lds16.hip: the throughput form of any layer list up to 128 wide: one wave per 16 rollouts on
+                                    // v_mfma_f32_16x16x4, the A operands from an LDS image, the reference's order; by name only ("lds16")
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
 };
@@ -148,6 +150,8 @@ struct mppi_handle {
   float *d_lds44pack = nullptr;  // any layer list with hidden widths <= 64: image of rollout_lds44.hip
   float *d_lds128pack = nullptr; // any layer list with hidden widths <= 128 whose image fits the LDS: image of rollout_lds128.hip
   size_t lds128_bytes = 0;       // ... and its size
+  float *d_lds16pack = nullptr;  // the same lists: image of rollout_lds16.hip
+  size_t lds16_bytes = 0;        // ... and its size
   float *d_tracepack = nullptr;  // network model: k-major image of rollout_trace.hip (every layer's W transposed)
   // mppi_trace_rollouts: the records of one chunk of trace_chunk rollouts -- states [c][T][7], controls [c][T][2], step costs
   // [c][T], costs [c], first_crash [c] (int) -- allocated with the handle (nothing is allocated or freed while armed); the
@@ -245,6 +249,7 @@ std::vector<float> pack_row64_weights(const std::vector<float> &theta, int NHID)
 std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
+std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
 int upload_rng_tables(mppi_handle *h);

@@ -292,6 +292,63 @@ std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const Ne
   return out;
 }
 
+// Image of the 16x16x4 LDS form (rollout_lds16.hip), any layer list with hidden widths <= 128, in float4 ("quads"); lane l =
+// (row = l & 15, kk = l >> 4), the neuron of row `row` of tile m is n = 16 m + 4 (row & 3) + (row >> 2) (the output layer: row & 3).
+//   biases   weight layer j at quad boff[j]: hidden layers 4 MT_j quads, quad 4 m + g = kTanhScale x (b[16 m + g], b[16 m + 4 + g],
+//            b[16 m + 8 + g], b[16 m + 12 + g]); the output layer ONE quad b_out[0..3]
+//   layer 0  at quad off[0]: MT_0 half blocks of 32 quads, float2 l of half block m = (W[n][kk], W[n][4 + kk]), 0 for k >= 6
+//   layer j  at quad off[j]: blocks of 64 quads, quad l of block (m, mi) = (W[n][16 mi + kk], W[n][16 mi + 4 + kk], W[n][16 mi + 8 + kk],
+//            W[n][16 mi + 12 + kk]) -- k-steps 4 mi .. 4 mi + 3 of tile m -- in the order of their use: block index 2 (P MT_in + mi) + h
+//            for tile m = 2 P + h of a pair, and (MT_j - 1) MT_in + mi for an odd last tile (MT_in = MT_(j-1) input tiles)
+//   then kLds16Ahead = 2 blocks the kernel's read-ahead may touch.
+// Every entry without a weight (a neuron or an input that does not exist) is 0.
+std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  std::vector<float> out((size_t)lds16_pack_floats(net), 0.0f);
+  if (out.empty()) return out;
+  const Lds16Net d = lds16_net_of(net);
+  const float *p = theta.data();
+  for (int j = 0; j < d.n_w; j++) {
+    const int nin = net.layers[j], nout = net.layers[j + 1];
+    const float *W = p, *B = p + (size_t)nout * nin;
+    const bool last = j == d.n_w - 1;
+    float *bq = out.data() + 4 * (size_t)d.boff[j];
+    if (last) {
+      for (int r = 0; r < 4; r++) bq[r] = B[r];
+    } else {
+      for (int m = 0; m < d.mt[j]; m++)
+        for (int g = 0; g < 4; g++)
+          for (int r = 0; r < 4; r++) {
+            const int n = 16 * m + 4 * r + g;
+            if (n < nout) bq[(4 * m + g) * 4 + r] = B[n] * kTanhScale;
+          }
+    }
+    float *wq = out.data() + 4 * (size_t)d.off[j];
+    const int mt_in = j == 0 ? 1 : d.mt[j - 1];
+    for (int m = 0; m < d.mt[j]; m++)
+      for (int l = 0; l < 64; l++) {
+        const int row = l & 15, kk = l >> 4;
+        const int n = last ? (row & 3) : 16 * m + 4 * (row & 3) + (row >> 2);
+        if (n >= nout) continue;
+        if (j == 0) {
+          for (int c = 0; c < 2; c++)
+            if (4 * c + kk < nin) wq[((size_t)m * 64 + l) * 2 + c] = W[(size_t)n * nin + 4 * c + kk];
+          continue;
+        }
+        for (int mi = 0; mi < mt_in; mi++) {
+          const bool odd_tail = (d.mt[j] & 1) && m == d.mt[j] - 1;
+          const size_t block = odd_tail ? (size_t)m * mt_in + mi : 2 * ((size_t)(m >> 1) * mt_in + mi) + (m & 1);
+          for (int c = 0; c < 4; c++) {
+            const int kap = 16 * mi + 4 * c + kk;
+            if (kap < nin) wq[(block * 64 + l) * 4 + c] = W[(size_t)n * nin + kap];
+          }
+        }
+      }
+    p += (size_t)nout * nin + nout;
+  }
+  return out;
+}
+
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)
 {
   // base state: L'Ecuyer's default 12345 x 6, scrambled by the seed (DESIGN.md noise spec)

@@ -108,6 +108,28 @@ hipError_t launch_rollout_lds128(const NetDesc &net, const RolloutArgs &a, hipSt
 // two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
 hipError_t launch_rollout_lds128_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
 
+// rollout_lds16.hip: the THROUGHPUT form for ANY layer list 6 -> hidden widths 1..128 -> 4 whose image fits one workgroup's LDS:
+// rollout_mfma_kernel's wave (16 rollouts, the whole step, v_mfma_f32_16x16x4_f32, eps from the stand-alone generator) with the
+// layer list a kernel argument and the A operands read from an LDS image, every layer in the reference's order (bit-identical
+// to the other exact forms); a.wpack = pack_lds16_weights (abi_pack.hip)
+struct Lds16Net {
+  int n_w;      // weight layers; the last one is the output layer
+  int img_f4;   // float4 of the whole image
+  int mt[7];    // weight layer j: its M tiles, ceil(outputs / 16) (1 for the output layer)
+  int ks[7];    // its k-steps: 2 for layer 0 (6 inputs padded to 8), else 4 x mt[j - 1]
+  int off[7];   // float4 index of its A operands in the image
+  int boff[7];  // float4 index of its biases
+  int nout[7];  // its outputs
+};
+Lds16Net lds16_net_of(const NetDesc &net);    // of a list lds16_lds_bytes(net) != 0
+bool lds16_supported(const NetDesc &net);
+int lds16_pack_floats(const NetDesc &net);
+size_t lds16_lds_bytes(const NetDesc &net);   // a workgroup's dynamic LDS = the image of a list 6 -> 1..128 -> 4 (0 for any other list)
+size_t lds16_lds_limit();                     // the dynamic LDS a workgroup may have
+// threads per workgroup for K rollouts on a device of `cus` CUs: the smallest of 256 / 512 / 1024 with every workgroup resident at once
+int lds16_block_threads(const NetDesc &net, int K, int cus);
+hipError_t launch_rollout_lds16(const NetDesc &net, const RolloutArgs &a, int cus, hipStream_t stream);  // cus: the device's CUs (the handle's)
+
 // rollout_bf.hip (GeneralizedLinear basis-function dynamics, W[4][25] in a.wpack)
 hipError_t launch_rollout_bf(const RolloutArgs &a, int waves, hipStream_t stream);  // waves per 64 rollouts: 1, 2, 3
 // several instances of the three-wave form in one launch (grid: groups of 64 rollouts x instances)

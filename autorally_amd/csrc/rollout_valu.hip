@@ -6,6 +6,9 @@
 // from global memory on every use, Q1); activations ping-pong through a lane-major LDS tile
 // act[i][lane] (bank = lane, conflict free), weights are LDS broadcasts.  This is the fallback
 // for shapes the MFMA kernel does not cover and the "vector-ALU" arm of the SURVEY cfg-4 A/B.
+// A blob that does not fit the LDS beside the two tiles (6-128-128-128-4: 135 KB + 64 KB) stays in
+// global memory and is read from there on every use, as in the reference (THETA_LDS = false): the
+// same arithmetic in the same order, so the same bits, for every list whose tiles alone fit.
 #include "mppi_kernels.hpp"
 
 namespace mppi {
@@ -47,15 +50,18 @@ __device__ __forceinline__ void nn_forward_valu(const NetDev &net, const float *
   for (int i = 0; i < kNetOut; i++) d[i] = cur[i * kValuLanes + lane];
 }
 
+template <bool THETA_LDS>
 __global__ __launch_bounds__(kValuLanes) void rollout_valu_kernel(const RolloutArgs a, const NetDev net)
 {
   extern __shared__ float lds[];
-  float *theta_s = lds;
-  float *act0 = lds + ((net.num_params + 3) & ~3);
+  float *stage = lds;
+  float *act0 = lds + (THETA_LDS ? ((net.num_params + 3) & ~3) : 0);
   float *act1 = act0 + net.max_width * kValuLanes;
   const int lane = threadIdx.x;
-  for (int i = lane; i < net.num_params; i += kValuLanes) theta_s[i] = a.wpack[i];
+  if constexpr (THETA_LDS)
+    for (int i = lane; i < net.num_params; i += kValuLanes) stage[i] = a.wpack[i];
   __syncthreads();
+  const float *theta_s = THETA_LDS ? stage : a.wpack;
   const int k = blockIdx.x * kValuLanes + lane;
   if (k >= a.K) return;  // K % 64 == 0: never splits a wave
 
@@ -310,13 +316,18 @@ size_t valu_lds_bytes(const NetDesc &net)
 
 hipError_t launch_rollout_valu(const NetDesc &net, const RolloutArgs &a, hipStream_t stream)
 {
-  const size_t lds = valu_lds_bytes(net);
+  size_t lds = valu_lds_bytes(net);
+  const bool theta_lds = lds <= 160 * 1024;
+  if (!theta_lds) lds = 2 * (size_t)net.max_width * kValuLanes * sizeof(float);  // the two tiles; the blob stays in global memory
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rollout_valu_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const void *kern = theta_lds ? reinterpret_cast<const void *>(rollout_valu_kernel<true>)
+                               : reinterpret_cast<const void *>(rollout_valu_kernel<false>);
+  hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  MPPI_LAUNCH_ROLLOUT(rollout_valu_kernel, dim3(a.K / kValuLanes), dim3(kValuLanes), lds, stream, a,
-                     to_dev(net));
+  if (theta_lds)
+    MPPI_LAUNCH_ROLLOUT(rollout_valu_kernel<true>, dim3(a.K / kValuLanes), dim3(kValuLanes), lds, stream, a, to_dev(net));
+  else
+    MPPI_LAUNCH_ROLLOUT(rollout_valu_kernel<false>, dim3(a.K / kValuLanes), dim3(kValuLanes), lds, stream, a, to_dev(net));
   return hipGetLastError();
 }
 

@@ -46,6 +46,8 @@ extern "C" {
  *    else changes ("lds44" keeps refusing widths above 64). */
 /*    (still 5) + mppi_trace_rollouts, mppi_top_rollouts (chosen rollouts of the last solve replayed with their states, clamped
  *    controls and step costs; compatible additions, no kernel form or launch path changes). */
+/*    (still 5) + rollout variant "lds16", name "mfma16x16x4_lds_l<N>_w<W>": the throughput form of any layer list up to 128 wide;
+ *    no new export.  "valu_lds" reads a parameter blob that does not fit the LDS from global memory instead of failing at its launch. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -343,6 +345,12 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     by name only; gated form as "lds44"; lists up to 64 wide are accepted and give "lds44"'s bits, but belong to "lds44";
  *     MPPI_ERR_UNSUPPORTED for the basis-function model, a hidden width above 128, a list without a hidden layer, or an
  *     image that does not fit (the message states needed and available bytes)
+ *     "lds16" mfma16x16x4_lds_l<hidden layers>_w<widest hidden layer>: the THROUGHPUT form of the same lists (hidden widths 1..128) --
+ *     "fused"'s wavefront (16 rollouts, the whole step, v_mfma_f32_16x16x4, eps from the stand-alone generator kernel) with the
+ *     layer list a kernel argument and the weights read from an LDS image per workgroup (6-128-128-128-4: 144 KB, fits; a fourth
+ *     128-wide layer does not); workgroups of 256 / 512 / 1024 threads, the smallest with every workgroup resident at once; by
+ *     name only; NO gated form (mppi_arm answers MPPI_ERR_UNSUPPORTED) and no batched launch (a batch solves handle by handle);
+ *     MPPI_ERR_UNSUPPORTED as "lds128"
  *   A/B arms and cross-checks (never chosen automatically)
  *     "valu" valu_reg_lds (lane = rollout, the independent implementation every parity test also runs; config 4's untuned
  *     vector-ALU reference), "valu_lds" (the generic kernel on a standard shape), "row64" = "row64_r16"
