@@ -1,5 +1,5 @@
-// m44_core.hpp -- what the forms on v_mfma_f32_4x4x1 with A-matrix broadcast share (rollout_m44.hip: weights in registers;
-// rollout_lds44.hip: weights in LDS, any layer list): the accumulator type, the 4 x 4 transpose inside a quad that turns a
+// m44_core.hpp -- the arithmetic the forms on v_mfma_f32_4x4x1 with A-matrix broadcast share (rollout_m44.hip: weights in
+// registers; rollout_lds44.hip, rollout_lds128.hip: weights in LDS, any layer list; their group is m44_group.hpp): the accumulator type, the 4 x 4 transpose inside a quad that turns a
 // layer's D (VGPR r = rollout r, lane n = neuron n) into the next layer's A (lane-in-quad = rollout, VGPR = neuron-in-quad),
 // and the packed tanh of a D.
 #pragma once

@@ -397,6 +397,9 @@ __device__ __forceinline__ int lds_peek(uint32_t addr)
   asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(addr) : "memory");
   return __builtin_amdgcn_readfirstlane(v);
 }
+// A read-ahead from LDS is requested HERE: without this the compiler moves a request behind the wave-uniform exit in front of
+// its use and waits for every read (no instruction, no wait: a compiler barrier for memory operations only)
+__device__ __forceinline__ void lds_pin_reads() { asm volatile("" ::: "memory"); }
 // The layer-0 B operand of k-step 0, [s3, s4, s5, s6][g] (g = lane >> 4), as a select tree of depth 2 (three
 // v_cndmask on lane-constant conditions; the ternary CHAIN on g is one level deeper on the T-step chain).
 __device__ __forceinline__ float row_sel(int g, float s3, float s4, float s5, float s6)

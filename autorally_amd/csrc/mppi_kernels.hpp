@@ -3,6 +3,7 @@
 #include "mppi_device.hpp"
 
 #include <hip/hip_ext.h>
+#include <type_traits>
 
 namespace mppi {
 
@@ -20,6 +21,58 @@ extern thread_local hipEvent_t tl_kernel_start, tl_kernel_stop;
     else                                                                                                           \
       hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);                                             \
   } while (0)
+
+// The launchers' run-time flags as compile-time ones: f(std::bool_constant<AFFINE>, std::bool_constant<CTRL>) -- and
+// std::bool_constant<GATED> for the forms that have a gated kernel -- launches that instance and returns its hipError_t.
+template <class F>
+inline hipError_t dispatch_cost_flags(bool affine, bool ctrl, F &&f)
+{
+  if (affine && !ctrl) return f(std::true_type{}, std::false_type{});
+  if (affine && ctrl) return f(std::true_type{}, std::true_type{});
+  if (!affine && !ctrl) return f(std::false_type{}, std::false_type{});
+  return f(std::false_type{}, std::true_type{});
+}
+template <class F>
+inline hipError_t dispatch_rollout_flags(bool affine, bool ctrl, bool gated, F &&f)
+{
+  if (gated) return dispatch_cost_flags(affine, ctrl, [&](auto af, auto ct) { return f(af, ct, std::true_type{}); });
+  return dispatch_cost_flags(affine, ctrl, [&](auto af, auto ct) { return f(af, ct, std::false_type{}); });
+}
+
+// More dynamic LDS than the default limit for kernel instance KERN: set once per instance and device.
+template <auto KERN>
+inline hipError_t raise_lds_limit_once(size_t bytes)
+{
+  static bool attr_set[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  if (!attr_set[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+    attr_set[dev] = true;
+  }
+  return hipSuccess;
+}
+
+// What one launch for the instances of a batch needs: the cost flags that serve all of them (the general forms are exact
+// supersets, rollout_mfma.hip), gated (mppi_arm_batch: every instance gated on its own block, or none) and the groups of the
+// largest instance.  False for a mixed gated / ungated batch or a K that is no whole number of groups.
+struct BatchFlags {
+  bool affine = true, ctrl = false, gated = false;
+  int gmax = 0;
+};
+inline bool batch_flags_of(const QuadBatchArgs &b, BatchFlags &f)
+{
+  f = BatchFlags{};
+  f.gated = b.inst[0].gate != nullptr;
+  for (int i = 0; i < b.n; i++) {
+    if ((b.inst[i].gate != nullptr) != f.gated || b.inst[i].K % kRolloutsPerWave != 0) return false;
+    f.affine = f.affine && b.inst[i].cost.affine != 0;
+    f.ctrl = f.ctrl || b.inst[i].cost.need_control_cost != 0;
+    f.gmax = b.inst[i].K / kRolloutsPerWave > f.gmax ? b.inst[i].K / kRolloutsPerWave : f.gmax;
+  }
+  return true;
+}
 
 // rollout_mfma.hip
 bool mfma_variant_supported(int hidden, int n_hidden);
@@ -61,7 +114,8 @@ hipError_t launch_rollout_row64(int hidden, int n_hidden, const RolloutArgs &a, 
 // rollouts each, all hidden weights in registers) + pose, cost, control and noise wave per 16 rollouts; output layer as a
 // butterfly, hidden layers (split) as two accumulation chains -- NOT the reference's summation order, and the AUTOMATIC form
 // for 64-wide nets up to 8192 rollouts ("m44_chain": hidden layers in the reference's order; "mfma": every layer);
-// a.wpack = pack_m44_weights (mppi_abi.hip)
+// a.wpack = pack_m44_weights (mppi_abi.hip).  The group -- shared state, the dynamics wave's hand-overs with the riders, the
+// group body -- is m44_group.hpp's, shared with rollout_lds44.hip and rollout_lds128.hip
 bool m44_variant_supported(int hidden, int n_hidden);
 int m44_pack_floats(int n_hidden);
 hipError_t launch_rollout_m44(int hidden, int n_hidden, const RolloutArgs &a, bool split, hipStream_t stream);  // split: two chains per hidden layer
@@ -75,6 +129,15 @@ struct NetDesc {
   int max_width;
   int num_params;
 };
+// a list 6 -> hidden widths 1..max_width -> 4 with at least one hidden layer: what the forms with the layer list as a kernel
+// argument take (lds44, lds128, lds16)
+inline bool lds_list_ok(const NetDesc &net, int max_width)
+{
+  if (net.n_layers < 3 || net.n_layers > 8 || net.layers[0] != kNetIn || net.layers[net.n_layers - 1] != kNetOut) return false;
+  for (int l = 1; l + 1 < net.n_layers; l++)
+    if (net.layers[l] < 1 || net.layers[l] > max_width) return false;
+  return true;
+}
 size_t valu_lds_bytes(const NetDesc &net);
 hipError_t launch_rollout_valu(const NetDesc &net, const RolloutArgs &a, hipStream_t stream);
 // register/scalar-operand vector-ALU kernel for 6 -> H x NHID -> 4 (theta with pre-scaled hidden biases)
@@ -84,7 +147,7 @@ hipError_t launch_dynamics_valu(const NetDesc &net, const float *theta, const fl
                                 const float *controls, float *ders, int n, int negate_yaw_der,
                                 hipStream_t stream);
 
-// rollout_lds44.hip: the m44 group (four dynamics waves x four rollouts on v_mfma_f32_4x4x1 with A-matrix broadcast + the four
+// rollout_lds44.hip: the m44 group (m44_group.hpp: four dynamics waves x four rollouts on v_mfma_f32_4x4x1 with A-matrix broadcast + the four
 // riders per 16 rollouts) for ANY layer list 6 -> hidden widths 1..64 -> 4: the layer list is a kernel argument, the weights of
 // all layers are read from LDS, every layer -- the output layer too -- is one k-ascending chain (the reference's order:
 // bit-identical to the other exact forms); a.wpack = pack_lds44_weights (abi_pack.hip)
@@ -96,7 +159,7 @@ hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStr
 // two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
 hipError_t launch_rollout_lds44_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
 
-// rollout_lds128.hip: the lds44 group for ANY layer list 6 -> hidden widths 1..128 -> 4 whose image fits one workgroup's LDS:
+// rollout_lds128.hip: the lds44 group (m44_group.hpp) for ANY layer list 6 -> hidden widths 1..128 -> 4 whose image fits one workgroup's LDS:
 // a hidden layer is one or two halves of 64 neurons with an accumulator each, its inputs one or two transposed activation
 // sets walked k ascending (the reference's order: bit-identical to the other exact forms); a.wpack = pack_lds128_weights
 constexpr int kLds128BiasQuads = 4;  // float4 per lane in front of the weights: float 2 j + h = bias of half h of weight layer j

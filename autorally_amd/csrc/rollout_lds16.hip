@@ -37,15 +37,7 @@ constexpr int kLds16Ahead = 2;                 // blocks requested ahead of thei
 constexpr int kLds16WavesPerSimd4 = 4, kLds16WavesPerSimd8 = 3;
 constexpr int kLds16MaxThreads8 = 512;         // the largest workgroup of the 8-tile instance
 
-static bool lds16_list_ok(const NetDesc &net)
-{
-  if (net.n_layers < 3 || net.n_layers > 8 || net.layers[0] != kNetIn || net.layers[net.n_layers - 1] != kNetOut) return false;
-  for (int l = 1; l + 1 < net.n_layers; l++)
-    if (net.layers[l] < 1 || net.layers[l] > 128) return false;
-  return true;
-}
-
-// offsets and counts of a list lds16_list_ok accepts
+// offsets and counts of a list lds_list_ok(net, 128) accepts
 Lds16Net lds16_net_of(const NetDesc &net)
 {
   Lds16Net d{};
@@ -67,11 +59,11 @@ Lds16Net lds16_net_of(const NetDesc &net)
   return d;
 }
 
-int lds16_pack_floats(const NetDesc &net) { return lds16_list_ok(net) ? 4 * lds16_net_of(net).img_f4 : 0; }
+int lds16_pack_floats(const NetDesc &net) { return lds_list_ok(net, 128) ? 4 * lds16_net_of(net).img_f4 : 0; }
 // a workgroup's dynamic LDS: the image and nothing else; 0 for a list the form does not take whatever its size
 size_t lds16_lds_bytes(const NetDesc &net) { return sizeof(float) * (size_t)lds16_pack_floats(net); }
 size_t lds16_lds_limit() { return kLds16MaxBytes; }
-bool lds16_supported(const NetDesc &net) { return lds16_list_ok(net) && lds16_lds_bytes(net) <= kLds16MaxBytes; }
+bool lds16_supported(const NetDesc &net) { return lds_list_ok(net, 128) && lds16_lds_bytes(net) <= kLds16MaxBytes; }
 
 static int lds16_tiles_max(const NetDesc &net)
 {
@@ -98,10 +90,6 @@ int lds16_block_threads(const NetDesc &net, int K, int cus)
   return largest;
 }
 
-// The read-ahead is requested HERE: without this the compiler moves a request behind the wave-uniform exit in front of its
-// use and waits for every block (no instruction, no wait: a compiler barrier for memory operations only)
-__device__ __forceinline__ void lds16_pin_reads() { asm volatile("" ::: "memory"); }
-
 #define MPPI_L16_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_16x16x4f32((A), (B), (C), 0, 0, 0)
 
 // a pair of tiles: stream blocks 2 MI and 2 MI + 1 are input tile MI of d0 and of d1 -- the same B operands, the k-steps of the
@@ -114,7 +102,7 @@ __device__ __forceinline__ void lds16_pair(f32x4 &d0, f32x4 &d1, const float (&a
     const f32x4 x0 = w[0], x1 = w[1];
     w[0] = p[(MI + 1) * 128];
     w[1] = p[(MI + 1) * 128 + 64];
-    lds16_pin_reads();
+    lds_pin_reads();
     d0 = MPPI_L16_MFMA(x0[0], act[4 * MI + 0], d0);
     d1 = MPPI_L16_MFMA(x1[0], act[4 * MI + 0], d1);
     d0 = MPPI_L16_MFMA(x0[1], act[4 * MI + 1], d0);
@@ -136,7 +124,7 @@ __device__ __forceinline__ void lds16_single_step(f32x4 &d, const float (&act)[M
     if (MI > 0 && MI >= mt_in) return;  // wave-uniform
     const f32x4 x = w[MI & 1];
     w[MI & 1] = p[(MI + 2) * 64];
-    lds16_pin_reads();
+    lds_pin_reads();
     d = MPPI_L16_MFMA(x[0], act[4 * MI + 0], d);
     d = MPPI_L16_MFMA(x[1], act[4 * MI + 1], d);
     d = MPPI_L16_MFMA(x[2], act[4 * MI + 2], d);
@@ -250,7 +238,7 @@ __global__ __launch_bounds__(THREADS) void rollout_lds16_kernel(const RolloutArg
     f32x4 w[2];
     w[0] = p1[0];
     w[1] = p1[64];
-    lds16_pin_reads();
+    lds_pin_reads();
     const float2 e = eps;
     const float2 Ut = Unext;
     const double rt = rt_next;
@@ -337,41 +325,27 @@ __global__ __launch_bounds__(THREADS) void rollout_lds16_kernel(const RolloutArg
 }
 #undef MPPI_L16_MFMA
 
+template <auto KERN>
+static hipError_t launch_lds16_instance(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const RolloutArgs &a, const Lds16Net &nd)
+{
+  if (hipError_t e = raise_lds_limit_once<KERN>(kLds16MaxBytes); e != hipSuccess) return e;
+  MPPI_LAUNCH_ROLLOUT(KERN, grid, block, lds, stream, a, nd);
+  return hipGetLastError();
+}
+
 hipError_t launch_rollout_lds16(const NetDesc &net, const RolloutArgs &a, int cus, hipStream_t stream)
 {
   if (!lds16_supported(net) || a.K % 64 != 0 || a.gate != nullptr || cus < 1) return hipErrorInvalidValue;
-  const bool affine = a.cost.affine != 0, ctrl = a.cost.need_control_cost != 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
   const int threads = lds16_block_threads(net, a.K, cus);
   const int waves = a.K / kRolloutsPerWave, wpb = threads / 64;
   const dim3 grid((waves + wpb - 1) / wpb), block(threads);
   const size_t lds = lds16_lds_bytes(net);
   const Lds16Net nd = lds16_net_of(net);
-  // more dynamic LDS than the default limit: set once per kernel instance and device
-#define MPPI_L16(MTM, AF, CT, TH)                                                                                      \
-  do {                                                                                                                 \
-    static bool attr_set[64] = {};                                                                                     \
-    if (!attr_set[dev]) {                                                                                              \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_lds16_kernel<MTM, AF, CT, TH>),       \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds16MaxBytes);             \
-      if (e != hipSuccess) return e;                                                                                   \
-      attr_set[dev] = true;                                                                                            \
-    }                                                                                                                  \
-    MPPI_LAUNCH_ROLLOUT((rollout_lds16_kernel<MTM, AF, CT, TH>), grid, block, lds, stream, a, nd);                     \
-  } while (0)
-#define MPPI_L16_COST(MTM, TH)                                 \
-  do {                                                         \
-    if (affine && !ctrl) MPPI_L16(MTM, true, false, TH);       \
-    else if (affine && ctrl) MPPI_L16(MTM, true, true, TH);    \
-    else if (!affine && !ctrl) MPPI_L16(MTM, false, false, TH); \
-    else MPPI_L16(MTM, false, true, TH);                       \
-  } while (0)
-  if (lds16_tiles_max(net) == 4) MPPI_L16_COST(4, 1024);
-  else MPPI_L16_COST(8, kLds16MaxThreads8);
-#undef MPPI_L16_COST
-#undef MPPI_L16
-  return hipGetLastError();
+  return dispatch_cost_flags(a.cost.affine != 0, a.cost.need_control_cost != 0, [&](auto af, auto ct) {
+    constexpr bool AF = decltype(af)::value, CT = decltype(ct)::value;
+    if (lds16_tiles_max(net) == 4) return launch_lds16_instance<&rollout_lds16_kernel<4, AF, CT, 1024>>(grid, block, lds, stream, a, nd);
+    return launch_lds16_instance<&rollout_lds16_kernel<8, AF, CT, kLds16MaxThreads8>>(grid, block, lds, stream, a, nd);
+  });
 }
 
 }  // namespace mppi

@@ -14,39 +14,9 @@
 //   * the OUTPUT layer is one more chain: W_out[c][k] sits at lane 16 c of the B image (zeros elsewhere), so after the
 //     transpose quad 0 of row c holds output c of rollouts 0..3 in register 0 -- the layout of the state register.  The
 //     reference's order in EVERY layer: bit-identical to "valu_lds", "valu", "quad", "row_exact".
-#include "group_roles.hpp"
-#include "m44_core.hpp"
-#include "mppi_kernels.hpp"
+#include "m44_group.hpp"
 
 namespace mppi {
-
-struct Lds44Net {
-  int n_layers;
-  int layers[8];
-};
-
-struct Lds44Shared {
-  static constexpr int NW = 4;            // dynamics waves per group, four rollouts each
-  static constexpr int NSW = 1;
-  static constexpr int kR = 16;
-  static constexpr bool kRecByAll = true;
-  int xseq[NW][64];
-  float rec[kGRing][kRolloutsPerWave][4];
-  int cost_done[64];
-  float ctl_b1[kGRing][64];
-  float ctl_rec[kGRing][kRolloutsPerWave][4];
-  int ctl_pub[64];
-  float tex[kGRing][kRolloutsPerWave][2];
-  int pose_pub[64];
-  float eps[kGRing][kRolloutsPerWave][2];
-  int rng_pub[64];
-  int fail[4];
-  int fin[8];
-  float gstate[8];   // gated launch: the vehicle state the pose wave took from the gate block, then 1 in gate_open[]
-  int gate_open[8];
-  float dump[NW][64 * kGRing];  // where the lanes that hold no record word put their copy (never read), per ring slot
-};
-constexpr size_t kLds44ImageOffset = (sizeof(Lds44Shared) + 15) & ~(size_t)15;
 
 // Image (pack_lds44_weights): float4 q of lane l at float4 index q * 64 + l.
 //   q 0 .. kLds44BiasQuads-1   float e = 4 q + c: bias of layer e for lane l -- hidden layers: b[l] x kTanhScale (0 for l >= nout);
@@ -71,11 +41,9 @@ __device__ __forceinline__ void lds44_chain(m44_f4 &d, const float (&T)[4], m44_
 }
 
 template <bool GATED>
-__device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44Net &net, Lds44Shared &sh, const m44_f4 *img, const int w)
+__device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const M44LayerList &net, M44GroupShared &sh, const m44_f4 *img, const int w)
 {
   const int lane = threadIdx.x & 63;
-  const int i = lane & 3, row = lane >> 4;
-  const int jr = 4 * w + i;  // rollout of the group (A layout: lane-in-quad = rollout)
   const bool hi = (lane & 2) != 0, od = (lane & 1) != 0;
   const int T = a.T;
   const int n_w = net.n_layers - 1;  // weight layers; the last one is the output layer
@@ -94,36 +62,10 @@ __device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44
 #pragma unroll
   for (int l = 1; l < 8; l++) nq_all |= (unsigned long long)lds44_quads_of(net.layers[l]) << (5 * l);
 
-  const uint32_t a_myseq = lds_addr(&sh.xseq[w][lane]);
-  typedef const volatile int __attribute__((address_space(3))) *lds_int_p;
-  typedef const volatile f32x2 __attribute__((address_space(3))) *lds_f2_p;
-  const lds_int_p p_pub = (lds_int_p)&sh.ctl_pub[0];
-  const lds_f2_p p_u = (lds_f2_p)&sh.ctl_rec[0][jr][0];  // clamped (u0, u1) of rollout lane & 3, ring slot 0
-  constexpr int kSlotF2 = kRolloutsPerWave * 2;
-  // the state record: quad 0 of row c holds s[3 + c] of rollouts 0..3; every lane stores (the others into a dump row)
-  const uint32_t a_rec0 = ((lane & 12) == 0) ? lds_addr(&sh.rec[0][jr][row]) : lds_addr(&sh.dump[w][lane]);
-  constexpr uint32_t kRecStride = sizeof(float) * kRolloutsPerWave * 4;
-  static_assert(kRecStride == sizeof(float) * 64, "dump rows move along with the record's ring slot");
-
-  int budget = spin_budget_init(a.spin_budget, T, a.fault_wave == w + 1);
-  float sv;
-  if constexpr (GATED) {  // the state arrives through the gate block: the pose wave has put it into LDS (group_gate_wait)
-    const uint32_t a_go = lds_addr(&sh.gate_open[0]);
-    while (lds_peek(a_go) == 0 && --budget > 0) __builtin_amdgcn_s_sleep(1);
-    const volatile float *gs = sh.gstate;
-    sv = gs[3 + row];
-  } else {
-    sv = a.state[3 + row];
-  }
-  while (__builtin_amdgcn_readfirstlane(*p_pub) < 1 && --budget > 0) __builtin_amdgcn_s_sleep(1);
-  f32x2 un = p_u[0];
-  asm volatile("" : "+v"(un));
-
+  M44Wave<GATED> wv(a, sh, w);
   for (int t = 0; t < T - 1; t++) {
-    const int slot = t & (kGRing - 1);
-    const f32x2 u = un;
-    asm volatile("ds_write_b32 %0, %1" ::"v"(a_rec0 + (uint32_t)slot * kRecStride), "v"(sv) : "memory");
-    lds_publish(a_myseq, t + 1);  // the record is out; also: this wave is done with the control record of step t
+    const f32x2 u = wv.open(t);
+    const float sv = wv.sv;
     // the first quads of layer 1, requested in front of layer 0
     m44_f4 wq[kLds44Ahead];
 #pragma unroll
@@ -136,10 +78,7 @@ __device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(sv, w0a[3], d, 4, 12, 0);
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(u.x, w0b[0], d, 4, 0, 0);
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(u.y, w0b[1], d, 4, 0, 0);
-    // requested now, used at the end of the step (rollout_row.hip)
-    const int sn = ((t + 1) & (kGRing - 1)) * kSlotF2;
-    const int cp_v = *p_pub;
-    un = p_u[sn];
+    wv.request(t + 1);
     float act[4], Tr[4];
     m44_tanh(d, bs0, act);
     if (pad0) act[0] = act[1] = act[2] = act[3] = 0.0f;
@@ -159,109 +98,25 @@ __device__ __forceinline__ void lds44_dynamics(const RolloutArgs &a, const Lds44
     // the output layer's D: lane 16 c of register r = output c of rollout r; transposed: quad 0 of row c, register 0
     act[0] = d[0]; act[1] = d[1]; act[2] = d[2]; act[3] = d[3];
     m44_transpose(act, Tr, hi, od);
-    const int want = t + 2;
-    const int cp_e = __builtin_amdgcn_readfirstlane(cp_v);
-    asm volatile("" : "+v"(un));
-    {
-      const float dd = Tr[0] + bo;
-      sv = fmaf(dd, a.dt, sv);  // incrementState, neural_net_model.cu:334-344
-      asm volatile("" : "+v"(sv));
-    }
-    if (__builtin_expect(cp_e < want, 0)) {
-      int cp = cp_e;
-      while (cp < want && --budget > 0) {
-        cp = __builtin_amdgcn_readfirstlane(*p_pub);
-        un = p_u[sn];
-      }
-      asm volatile("" : "+v"(un));
-    }
+    wv.close(t, a.dt, Tr[0] + bo);
   }
-  {  // the record of step T-1
-    const int t = T - 1;
-    asm volatile("ds_write_b32 %0, %1" ::"v"(a_rec0 + (uint32_t)(t & (kGRing - 1)) * kRecStride), "v"(sv) : "memory");
-    lds_publish(a_myseq, t + 1);
-  }
-  spin_finish(budget, lds_addr(&sh.fail[0]), lds_addr(&sh.fin[w]));
+  wv.finish(T - 1, sh, w);
 }
 
-// one group (workgroup): the four dynamics waves and the four riders; smem: the group's dynamic LDS (Lds44Shared, then the image)
-// GATED: enqueued one solve ahead (a.gate != nullptr), state and nominal sequence from the gate block: group_gate_wait
+// the kernels: m44_group.hpp's group with the image behind the shared state as the group's dynamic LDS
 template <bool AFFINE, bool CTRL, bool GATED>
-__device__ __forceinline__ void lds44_group(const RolloutArgs &a, const Lds44Net &net, const int img_f4, unsigned char *smem)
+__global__ __launch_bounds__(512) void rollout_lds44_kernel(const RolloutArgs a, const M44LayerList net, const int img_f4)
 {
-  using SH = Lds44Shared;
-  using RO = GroupRoles<SH>;
-  SH &sh = *reinterpret_cast<SH *>(smem);
-  m44_f4 *img = reinterpret_cast<m44_f4 *>(smem + kLds44ImageOffset);
-  const int lane = threadIdx.x & 63;
-  const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  MrgHalf g0{0, 0, 0};
-  if (role == RO::kRng) g0 = group_rng_load<SH>(a);
-  {  // the image into LDS: it is in LDS order, 16 B per thread and pass
-    const m44_f4 *src = reinterpret_cast<const m44_f4 *>(a.wpack);
-    for (int q = threadIdx.x; q < img_f4; q += 512) img[q] = src[q];
-  }
-  if (role == 0) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) sh.xseq[w][lane] = 0;
-    sh.cost_done[lane] = 0;
-    sh.ctl_pub[lane] = 0;
-    sh.pose_pub[lane] = 0;
-    sh.rng_pub[lane] = 0;
-    sh.fail[lane & 3] = 0;
-    sh.fin[lane & 7] = 0;
-    sh.gate_open[lane & 7] = 0;
-  }
-  __syncthreads();  // the only barrier
-  if (role < 4) lds44_dynamics<GATED>(a, net, sh, img, role);
-  else if (role == RO::kCost) group_cost_wave4<SH, CTRL>(a, sh);
-  else if (role == RO::kCtl) group_control_wave(a, sh, GATED ? lds_addr(&sh.gate_open[0]) : 0u);
-  else if (role == RO::kPose) {
-    if constexpr (GATED) {
-      const int shut = group_gate_wait(a, sh);
-      const volatile float *gs = sh.gstate;
-      const float x0 = gs[0], y0 = gs[1], yaw0 = gs[2];
-      group_pose_wave4<SH, AFFINE>(a, sh, x0, y0, yaw0, shut);
-    } else {
-      group_pose_wave4<SH, AFFINE>(a, sh);
-    }
-  }
-  else group_rng_wave<SH, true>(a, sh, g0);
+  m44_lds_kernel_body<&lds44_dynamics<GATED>, AFFINE, CTRL, GATED>(a, net, img_f4);
 }
-
-extern __shared__ __attribute__((aligned(16))) unsigned char lds44_smem[];
-
-template <bool AFFINE, bool CTRL, bool GATED>
-__global__ __launch_bounds__(512) void rollout_lds44_kernel(const RolloutArgs a, const Lds44Net net, const int img_f4)
-{
-  lds44_group<AFFINE, CTRL, GATED>(a, net, img_f4, lds44_smem);
-}
-
-// The two controllers of a tick in one launch (mppi_compute_control_batch, mppi_arm_batch): grid (groups of the larger
-// instance, 2) -- workgroup (x, y) runs group x of instance y, whose argument block sits at a compile-time position of the
-// kernel-argument segment (MPPI_BATCH_DISPATCH, mppi_device.hpp).  All instances have the SAME layer list: one Lds44Net, one
-// image size and one dynamic-LDS size serve the launch; each instance copies its own image from its own a.wpack.  GATED: every
-// instance's block carries its own handle's gate block (replica blockIdx.x % kGateReplicas: the group index inside the instance).
 template <bool AFFINE, bool CTRL, bool GATED, int NB>
-__global__ __launch_bounds__(512) void rollout_lds44_batch_kernel(const QuadBatchArgsT<NB> b, const Lds44Net net, const int img_f4)
+__global__ __launch_bounds__(512) void rollout_lds44_batch_kernel(const QuadBatchArgsT<NB> b, const M44LayerList net, const int img_f4)
 {
-#define MPPI_L44_BODY(A)                                                                                   \
-  do {                                                                                                     \
-    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* the smaller instance of the two */         \
-    lds44_group<AFFINE, CTRL, GATED>((A), net, img_f4, lds44_smem);                                        \
-  } while (0)
-  MPPI_BATCH_DISPATCH(NB, b, MPPI_L44_BODY);
-#undef MPPI_L44_BODY
+  m44_lds_batch_kernel_body<&lds44_dynamics<GATED>, AFFINE, CTRL, GATED, NB>(b, net, img_f4);
 }
 
 // every list 6 -> hidden widths 1..64 -> 4 with at least one hidden layer
-bool lds44_supported(const NetDesc &net)
-{
-  if (net.n_layers < 3 || net.n_layers > 8 || net.layers[0] != kNetIn || net.layers[net.n_layers - 1] != kNetOut) return false;
-  for (int l = 1; l + 1 < net.n_layers; l++)
-    if (net.layers[l] < 1 || net.layers[l] > 64) return false;
-  return true;
-}
+bool lds44_supported(const NetDesc &net) { return lds_list_ok(net, 64); }
 
 int lds44_pack_floats(const NetDesc &net)
 {
@@ -270,91 +125,39 @@ int lds44_pack_floats(const NetDesc &net)
   return q * 64 * 4;
 }
 
-// more dynamic LDS than the default limit: set once per kernel instance and device
-#define MPPI_L44_ATTR(KERN)                                                                                            \
-  do {                                                                                                                 \
-    static bool attr_set[64] = {};                                                                                     \
-    if (!attr_set[dev]) {                                                                                              \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&KERN), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                         160 * 1024);                                                                  \
-      if (e != hipSuccess) return e;                                                                                   \
-      attr_set[dev] = true;                                                                                            \
-    }                                                                                                                  \
-  } while (0)
+constexpr size_t kLds44MaxBytes = 160 * 1024;  // the dynamic-LDS limit the launchers request
 
 hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStream_t stream)
 {
   if (!lds44_supported(net) || a.K % kRolloutsPerWave != 0) return hipErrorInvalidValue;
-  const bool affine = a.cost.affine != 0, ctrl = a.cost.need_control_cost != 0, gated = a.gate != nullptr;
   const dim3 grid(a.K / kRolloutsPerWave), block(512);
   const int img_f4 = lds44_pack_floats(net) / 4;
-  const size_t lds = kLds44ImageOffset + sizeof(m44_f4) * (size_t)img_f4;
-  Lds44Net nd;
-  nd.n_layers = net.n_layers;
-  for (int i = 0; i < 8; i++) nd.layers[i] = net.layers[i];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-#define MPPI_L44(AF, CT, GA)                                                                                          \
-  do {                                                                                                                \
-    MPPI_L44_ATTR((rollout_lds44_kernel<AF, CT, GA>));                                                                \
-    MPPI_LAUNCH_ROLLOUT((rollout_lds44_kernel<AF, CT, GA>), grid, block, lds, stream, a, nd, img_f4);                 \
-  } while (0)
-  if (gated) {
-    if (affine && !ctrl) MPPI_L44(true, false, true);
-    else if (affine && ctrl) MPPI_L44(true, true, true);
-    else if (!affine && !ctrl) MPPI_L44(false, false, true);
-    else MPPI_L44(false, true, true);
-  } else {
-    if (affine && !ctrl) MPPI_L44(true, false, false);
-    else if (affine && ctrl) MPPI_L44(true, true, false);
-    else if (!affine && !ctrl) MPPI_L44(false, false, false);
-    else MPPI_L44(false, true, false);
-  }
-#undef MPPI_L44
-  return hipGetLastError();
+  const size_t lds = kM44GroupImageOffset + sizeof(m44_f4) * (size_t)img_f4;
+  const M44LayerList nd = m44_layer_list_of(net);
+  return dispatch_rollout_flags(a.cost.affine != 0, a.cost.need_control_cost != 0, a.gate != nullptr, [&](auto af, auto ct, auto ga) {
+    constexpr auto kern = &rollout_lds44_kernel<decltype(af)::value, decltype(ct)::value, decltype(ga)::value>;
+    if (hipError_t e = raise_lds_limit_once<kern>(kLds44MaxBytes); e != hipSuccess) return e;
+    MPPI_LAUNCH_ROLLOUT(kern, grid, block, lds, stream, a, nd, img_f4);
+    return hipGetLastError();
+  });
 }
 
 // two instances of ONE layer list (net) in one launch
 hipError_t launch_rollout_lds44_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream)
 {
-  if (b.n != 2 || !lds44_supported(net)) return hipErrorInvalidValue;
-  bool affine = true, ctrl = false;  // the general forms are exact supersets (rollout_mfma.hip)
-  int gmax = 0;
-  const bool gated = b.inst[0].gate != nullptr;  // mppi_arm_batch: every instance gated on its own block, or none
-  for (int i = 0; i < b.n; i++) {
-    if ((b.inst[i].gate != nullptr) != gated || b.inst[i].K % kRolloutsPerWave != 0) return hipErrorInvalidValue;
-    affine = affine && b.inst[i].cost.affine != 0;
-    ctrl = ctrl || b.inst[i].cost.need_control_cost != 0;
-    gmax = b.inst[i].K / kRolloutsPerWave > gmax ? b.inst[i].K / kRolloutsPerWave : gmax;
-  }
+  BatchFlags f;
+  if (b.n != 2 || !lds44_supported(net) || !batch_flags_of(b, f)) return hipErrorInvalidValue;
   const QuadBatchArgsT<2> b2 = batch_args_prefix<2>(b);
-  const dim3 grid(gmax, 2), block(512);
+  const dim3 grid(f.gmax, 2), block(512);
   const int img_f4 = lds44_pack_floats(net) / 4;
-  const size_t lds = kLds44ImageOffset + sizeof(m44_f4) * (size_t)img_f4;
-  Lds44Net nd;
-  nd.n_layers = net.n_layers;
-  for (int i = 0; i < 8; i++) nd.layers[i] = net.layers[i];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-#define MPPI_L44B(AF, CT, GA)                                                                                         \
-  do {                                                                                                                \
-    MPPI_L44_ATTR((rollout_lds44_batch_kernel<AF, CT, GA, 2>));                                                       \
-    hipLaunchKernelGGL((rollout_lds44_batch_kernel<AF, CT, GA, 2>), grid, block, lds, stream, b2, nd, img_f4);        \
-  } while (0)
-  if (gated) {
-    if (affine && !ctrl) MPPI_L44B(true, false, true);
-    else if (affine && ctrl) MPPI_L44B(true, true, true);
-    else if (!affine && !ctrl) MPPI_L44B(false, false, true);
-    else MPPI_L44B(false, true, true);
-  } else {
-    if (affine && !ctrl) MPPI_L44B(true, false, false);
-    else if (affine && ctrl) MPPI_L44B(true, true, false);
-    else if (!affine && !ctrl) MPPI_L44B(false, false, false);
-    else MPPI_L44B(false, true, false);
-  }
-#undef MPPI_L44B
-  return hipGetLastError();
+  const size_t lds = kM44GroupImageOffset + sizeof(m44_f4) * (size_t)img_f4;
+  const M44LayerList nd = m44_layer_list_of(net);
+  return dispatch_rollout_flags(f.affine, f.ctrl, f.gated, [&](auto af, auto ct, auto ga) {
+    constexpr auto kern = &rollout_lds44_batch_kernel<decltype(af)::value, decltype(ct)::value, decltype(ga)::value, 2>;
+    if (hipError_t e = raise_lds_limit_once<kern>(kLds44MaxBytes); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, b2, nd, img_f4);
+    return hipGetLastError();
+  });
 }
-#undef MPPI_L44_ATTR
 
 }  // namespace mppi

@@ -33,35 +33,14 @@
 //     Both are checked bit for bit against their oracle mode and against the NOMINAL oracle at the north-star tolerance
 //     (tests/test_m44_gpu.py); what the re-association costs at the 1e-4 mark, at the launch defaults:
 //     profiles/r05_b_nominal_margin_wd.txt (no more draws beyond 1e-4 than the exact oct form).
-#include "group_roles.hpp"
-#include "m44_core.hpp"
-#include "mppi_kernels.hpp"
+#include "m44_group.hpp"
 
 namespace mppi {
 
 constexpr int kM44H = 64;
 
-struct M44Shared {
-  static constexpr int NW = 4;            // dynamics waves per group, four rollouts each
-  static constexpr int NSW = 1;
-  static constexpr int kR = 16;
-  static constexpr bool kRecByAll = true;
-  int xseq[NW][64];
-  float rec[kGRing][kRolloutsPerWave][4];
-  int cost_done[64];
-  float ctl_b1[kGRing][64];
-  float ctl_rec[kGRing][kRolloutsPerWave][4];
-  int ctl_pub[64];
-  float tex[kGRing][kRolloutsPerWave][2];
-  int pose_pub[64];
-  float eps[kGRing][kRolloutsPerWave][2];
-  int rng_pub[64];
-  int fail[4];
-  int fin[8];
-  float gstate[8];   // gated launch: the vehicle state the pose wave took from the gate block, then 1 in gate_open[]
-  int gate_open[8];
-  m44_f4 wo[4][64];             // output-layer weights of lane l (6-64x4-4: they do not fit the registers beside 192 + ...)
-  float dump[NW][64 * kGRing];  // where the lanes that hold no record word put their copy (never read), per ring slot
+struct M44Shared : M44GroupShared {
+  m44_f4 wo[4][64];  // output-layer weights of lane l (6-64x4-4: they do not fit the registers beside 192 + ...)
 };
 
 // Image (pack_m44_weights, mppi_abi.hip): float4 q of lane l at float4 index q * 64 + l; as floats e = 4 q + c:
@@ -129,8 +108,6 @@ __device__ __forceinline__ void m44_dynamics(const RolloutArgs &a, M44Shared &sh
 {
   constexpr bool OUT_LDS = (NHID > 2);
   const int lane = threadIdx.x & 63;
-  const int i = lane & 3, row = lane >> 4;
-  const int jr = 4 * w + i;  // rollout of the group (A layout: lane-in-quad = rollout)
   const bool hi = (lane & 2) != 0, od = (lane & 1) != 0;
   const int T = a.T;
   const float4 *pk = reinterpret_cast<const float4 *>(a.wpack) + lane;
@@ -167,38 +144,13 @@ __device__ __forceinline__ void m44_dynamics(const RolloutArgs &a, M44Shared &sh
 #pragma unroll
     for (int k = 0; k < kM44H; k++) asm volatile("" : "+v"(wh[l][k]));
 
-  const uint32_t a_myseq = lds_addr(&sh.xseq[w][lane]);
-  typedef const volatile int __attribute__((address_space(3))) *lds_int_p;
-  typedef const volatile f32x2 __attribute__((address_space(3))) *lds_f2_p;
   typedef const volatile m44_f4 __attribute__((address_space(3))) *lds_f4_p;
-  const lds_int_p p_pub = (lds_int_p)&sh.ctl_pub[0];
-  const lds_f2_p p_u = (lds_f2_p)&sh.ctl_rec[0][jr][0];  // clamped (u0, u1) of rollout lane & 3, ring slot 0
   const lds_f4_p p_wo = (lds_f4_p)&sh.wo[0][lane];
-  constexpr int kSlotF2 = kRolloutsPerWave * 2;
-  // the state record: quad 0 of row c holds s[3 + c] of rollouts 0..3; every lane stores (the others into a dump row)
-  const uint32_t a_rec0 = ((lane & 12) == 0) ? lds_addr(&sh.rec[0][jr][row]) : lds_addr(&sh.dump[w][lane]);
-  constexpr uint32_t kRecStride = sizeof(float) * kRolloutsPerWave * 4;
-  static_assert(kRecStride == sizeof(float) * 64, "dump rows move along with the record's ring slot");
 
-  int budget = spin_budget_init(a.spin_budget, T, a.fault_wave == w + 1);
-  float sv;
-  if constexpr (GATED) {  // the state arrives through the gate block: the pose wave has put it into LDS (group_gate_wait)
-    const uint32_t a_go = lds_addr(&sh.gate_open[0]);
-    while (lds_peek(a_go) == 0 && --budget > 0) __builtin_amdgcn_s_sleep(1);
-    const volatile float *gs = sh.gstate;
-    sv = gs[3 + row];
-  } else {
-    sv = a.state[3 + row];
-  }
-  while (__builtin_amdgcn_readfirstlane(*p_pub) < 1 && --budget > 0) __builtin_amdgcn_s_sleep(1);
-  f32x2 un = p_u[0];
-  asm volatile("" : "+v"(un));
-
+  M44Wave<GATED> wv(a, sh, w);
   for (int t = 0; t < T - 1; t++) {
-    const int slot = t & (kGRing - 1);
-    const f32x2 u = un;
-    asm volatile("ds_write_b32 %0, %1" ::"v"(a_rec0 + (uint32_t)slot * kRecStride), "v"(sv) : "memory");
-    lds_publish(a_myseq, t + 1);  // the record is out; also: this wave is done with the control record of step t
+    const f32x2 u = wv.open(t);
+    const float sv = wv.sv;
     // layer 0: [s3, s4, s5, s6, u0, u1] -- row c of the state register is component c: ABID = 4 c
     m44_f4 d = {0.0f, 0.0f, 0.0f, 0.0f};
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(sv, w0[0], d, 4, 0, 0);
@@ -207,10 +159,7 @@ __device__ __forceinline__ void m44_dynamics(const RolloutArgs &a, M44Shared &sh
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(sv, w0[3], d, 4, 12, 0);
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(u.x, w0[4], d, 4, 0, 0);
     d = __builtin_amdgcn_mfma_f32_4x4x1f32(u.y, w0[5], d, 4, 0, 0);
-    // requested now, used at the end of the step (rollout_row.hip)
-    const int sn = ((t + 1) & (kGRing - 1)) * kSlotF2;
-    const int cp_v = *p_pub;
-    un = p_u[sn];
+    wv.request(t + 1);
     float act[4], Tr[4];
     m44_tanh(d, bsv[0], act);
 #pragma unroll
@@ -248,114 +197,44 @@ __device__ __forceinline__ void m44_dynamics(const RolloutArgs &a, M44Shared &sh
       m44_tanh(d, bsv[l], act);
     }
     m44_transpose(act, Tr, hi, od);
-    const int want = t + 2;
-    const int cp_e = __builtin_amdgcn_readfirstlane(cp_v);
-    asm volatile("" : "+v"(un));
-    {
-      const float dd = m44_out_tree(oq, op, Tr) + bo;
-      sv = fmaf(dd, a.dt, sv);  // incrementState, neural_net_model.cu:334-344
-      asm volatile("" : "+v"(sv));
-    }
-    if (__builtin_expect(cp_e < want, 0)) {
-      int cp = cp_e;
-      while (cp < want && --budget > 0) {
-        cp = __builtin_amdgcn_readfirstlane(*p_pub);
-        un = p_u[sn];
-      }
-      asm volatile("" : "+v"(un));
-    }
+    wv.close(t, a.dt, m44_out_tree(oq, op, Tr) + bo);
   }
-  {  // the record of step T-1
-    const int t = T - 1;
-    asm volatile("ds_write_b32 %0, %1" ::"v"(a_rec0 + (uint32_t)(t & (kGRing - 1)) * kRecStride), "v"(sv) : "memory");
-    lds_publish(a_myseq, t + 1);
-  }
-  spin_finish(budget, lds_addr(&sh.fail[0]), lds_addr(&sh.fin[w]));
+  wv.finish(T - 1, sh, w);
 }
 
-// one group (workgroup): the four dynamics waves and the four riders
-// GATED: enqueued one solve ahead (a.gate != nullptr), state and nominal sequence from the gate block: group_gate_wait
-template <int NHID, bool AFFINE, bool CTRL, bool SPLIT, bool GATED>
-__device__ __forceinline__ void m44_group(const RolloutArgs &a, M44Shared &sh)
-{
-  using SH = M44Shared;
-  using RO = GroupRoles<SH>;
-  const int lane = threadIdx.x & 63;
-  const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  MrgHalf g0{0, 0, 0};
-  if (role == RO::kRng) g0 = group_rng_load<SH>(a);
-  if (role == 0) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) sh.xseq[w][lane] = 0;
-    sh.cost_done[lane] = 0;
-    sh.ctl_pub[lane] = 0;
-    sh.pose_pub[lane] = 0;
-    sh.rng_pub[lane] = 0;
-    sh.fail[lane & 3] = 0;
-    sh.fin[lane & 7] = 0;
-    sh.gate_open[lane & 7] = 0;
-  }
-  if (role == 1) {  // the output layer's weights into LDS
+// m44_group.hpp's group: the hidden weights are in registers, wave 1 puts the output layer's into LDS
+template <int NHID, bool SPLIT>
+struct M44Form {
+  using Shared = M44Shared;
+  __device__ __forceinline__ void stage_by_all(const RolloutArgs &, Shared &) const {}
+  __device__ __forceinline__ void stage_by_wave1(const RolloutArgs &a, Shared &sh) const
+  {
+    const int lane = threadIdx.x & 63;
     const m44_f4 *src = reinterpret_cast<const m44_f4 *>(a.wpack) + m44_q_out<NHID>() * 64 + lane;
 #pragma unroll
     for (int s = 0; s < 4; s++) sh.wo[s][lane] = src[s * 64];
   }
-  __syncthreads();  // the only barrier
-  if (role < 4) m44_dynamics<NHID, SPLIT, GATED>(a, sh, role);
-  else if (role == RO::kCost) group_cost_wave4<SH, CTRL>(a, sh);
-  else if (role == RO::kCtl) group_control_wave(a, sh, GATED ? lds_addr(&sh.gate_open[0]) : 0u);
-  else if (role == RO::kPose) {
-    if constexpr (GATED) {
-      const int shut = group_gate_wait(a, sh);
-      const volatile float *gs = sh.gstate;
-      const float x0 = gs[0], y0 = gs[1], yaw0 = gs[2];
-      group_pose_wave4<SH, AFFINE>(a, sh, x0, y0, yaw0, shut);
-    } else {
-      group_pose_wave4<SH, AFFINE>(a, sh);
-    }
+  template <bool GATED>
+  __device__ __forceinline__ void dynamics(const RolloutArgs &a, Shared &sh, const int w) const
+  {
+    m44_dynamics<NHID, SPLIT, GATED>(a, sh, w);
   }
-  else group_rng_wave<SH, true>(a, sh, g0);
-}
+};
 
 template <int NHID, bool AFFINE, bool CTRL, bool SPLIT, bool GATED = false>
 __global__ __launch_bounds__(512) void rollout_m44_kernel(const RolloutArgs a)
 {
   __shared__ __attribute__((aligned(16))) M44Shared sh;
-  m44_group<NHID, AFFINE, CTRL, SPLIT, GATED>(a, sh);
+  m44_group_body<AFFINE, CTRL, GATED>(a, sh, M44Form<NHID, SPLIT>{});
 }
 
-// The two controllers of a tick in one launch (mppi_compute_control_batch; the split form only: the automatic one, and the one
-// that has a gated form): grid (groups of the larger instance, 2) -- workgroup (x, y) runs group x of instance y, whose argument
-// block sits at a compile-time position of the kernel-argument segment (MPPI_BATCH_DISPATCH, mppi_device.hpp: the body reads
-// its parameters as the single-instance kernel does, not through scratch).  Every block carries its own wpack and generator
-// state; the body is m44_group, unchanged: an instance's bits are those of its own launch.
-template <int NHID, bool AFFINE, bool CTRL, int NB>
+// The two controllers of a tick in one launch (m44_group_batch_body; the split form only: the automatic one, and the one that
+// has a gated form)
+template <int NHID, bool AFFINE, bool CTRL, bool GATED, int NB>
 __global__ __launch_bounds__(512) void rollout_m44_batch_kernel(const QuadBatchArgsT<NB> b)
 {
   __shared__ __attribute__((aligned(16))) M44Shared sh;
-#define MPPI_M44_BODY(A)                                                                                   \
-  do {                                                                                                     \
-    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* the smaller instance of the two */         \
-    m44_group<NHID, AFFINE, CTRL, true, false>((A), sh);                                                   \
-  } while (0)
-  MPPI_BATCH_DISPATCH(NB, b, MPPI_M44_BODY);
-#undef MPPI_M44_BODY
-}
-
-// the same enqueued one solve ahead (mppi_arm_batch): every instance's block carries its OWN handle's gate block, whose pose
-// wave polls replica blockIdx.x % kGateReplicas of it -- blockIdx.x is the group index inside the instance, as in the single
-// gated kernel
-template <int NHID, bool AFFINE, bool CTRL, int NB>
-__global__ __launch_bounds__(512) void rollout_m44_batch_gated_kernel(const QuadBatchArgsT<NB> b)
-{
-  __shared__ __attribute__((aligned(16))) M44Shared sh;
-#define MPPI_M44_BODY(A)                                                                                   \
-  do {                                                                                                     \
-    if ((int)blockIdx.x >= (A).K / kRolloutsPerWave) return; /* the smaller instance of the two */         \
-    m44_group<NHID, AFFINE, CTRL, true, true>((A), sh);                                                    \
-  } while (0)
-  MPPI_BATCH_DISPATCH(NB, b, MPPI_M44_BODY);
-#undef MPPI_M44_BODY
+  m44_group_batch_body<AFFINE, CTRL, GATED, NB>(b, sh, M44Form<NHID, true>{});
 }
 
 bool m44_variant_supported(int hidden, int n_hidden) { return hidden == 64 && (n_hidden == 2 || n_hidden == 4); }
@@ -364,24 +243,14 @@ int m44_pack_floats(int n_hidden) { return (n_hidden == 2 ? m44_q_total<2>() : m
 template <int NHID, bool SPLIT>
 static hipError_t launch_m44(const RolloutArgs &a, hipStream_t stream)
 {
-  const bool affine = a.cost.affine != 0, ctrl = a.cost.need_control_cost != 0;
   const dim3 grid(a.K / kRolloutsPerWave), block(512);
-  if (a.gate != nullptr) {  // the gated form exists for the automatic (split) form only: abi_solve.hip: chain_ok
-    if constexpr (SPLIT) {
-      if (affine && !ctrl) MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, true, false, true, true>), grid, block, 0, stream, a);
-      else if (affine && ctrl) MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, true, true, true, true>), grid, block, 0, stream, a);
-      else if (!affine && !ctrl) MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, false, false, true, true>), grid, block, 0, stream, a);
-      else MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, false, true, true, true>), grid, block, 0, stream, a);
-      return hipGetLastError();
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  if (affine && !ctrl) MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, true, false, SPLIT>), grid, block, 0, stream, a);
-  else if (affine && ctrl) MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, true, true, SPLIT>), grid, block, 0, stream, a);
-  else if (!affine && !ctrl) MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, false, false, SPLIT>), grid, block, 0, stream, a);
-  else MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, false, true, SPLIT>), grid, block, 0, stream, a);
-  return hipGetLastError();
+  const bool gated = a.gate != nullptr;
+  if (gated && !SPLIT) return hipErrorInvalidValue;  // the gated form exists for the automatic (split) form only: abi_solve.hip: chain_ok
+  return dispatch_rollout_flags(a.cost.affine != 0, a.cost.need_control_cost != 0, gated, [&](auto af, auto ct, auto ga) {
+    if constexpr (SPLIT || !decltype(ga)::value)
+      MPPI_LAUNCH_ROLLOUT((rollout_m44_kernel<NHID, decltype(af)::value, decltype(ct)::value, SPLIT, decltype(ga)::value>), grid, block, 0, stream, a);
+    return hipGetLastError();
+  });
 }
 
 // split: the hidden layers as two accumulation chains (the automatic form); false: one chain, the reference's order ("m44_chain")
@@ -392,42 +261,20 @@ hipError_t launch_rollout_m44(int hidden, int n_hidden, const RolloutArgs &a, bo
   return split ? launch_m44<4, true>(a, stream) : launch_m44<4, false>(a, stream);
 }
 
-template <int NHID>
-static hipError_t launch_m44_batch2(const QuadBatchArgsT<2> &b2, bool affine, bool ctrl, bool gated, dim3 grid, hipStream_t stream)
-{
-  const dim3 block(512);
-#define MPPI_M44_BATCH(KERN)                                                                                  \
-  do {                                                                                                        \
-    if (affine && !ctrl) hipLaunchKernelGGL((KERN<NHID, true, false, 2>), grid, block, 0, stream, b2);        \
-    else if (affine && ctrl) hipLaunchKernelGGL((KERN<NHID, true, true, 2>), grid, block, 0, stream, b2);     \
-    else if (!affine && !ctrl) hipLaunchKernelGGL((KERN<NHID, false, false, 2>), grid, block, 0, stream, b2); \
-    else hipLaunchKernelGGL((KERN<NHID, false, true, 2>), grid, block, 0, stream, b2);                        \
-  } while (0)
-  if (gated) MPPI_M44_BATCH(rollout_m44_batch_gated_kernel);
-  else MPPI_M44_BATCH(rollout_m44_batch_kernel);
-#undef MPPI_M44_BATCH
-  return hipGetLastError();
-}
-
-// the split form for the two controllers of a tick (two instances only: each (NHID, AFFINE, CTRL, gated) instance is a
+// the split form for the two controllers of a tick (two instances only: each (NHID, AFFINE, CTRL, GATED) instance is a
 // 240-register kernel); every instance 6 -> 64 x n_hidden -> 4
 hipError_t launch_rollout_m44_batch(int n_hidden, const QuadBatchArgs &b, hipStream_t stream)
 {
-  if (b.n != 2 || !m44_variant_supported(kM44H, n_hidden)) return hipErrorInvalidValue;
-  bool affine = true, ctrl = false;  // the general forms are exact supersets (rollout_mfma.hip)
-  int gmax = 0;
-  const bool gated = b.inst[0].gate != nullptr;  // mppi_arm_batch: every instance gated on its own block, or none
-  for (int i = 0; i < b.n; i++) {
-    if ((b.inst[i].gate != nullptr) != gated || b.inst[i].K % kRolloutsPerWave != 0) return hipErrorInvalidValue;
-    affine = affine && b.inst[i].cost.affine != 0;
-    ctrl = ctrl || b.inst[i].cost.need_control_cost != 0;
-    gmax = b.inst[i].K / kRolloutsPerWave > gmax ? b.inst[i].K / kRolloutsPerWave : gmax;
-  }
+  BatchFlags f;
+  if (b.n != 2 || !m44_variant_supported(kM44H, n_hidden) || !batch_flags_of(b, f)) return hipErrorInvalidValue;
   const QuadBatchArgsT<2> b2 = batch_args_prefix<2>(b);
-  const dim3 grid(gmax, 2);
-  return n_hidden == 2 ? launch_m44_batch2<2>(b2, affine, ctrl, gated, grid, stream)
-                       : launch_m44_batch2<4>(b2, affine, ctrl, gated, grid, stream);
+  const dim3 grid(f.gmax, 2), block(512);
+  return dispatch_rollout_flags(f.affine, f.ctrl, f.gated, [&](auto af, auto ct, auto ga) {
+    constexpr bool AF = decltype(af)::value, CT = decltype(ct)::value, GA = decltype(ga)::value;
+    if (n_hidden == 2) hipLaunchKernelGGL((rollout_m44_batch_kernel<2, AF, CT, GA, 2>), grid, block, 0, stream, b2);
+    else hipLaunchKernelGGL((rollout_m44_batch_kernel<4, AF, CT, GA, 2>), grid, block, 0, stream, b2);
+    return hipGetLastError();
+  });
 }
-
 
 }  // namespace mppi
