@@ -78,6 +78,7 @@ Form form_of(const mppi_handle *h)
     // basis-function model, wavefronts per 64 rollouts: dynamics + cost + control wave (in-kernel generator) while each gets
     // a SIMD of its own; dynamics + cost wave up to twice that; else one wave
     if (h->forced == Form::Bf1 || h->forced == Form::Bf2 || h->forced == Form::Bf3) return h->forced;
+    if (h->forced == Form::BfRow) return Form::BfRow;  // by name only
     if (3 * (h->K / 64) <= h->num_simds) return Form::Bf3;
     return (2 * (h->K / 64) <= 2 * h->num_simds) ? Form::Bf2 : Form::Bf1;
   }
@@ -110,7 +111,7 @@ bool has_noise_wave(const mppi_handle *h)
 {
   switch (form_of(h)) {
     case Form::Bf3: case Form::Quad: case Form::Row: case Form::RowTree: case Form::Row64R16: case Form::M44: case Form::M44Chain:
-    case Form::Lds44: case Form::Lds128:
+    case Form::Lds44: case Form::Lds128: case Form::BfRow:
       return true;
     case Form::Oct: case Form::Multi2: case Form::Multi4: case Form::Multi4Tree:
       return !form_generator_noise(h);
@@ -140,6 +141,7 @@ const char *mppi_rollout_variant(const mppi_handle *h)
     case Form::Bf3: return "basis_funcs25_valu_3w";
     case Form::Bf2: return "basis_funcs25_valu_2w";
     case Form::Bf1: return "basis_funcs25_valu";
+    case Form::BfRow: return "basis_funcs25_row8w";
     case Form::ValuReg: return "valu_reg_lds";
     case Form::ValuLds: return "valu_lds";
     case Form::Multi4Tree: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_multi4_tree%s", h->hidden, h->n_hidden, gen); break;
@@ -197,6 +199,12 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
   else if (strcmp(name, "bf3") == 0) {
     if ((rc = need(h->basis, "bf3 is a form of the basis-function model"))) return rc;
     h->forced = Form::Bf3;
+  }
+  else if (strcmp(name, "bf_row") == 0) {  // the latency form of the basis-function model; the bits of bf3
+    if ((rc = need(h->basis, "bf_row is a form of the basis-function model"))) return rc;
+    if ((rc = need(h->K % kRolloutsPerWave == 0, "bf_row form needs K to be a multiple of 16"))) return rc;
+    if ((rc = need(h->d_bfrowpack != nullptr, "bf_row form: this handle has no image"))) return rc;
+    h->forced = Form::BfRow;
   }
   else if (strcmp(name, "row") == 0 || strcmp(name, "row_exact") == 0 || strcmp(name, "row_tree") == 0) {
     if ((rc = need(h->mfma_ok && row_variant_supported(h->hidden, h->n_hidden), "row form exists for 6-32x2-4"))) return rc;

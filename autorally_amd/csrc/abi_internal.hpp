@@ -57,6 +57,8 @@ enum class Form : int {
                                     // v_mfma_f32_16x16x4, the A operands from an LDS image, the reference's order; by name only ("lds16")
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
+  BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
+                                    // riders per 16 rollouts), the bits of Bf1..3; by name only ("bf_row")
 };
 enum class Pref : int { Auto = 0, Mfma, Valu, ValuLds };
 
@@ -145,6 +147,7 @@ struct mppi_handle {
   float *d_theta = nullptr, *d_wpack = nullptr, *d_map = nullptr;
   float *d_theta_s = nullptr;  // theta with hidden-layer biases * kTanhScale (register VALU kernel)
   float *d_rowpack = nullptr;  // 6-32-32-4: the weights in the register order of the row form (rollout_row.hip)
+  float *d_bfrowpack = nullptr;  // basis-function model: the per-lane image of rollout_bf_row.hip
   float *d_row64pack = nullptr;  // 64-wide nets: register + LDS image of rollout_row64.hip
   float *d_m44pack = nullptr;    // 64-wide nets: image of rollout_m44.hip
   float *d_lds44pack = nullptr;  // any layer list with hidden widths <= 64: image of rollout_lds44.hip
@@ -245,6 +248,7 @@ inline hipError_t ensure_device(int dev)
 int compute_k99(int K);
 std::vector<float> pack_mfma_weights(const std::vector<float> &theta, int H, int NHID);
 std::vector<float> pack_row_weights(const std::vector<float> &theta);
+std::vector<float> pack_bf_row_weights(const std::vector<float> &W);
 std::vector<float> pack_row64_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID);
 std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);

@@ -142,6 +142,37 @@ std::vector<float> pack_row_weights(const std::vector<float> &theta)
   return out;
 }
 
+// Per-lane image of the basis-function row form (rollout_bf_row.hip: bf_row_load; the layout is written down at
+// kBfRowSlots, mppi_kernels.hpp): lane p = 4 j + y of a rollout's DPP row runs y-thread y of output j, slot m of the lane is
+// basis function i = y + 4 m.  The divisors are those of basis_funcs_from (basis_funcs.hpp; car_bfs.cuh:44-120), 0 = the basis
+// function is its numerator; the reciprocals are the RN(1 / c) of MPPI_DIVC.
+std::vector<float> pack_bf_row_weights(const std::vector<float> &W)
+{
+  static const float kDiv[kNumBfs] = {0.0f, 10.0f, 1200.0f, 1440000.0f, 1728000000.0f, 25.0f, 10.0f, 10.0f, 0.0f, 40.0f,
+                                      1400.0f, 1960000.0f, 2744000000.0f, 40.0f, 1600.0f, 64000.0f, 50.0f, 0.0f, 0.0f, 3.0f,
+                                      5.0f, 100.0f, 1000.0f, 0.0f, 0.0f};
+  std::vector<float> out((size_t)bf_row_pack_floats(), 0.0f);
+  for (int p = 0; p < 16; p++) {
+    const int j = p >> 2, y = p & 3;
+    auto slot = [&](int e0, int m) { return &out[((size_t)(e0 + m / 4) * 16 + p) * 4 + m % 4]; };
+    unsigned marks = 0;
+    for (int m = 0; m < kBfRowSlots; m++) {
+      const int i = y + 4 * m;
+      const bool used = i < kNumBfs, plain = !used || kDiv[i] == 0.0f;
+      const float c = plain ? 1.0f : kDiv[i];
+      *slot(0, m) = used ? W[(size_t)j * kNumBfs + i] : 0.0f;
+      *slot(2, m) = c;
+      *slot(4, m) = 1.0f / c;
+      if (plain) marks |= kBfRowPlain << m;
+      if (i == 9 || i == 13 || i == 14 || i == 15) marks |= kBfRowBigOnly << m;
+      if (used) marks |= kBfRowUsed << m;
+      if (i == 13 || i == 14) marks |= kBfRowDouble;
+    }
+    memcpy(slot(0, kBfRowSlots), &marks, sizeof(marks));  // the last word of entry 1
+  }
+  return out;
+}
+
 // Image of the 64-wide row form (rollout_row64.hip: row64_load + the LDS part): lane g of a 32-lane rollout owns neurons
 // 2g, 2g+1 of every hidden layer; register entry i of lane g at float4 index i * 32 + g, then the 64 x 64 layers as
 // [layer][k][g] pairs.  Hidden biases times kTanhScale.  Output layer in the order of row64_out_tree: Q = outputs {0, 1},

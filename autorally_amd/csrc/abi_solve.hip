@@ -58,7 +58,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.noise = noise;
   a.costs = h->d_costs;
   const Form f = form_of(h);
-  a.wpack = form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
+  a.wpack = f == Form::BfRow ? h->d_bfrowpack : form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
             : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : f == Form::Lds16 ? h->d_lds16pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
   a.inv_t = h->d_invt;
   a.K = h->K;
@@ -71,7 +71,9 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
     a.u_hi[i] = h->u_hi[i];
   }
   a.dt = h->dt;
-  a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
+  // (the bf_row form's kinematics are the riders': computeKinematics of the basis-function model always negates the yaw rate,
+  // generalized_linear.cu:212-217 -- its own kernels never look at the flag)
+  a.negate_yaw_der = (h->cfg.negate_yaw_der || f == Form::BfRow) ? 1 : 0;
   a.rng_in = nullptr;
   a.rng_out = nullptr;
   a.inline_noise = 0;
@@ -116,6 +118,7 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
   hipError_t e = hipSuccess;
   switch (f) {
     case Form::Bf1: case Form::Bf2: case Form::Bf3: e = launch_rollout_bf(a, form_bf_waves(f), h->stream); break;
+    case Form::BfRow: e = launch_rollout_bf_row(a, h->stream); break;
     case Form::Multi2: case Form::Multi4: case Form::Multi4Tree:
       e = launch_rollout_multi(h->hidden, h->n_hidden, a, form_multi_nd(f), h->stream);
       break;
@@ -581,15 +584,15 @@ int enqueue_solve(mppi_handle *h, const float *state)
 // d_in at the one it smooths into.
 
 // The forms that have a gated rollout and gain from it (one iteration, no stage events, no capture): 1: a latency form with
-// riders (the row forms, the automatic m44 form, the lds44 and lds128 forms) and its in-kernel generator; 2: the automatic multi4-tree form with the
+// riders (the row forms, the automatic m44 form, the lds44 and lds128 forms, the basis-function model's bf_row form) and its in-kernel generator; 2: the automatic multi4-tree form with the
 // stand-alone generator kernel prefetched on a second stream; 0: none
 static int arm_kind(const mppi_handle *h)
 {
-  if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
-        h->explicit_iters == 0 && !h->basis && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
-    return 0;
   const Form f = form_of(h);
-  if ((form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128) && has_noise_wave(h) && !h->prefetch_valid) return 1;
+  if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
+        h->explicit_iters == 0 && (!h->basis || f == Form::BfRow) && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
+    return 0;
+  if ((form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::BfRow) && has_noise_wave(h) && !h->prefetch_valid) return 1;
   // (where the generator kernel runs beside the rollout.  Where it runs behind it -- 32-wide nets at K = 65 536 -- the phase
   // between two rollouts is the generator's own 41 us whatever the launches cost: chained 0.3139, unchained 0.3131 ms)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;
@@ -812,7 +815,8 @@ static hipError_t launch_rollout_batch(mppi_handle *const *hs, int n, const Quad
 {
   const mppi_handle *h0 = hs[0];
   const Form f = form_of(h0);
-  const hipError_t e = h0->basis          ? launch_rollout_bf_batch(qb, S)
+  const hipError_t e = f == Form::BfRow   ? launch_rollout_bf_row_batch(qb, S)
+                       : h0->basis        ? launch_rollout_bf_batch(qb, S)
                        : form_is_row(f)   ? launch_rollout_row_batch(qb, f == Form::RowTree, S)
                        : f == Form::M44   ? launch_rollout_m44_batch(h0->n_hidden, qb, S)
                        : f == Form::Lds44 ? launch_rollout_lds44_batch(h0->net, qb, S)
@@ -827,13 +831,13 @@ static hipError_t launch_rollout_batch(mppi_handle *const *hs, int n, const Quad
 }
 
 // mppi_arm_batch: one launch for the batch where mppi_compute_control_batch would use one and the form has a gated batched kernel
-// (the row forms; the pair of the automatic m44 form, of the lds44 form and of the lds128 form)
+// (the row forms; the pair of the automatic m44 form, of the lds44 form, of the lds128 form and of the bf_row form)
 static bool batch_together(mppi_handle *const *hs, int n);
 static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
 {
   mppi_handle *h0 = hs[0];
   const Form f0 = form_of(h0);
-  if (!(form_is_row(f0) || f0 == Form::M44 || f0 == Form::Lds44 || f0 == Form::Lds128))
+  if (!(form_is_row(f0) || f0 == Form::M44 || f0 == Form::Lds44 || f0 == Form::Lds128 || f0 == Form::BfRow))
     return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
   for (int i = 0; i < n; i++)
     if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");
@@ -894,7 +898,8 @@ static bool batch_together(mppi_handle *const *hs, int n)
     const bool wide = f == Form::M44 || by_list;
     bool same_list = h->net.n_layers == h0->net.n_layers;
     for (int l = 0; l < h->net.n_layers && same_list; l++) same_list = h->net.layers[l] == h0->net.layers[l];
-    const bool form_ok = h->basis ? (h0->basis && f == Form::Bf3)
+    // (... or the pair of its bf_row form, by name only: forced on both handles)
+    const bool form_ok = h->basis ? (h0->basis && (f == Form::Bf3 || (f == Form::BfRow && n == 2)) && f == form_of(h0))
                                   : (!h0->basis && (f == Form::Quad || form_is_row(f) || (wide && n == 2)) && f == form_of(h0) &&
                                      h->hidden == h0->hidden && h->n_hidden == h0->n_hidden && (!by_list || same_list));
     // one kernel instance serves the whole batch: the instances must agree on what it is specialised for (affine / projective
@@ -911,8 +916,9 @@ static bool batch_together(mppi_handle *const *hs, int n)
     together = form_ok && ci.affine == c0.affine && ctrl_ok &&
                h->cfg.device == h0->cfg.device && h->cfg.num_iters == h0->cfg.num_iters &&
                h->K <= 4096 && !h->timing && !h->capture && !h->prefetch_valid && h->have_nn && h->have_map && h->have_cost;
-    // waves of a group that need a SIMD each: quad 4, row 4 dynamics waves (its riders ride), basis functions 3
-    waves += h->basis ? 3 * (h->K / 64) : 4 * (h->K / kRolloutsPerWave);
+    // waves of a group that need a SIMD each: quad 4, row 4 dynamics waves (its riders ride), basis functions 3 per 64 rollouts
+    // (bf_row: the row form's 4 per 16)
+    waves += (h->basis && f != Form::BfRow) ? 3 * (h->K / 64) : 4 * (h->K / kRolloutsPerWave);
   }
   return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
 }

@@ -44,7 +44,7 @@ void free_all(mppi_handle *h)
 {
   if (!h) return;
   float *fp[] = {h->d_theta_s, h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
-                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_lds128pack, h->d_lds16pack, h->d_cap, h->d_tracepack, h->d_trace};
+                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_bfrowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_lds128pack, h->d_lds16pack, h->d_cap, h->d_tracepack, h->d_trace};
   for (float *p : fp)
     if (p) (void)hipFree(p);
   if (h->d_invt) (void)hipFree(h->d_invt);
@@ -236,6 +236,7 @@ int mppi_create(const mppi_config *cfg, mppi_handle **out)
   if (h->mfma_ok)
     CR(hipMalloc(&h->d_wpack, sizeof(float) * 64 * (size_t)mfma_pack_floats_per_lane(h->hidden, h->n_hidden)));
   if (h->mfma_ok && row_variant_supported(h->hidden, h->n_hidden)) CR(hipMalloc(&h->d_rowpack, sizeof(float) * (size_t)row_pack_floats()));
+  if (basis) CR(hipMalloc(&h->d_bfrowpack, sizeof(float) * (size_t)bf_row_pack_floats()));
   if (h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden))
     CR(hipMalloc(&h->d_row64pack, sizeof(float) * (size_t)row64_pack_floats(h->n_hidden)));
   if (h->mfma_ok && m44_variant_supported(h->hidden, h->n_hidden))
@@ -336,6 +337,10 @@ int mppi_set_bf_params(mppi_handle *h, const float *W, size_t n)
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->theta.assign(W, W + n);
   HIPCHK(h, hipMemcpy(h->d_theta, W, n * sizeof(float), hipMemcpyHostToDevice));
+  {
+    const std::vector<float> pk = pack_bf_row_weights(h->theta);
+    HIPCHK(h, hipMemcpy(h->d_bfrowpack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
   h->have_nn = true;
   return MPPI_OK;
 }

@@ -200,6 +200,19 @@ hipError_t launch_rollout_bf_batch(const QuadBatchArgs &b, hipStream_t stream);
 hipError_t launch_dynamics_bf(const float *W, const float *states, const float *controls, float *ders, int n,
                               hipStream_t stream);
 
+// rollout_bf_row.hip: latency form of the basis-function model -- four dynamics waves (four rollouts each, a rollout's sixteen
+// (output, y-thread) cells on one DPP row) + pose, cost, control and noise wave per 16 rollouts; a.wpack = the per-lane image
+// (pack_bf_row_weights, abi_pack.hip): 16-B entry e of lane p = 4 j + y at float4 index e * 16 + p; slot m of a lane is basis
+// function i = y + 4 m.  Entries 0, 1: the weights W[j][y + 4 m] (0 where i > 24) and, in the last word, the lane's marks;
+// 2, 3: the divisors c (1 for a plain basis function); 4, 5: RN(1 / c) in fp32
+constexpr int kBfRowSlots = 7, kBfRowPackEntries = 6;
+// marks, one bit per slot m each, shifted left by m: the basis function is its numerator (no quotient); it is 0 unless
+// u_x >= 0.1 (BasisShared::big); the slot exists (i <= 24).  kBfRowDouble: slot 3 is a double quotient (i = 13, 14)
+constexpr unsigned kBfRowPlain = 1u, kBfRowBigOnly = 1u << 8, kBfRowUsed = 1u << 16, kBfRowDouble = 1u << 24;
+int bf_row_pack_floats();
+hipError_t launch_rollout_bf_row(const RolloutArgs &a, hipStream_t stream);
+hipError_t launch_rollout_bf_row_batch(const QuadBatchArgs &b, hipStream_t stream);  // two instances: grid (groups, 2)
+
 // rollout_trace.hip: chosen rollouts of a finished solve replayed with their records (mppi_trace_rollouts) -- one wavefront per
 // rollout and one lane per neuron for ANY layer list (every neuron the reference's chain: costs bit-identical to the exact
 // forms), one lane per rollout for the basis-function model

@@ -48,6 +48,9 @@ extern "C" {
  *    controls and step costs; compatible additions, no kernel form or launch path changes). */
 /*    (still 5) + rollout variant "lds16", name "mfma16x16x4_lds_l<N>_w<W>": the throughput form of any layer list up to 128 wide;
  *    no new export.  "valu_lds" reads a parameter blob that does not fit the LDS from global memory instead of failing at its launch. */
+/*    (still 5) + rollout variant "bf_row", name "basis_funcs25_row8w": the basis-function model in the row form's group, the bits
+ *    of "bf3", by name only; with it the basis-function model has a gated form (mppi_arm, mppi_arm_batch, chained
+ *    mppi_control_ticks); no new export, the automatic choice does not change. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -193,7 +196,8 @@ int mppi_synchronize(mppi_handle *h);
  * (network model, same layer list and num_iters, all groups of 16 rollouts together at most one per CU: 2 x K=1920 on
  * 256 CUs; the forms that have a batched kernel: the four-wavefront form and the row forms for n <= 4, the automatic
  * "m44" form of 64-wide nets and "lds44" / "lds128" -- forced on every handle, the whole layer list equal -- for n == 2; the
- * basis-function model's three-wavefront form) the n solves cost TWO kernel launches in all, on a stream of the library
+ * basis-function model's three-wavefront form, or its "bf_row" form forced on both handles of a pair under the row forms' rule:
+ * 2 x K=1920 shares a launch, 2 x K=2560 does not) the n solves cost TWO kernel launches in all, on a stream of the library
  * shared by the device's handles; otherwise ("m44_chain", three m44 handles ...) this is n calls of
  * mppi_compute_control_async.  mppi_debug_launch_info tells which it was.  Either way every
  * handle's results are bit for bit those of its own mppi_compute_control, collected per handle with
@@ -205,8 +209,8 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
  * mppi_compute_control[_async] to supply the state -- that call does not launch, it writes its state, the host's U and hist into
  * the gate and opens it.  May be called with a solve pending (the armed one goes behind it) or idle.  MPPI_ERR_UNSUPPORTED
  * (nothing enqueued, handle unchanged) where the handle's form / configuration has no gated form: num_iters > 1, the
- * basis-function model, forms other than the row forms, the automatic m44 form and the automatic multi4-tree form with its
- * generator kernel, stage timing, capture, explicit noise.  Results are bit for bit those of the same calls without mppi_arm;
+ * basis-function model in any form but "bf_row", forms other than the row forms, the automatic m44 form, "lds44", "lds128", "bf_row"
+ * and the automatic multi4-tree form with its generator kernel, stage timing, capture, explicit noise.  Results are bit for bit those of the same calls without mppi_arm;
  * the slide stride between ticks may vary, and mppi_set_control_seq / _hist between arm and compute go through the gate.
  * Every call that changes what the armed solve would compute (model, cost, costmap, limits, seed, noise, variant, timing,
  * capture, mppi_rollout_only, mppi_control_ticks, the debug entries, mppi_destroy) calls it off first; the generator stream is
@@ -217,7 +221,7 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
 int mppi_arm(mppi_handle *h, double max_wait_s);
 /* The same for the solves of one mppi_compute_control_batch[_async](handles, states, n) call: the shared one-launch form where
  * the batch would use it and the form has a gated batched kernel (the row forms; two handles of the automatic "m44" form or of
- * "lds44" or of "lds128"), otherwise each handle armed on its own where it can be
+ * "lds44" or of "lds128" or of "bf_row"), otherwise each handle armed on its own where it can be
  * (MPPI_ERR_UNSUPPORTED if one could not be; the others stay armed).  Only a batch call with the same handles in the same order
  * opens the gates; any other call on one of them calls the whole armed launch off first. */
 int mppi_arm_batch(mppi_handle *const *handles, int n, double max_wait_s);
@@ -332,6 +336,11 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     "fused"            ..._fused_b256                     shapes without a multi form beyond two groups per CU (6-64x4-4, K > 8192)
  *     (generic)          valu_lds                           any other layer list: the only form for non-uniform nets
  *     basis functions    basis_funcs25_valu[_2w|_3w]        "fused" | "quad" | "bf3"
+ *   the basis-function model by name only (the bits of the three forms above)
+ *     "bf_row"           basis_funcs25_row8w                a rollout's 16 (output, y-thread) cells on one DPP row, four dynamics
+ *     wavefronts + pose, cost, control and noise wavefront per 16 rollouts (the row form's group); K a multiple of 16; the model's
+ *     only form with a gated kernel (mppi_arm, mppi_arm_batch for a pair, chained mppi_control_ticks); MPPI_ERR_UNSUPPORTED on a
+ *     network handle
  *   the reference's summation order in EVERY layer (bit-identical to one another; "mfma" = the table restricted to them)
  *     "row_exact" (= "row") valu_row8w_h32_l2, "m44_chain" mfma4x4x1_*_m44_tree (hidden layers one chain; output a butterfly),
  *     "oct[_gen]" ..._oct8w, "quad", "multi2[_gen]", "multi4[_gen]", "fused" = "block256" | "block64" ..._fused_b256 / _b64,
@@ -375,7 +384,7 @@ int mppi_debug_dynamics(mppi_handle *h, int n, const float *states, const float 
  * dynamics waves, 3 = cost wave, 4 = control wave; of the two-wavefront basis-function kernel: 1 = dynamics,
  * 2 = cost.  The solve must then end in MPPI_ERR_HIP ("hand-over failed"), never in finite costs.
  * wave = 0 and spin_budget = 0 restore normal operation.
- * Roles of the row form and of the oct form: 1 .. 4 = dynamics waves, 5 = pose, 6 = cost, 7 = control, 8 = noise wave.
+ * Roles of the row form, of "bf_row" and of the oct form: 1 .. 4 = dynamics waves, 5 = pose, 6 = cost, 7 = control, 8 = noise wave.
  * Roles of the multi form: 1 .. ND = dynamics waves, then the cost wave and the control wave (ND = 4: the pose
  * wave, the cost wave, the control wave).
  * Roles 32 .. 34: waits of the one-launch tail kernel of solves with more than 4096 rollouts -- the weights workgroup of
