@@ -14,12 +14,15 @@ from tests.helpers import noise_for
 
 SCENES = ["patchwork", "tilt_l2", "tilt_l1"]
 SHAPES = [(64, 17), (1984, 37), (1984, 100)]
-# the layer lists of tests/test_every_rollout_gpu.py (FORMS) and those the "lds44" and "lds128" forms are held on here
+# the layer lists of tests/test_every_rollout_gpu.py (FORMS) and those the "lds44", "lds128" and "lds16" forms are held on here
 NET_LAYERS = {"32x2": None, "32x4": [6, 32, 32, 32, 32, 4], "64x2": [6, 64, 64, 4], "64x4": [6, 64, 64, 64, 64, 4],
               "16-8": [6, 16, 8, 4], "5-7": [6, 5, 7, 4], "24": [6, 24, 4], "bf": None,
               "32x3": [6, 32, 32, 32, 4], "16-24": [6, 16, 24, 4], "64x6": [6, 64, 64, 64, 64, 64, 64, 4],
-              "128x2": [6, 128, 128, 4], "33-97-66": [6, 33, 97, 66, 4]}
+              "128x2": [6, 128, 128, 4], "33-97-66": [6, 33, 97, 66, 4], "65": [6, 65, 4], "128x3": [6, 128, 128, 128, 4]}
 LDS44_NETS, LDS128_NETS = ["32x3", "16-24", "64x6"], ["128x2", "33-97-66"]
+# "lds16": the 4-tile and the 8-tile instance, a layer narrower than a tile, half-full last tiles, odd tile counts (6-65-4: five,
+# a single tile behind two pairs), no middle layer, seven weight layers, the largest image
+LDS16_NETS = ["32x2", "5-7", "24", "16-24", "65", "33-97-66", "64x6", "128x2", "128x3"]
 
 
 @functools.lru_cache(maxsize=None)

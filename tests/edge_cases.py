@@ -159,6 +159,11 @@ SHARED_KS = (1984, 1920)
 OTHER_LAUNCH_CASES = [("border", p, net, 2 * MI355X_CUS * 16 + 64, 17, 0) for net in CAPACITY_NETS for p in CAPACITY_PARTS]
 OTHER_LAUNCH_CASES += [(scene, SHARED[scene][1][i], net, SHARED_KS[i], SHARED[scene][0], i) for scene in SHARED for net in SHARED_NETS
                        for i in (0, 1)]
+# the "bf_row" pair of the basis-function model, on the border only (the crawl's shared parts are network start speeds)
+OTHER_LAUNCH_CASES += [("border", SHARED["border"][1][i], "bf", SHARED_KS[i], SHARED["border"][0], i) for i in (0, 1)]
+# "lds16" at the K where its launcher's rule picks 512 threads (6-128-128-128-4: one workgroup per CU) and 1024 (6-64x6-4)
+LDS16_THREADS = (("128x3", 128, 512), ("64x6", 256, 1024))   # (net, rollouts per CU, threads per workgroup)
+OTHER_LAUNCH_CASES += [("border", p, net, per_cu * MI355X_CUS, 17, 0) for net, per_cu, threads in LDS16_THREADS for p in CAPACITY_PARTS]
 
 
 # ------------------------------------------------------------------------------------------- non-finite and huge start states

@@ -23,6 +23,7 @@ from tests import scenes as SC
 from tests.helpers import oracle_mode_for, rel_err
 from tests.scenes import TOL64, TOL_MODE
 from tests.test_every_rollout_gpu import FORMS, GROUPS_PER_CU, NET_LAYERS, _cus, _results, _solver, expected_name
+from tests.test_lds16_gpu import lds16_name
 from tests.test_lds44_gpu import lds44_name
 from tests.test_lds128_gpu import lds128_name
 
@@ -44,6 +45,8 @@ def _want(variant, net):
         return lds44_name(BC.NET_LAYERS[net])
     if variant == "lds128":
         return lds128_name(BC.NET_LAYERS[net])
+    if variant == "lds16":   # exact: the oracle's mode 1
+        return lds16_name(BC.NET_LAYERS[net] or [6, 32, 32, 4])
     return expected_name(variant, net)
 
 
@@ -83,7 +86,7 @@ def _solve(scene, net, K, T, variant):
 
 
 FORM_CASES = [(net, v) for net, vs in FORMS.items() for v in vs] + [(net, "lds44") for net in BC.LDS44_NETS] + \
-    [(net, "lds128") for net in BC.LDS128_NETS]
+    [(net, "lds128") for net in BC.LDS128_NETS] + [(net, "lds16") for net in BC.LDS16_NETS]
 
 
 @pytest.mark.parametrize("K,T", BC.SHAPES)
@@ -103,14 +106,19 @@ def test_beyond_the_resident_capacity_on_the_patchwork(net, variant):
     _hold("capacity", "patchwork", net, K, 17, _solve("patchwork", net, K, 17, variant), _want(variant, net))
 
 
+# net -> (the variant requested, the form that runs) of the armed solves
+ARMED = {"32x2": ("auto", "row_tree"), "64x2": ("auto", "m44"), "bf": ("bf_row", "bf_row")}
+
+
 @pytest.mark.parametrize("K,T", BC.SHAPES[1:])
-@pytest.mark.parametrize("net", ["32x2", "64x2"])
+@pytest.mark.parametrize("net", list(ARMED))
 @pytest.mark.parametrize("scene", BC.SCENES)
 def test_every_decided_rollout_of_an_armed_solve(scene, net, K, T):
-    """The automatic choice (at K = 1984 the row-tree form on the shipped list, "m44" on 6-64-64-4), armed (mppi_arm): the gated
-    solve draws its own noise, seeded to be the explicit noise."""
+    """The automatic choice (at K = 1984 the row-tree form on the shipped list, "m44" on 6-64-64-4) and, by name, the "bf_row" form
+    of the basis-function model (its automatic choice, "bf3", has no gated kernel), armed (mppi_arm): the gated solve draws its
+    own noise, seeded to be the explicit noise."""
     cfg, U0, eps = BC.problem(scene, net, K, T)
-    sol = _solver(cfg, "auto", U0, None, seed=BC.noise_seed(T))
+    sol = _solver(cfg, ARMED[net][0], U0, None, seed=BC.noise_seed(T))
     try:
         sol.arm(0.1)
         assert sol.is_armed()
@@ -119,7 +127,7 @@ def test_every_decided_rollout_of_an_armed_solve(scene, net, K, T):
         got = _results(sol)
     finally:
         sol.close()
-    _hold("armed", scene, net, K, T, got, expected_name({"32x2": "row_tree", "64x2": "m44"}[net], net))
+    _hold("armed", scene, net, K, T, got, expected_name(ARMED[net][1], net))
 
 
 @pytest.mark.parametrize("armed", [False, True], ids=["plain", "armed"])

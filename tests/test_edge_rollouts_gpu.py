@@ -10,7 +10,8 @@ the host which rollouts are decided, before any GPU result is looked at; tests/t
 bar rejects ten mutants of the clamp, the speed guard, the basis functions' switch and the cap.
   (a) every form x its layer lists x the four scenes x (K, T) = (64, 17), (1984, 37), the border also (1984, 100); a case runs
       every PART of its scene (six borders and corners, three start speeds, three cap settings, four headings), a solve each;
-  (b) beyond the resident capacity, armed, and the shared two-handle launch, on the border and the crawl;
+  (b) beyond the resident capacity, every workgroup size of "lds16", armed, and the shared two-handle launch, on the border and
+      the crawl;
   (c) non-finite and huge start states for every form: capped rollouts exactly (float)1e12, the others held to the oracle, U to
       ref64's tail stages fed with the GPU's own costs and V;
   (d) mppi_trace_rollouts on 16 rollouts chosen from ref64's record.
@@ -20,10 +21,12 @@ import pytest
 
 from autorally_amd import capi
 from tests import edge_cases as EC
+from tests import ref64 as R
 from tests import trace_cases as TC
 from tests.helpers import oracle_mode_for
-from tests.test_branch_rollouts_gpu import FORM_CASES, _want
+from tests.test_branch_rollouts_gpu import ARMED, FORM_CASES, _want
 from tests.test_every_rollout_gpu import GROUPS_PER_CU, _cus, _results, _solver, expected_name
+from tests.test_lds16_pack import packer, workgroup_threads  # noqa: F401 (packer: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -69,15 +72,37 @@ def test_beyond_the_resident_capacity_on_the_border(net, variant):
         EC.hold("capacity", "border", part, net, K, 17, _solve(cfg, U0, eps, variant), _want(variant, net))
 
 
-@pytest.mark.parametrize("net", ["32x2", "64x2"])
+@pytest.mark.parametrize("net,per_cu,threads", EC.LDS16_THREADS)
+def test_every_workgroup_size_of_lds16_on_the_border(net, per_cu, threads, packer):  # noqa: F811
+    """The "lds16" form where its launcher's rule picks workgroups of 512 threads (6-128-128-128-4 at 128 rollouts per CU: one
+    workgroup per CU) and of 1024 (6-64x6-4 at 256 per CU), at the two corners; K > 4096, so the streaming tail runs behind the
+    rollouts: U within 2e-6 of ref64's weighting, reduction and smoothing fed with the solve's own costs and V, as
+    edge_cases.hold_start_state holds it."""
+    cus = _cus()
+    K, T, layers = per_cu * cus, 17, EC.NET_LAYERS[net]
+    # the library's own rule (lds16_block_threads, what the launcher calls with the handle's CU count) on this device's CUs
+    assert packer(layers, launch=(K, cus))[3] == workgroup_threads(layers, K, cus) == threads, (packer(layers, launch=(K, cus)), threads)
+    for part in EC.CAPACITY_PARTS:
+        cfg, U0, eps = EC.problem("border", part, net, K, T)
+        got = _solve(cfg, U0, eps, "lds16", hist=EC.START_HIST)
+        EC.hold("threads%d" % threads, "border", part, net, K, T, got, _want("lds16", net))
+        r = R.Ref64(cfg)
+        w, beta, eta, tc = r.weights(got["costs"])
+        dU = float(np.max(np.abs(r.savgol(r.weighted_reduction(w, eta, got["V"]), EC.START_HIST) - got["U"])))
+        print("EDGE_ROLLOUT threads%d border/%s net=%s K=%d: |dU| %.2e against ref64's tail stages (bar 2e-6)" % (threads, part, net, K, dU))
+        assert np.all(np.isfinite(got["U"])) and dU <= 2e-6, dU
+
+
+@pytest.mark.parametrize("net", list(ARMED))
 @pytest.mark.parametrize("scene", ["border", "crawl"])
 def test_every_decided_rollout_of_an_armed_solve(scene, net):
-    """The automatic choice (at K = 1984 the row-tree form on the shipped list, "m44" on 6-64-64-4), armed (mppi_arm): the gated
-    solve draws its own noise, seeded to be the explicit noise."""
+    """The automatic choice (at K = 1984 the row-tree form on the shipped list, "m44" on 6-64-64-4) and, by name, the "bf_row" form
+    of the basis-function model (its automatic choice has no gated kernel), armed (mppi_arm): the gated solve draws its own
+    noise, seeded to be the explicit noise."""
     K, T = EC.SHAPES[1]
     for part in EC.parts(scene, net):
         cfg, U0, eps = EC.problem(scene, part, net, K, T)
-        sol = _solver(cfg, "auto", U0, None, seed=EC.noise_seed(T))
+        sol = _solver(cfg, ARMED[net][0], U0, None, seed=EC.noise_seed(T))
         try:
             sol.arm(0.1)
             assert sol.is_armed()
@@ -86,16 +111,29 @@ def test_every_decided_rollout_of_an_armed_solve(scene, net):
             got = _results(sol)
         finally:
             sol.close()
-        EC.hold("armed", scene, part, net, K, T, got, expected_name({"32x2": "row_tree", "64x2": "m44"}[net], net))
+        EC.hold("armed", scene, part, net, K, T, got, expected_name(ARMED[net][1], net))
+
+
+# the basis-function pair on the border only: the crawl's shared parts are network start speeds
+SHARED_CASES = [(scene, net, v) for scene in EC.SHARED for net, v in (("64x2", "auto"), ("32x3", "lds44"), ("128x2", "lds128"))] + \
+    [("border", "bf", "bf_row")]
+
+
+def _launched_together(variant, Ks):
+    """What batch_together (csrc/abi_solve.hip) decides for the pair.  The network pairs here: one launch.  The "bf_row" pair
+    falls under the row forms' rule -- every dynamics wave of every group a SIMD of its own, four waves per 16 rollouts against four
+    SIMDs per CU: 1984 + 1920 rollouts are 976 waves, one launch from 244 CUs on (the MI355X has 256); on a smaller device the
+    handles are solved, and armed, one by one."""
+    return variant != "bf_row" or sum(4 * (K // 16) for K in Ks) <= 4 * _cus()
 
 
 @pytest.mark.parametrize("armed", [False, True], ids=["plain", "armed"])
-@pytest.mark.parametrize("net,variant", [("64x2", "auto"), ("32x3", "lds44"), ("128x2", "lds128")])
-@pytest.mark.parametrize("scene", list(EC.SHARED))
+@pytest.mark.parametrize("scene,net,variant", SHARED_CASES)
 def test_every_decided_rollout_of_a_shared_launch(scene, net, variant, armed):
-    """mppi_compute_control_batch on two handles of one layer list, K = 1984 and 1920, the second handle on another part of the
-    scene (the opposite corner, a negative start speed) with other cost parameters: ONE rollout launch, gated after
-    mppi_arm_batch; each instance held to the bar."""
+    """mppi_compute_control_batch on two handles of one layer list (or of the basis-function model), K = 1984 and 1920, the
+    second handle on another part of the scene (the opposite corner, a negative start speed) with other cost parameters: ONE
+    rollout launch (mppi_debug_launch_info reports what _launched_together says), gated after mppi_arm_batch; each instance
+    held to the bar."""
     T, parts = EC.SHARED[scene]
     sols, states = [], []
     try:
@@ -109,7 +147,7 @@ def test_every_decided_rollout_of_a_shared_launch(scene, net, variant, armed):
         capi.compute_control_batch(sols, states)
         assert not any(s.is_armed() for s in sols)
         infos = [s.debug_launch_info() for s in sols]
-        assert infos == [(2, 1 if armed else 0)] * 2, infos
+        assert infos == [(2 if _launched_together(variant, EC.SHARED_KS) else 1, 1 if armed else 0)] * 2, infos
         outs = [_results(s) for s in sols]
     finally:
         for s in sols:
@@ -121,7 +159,7 @@ def test_every_decided_rollout_of_a_shared_launch(scene, net, variant, armed):
 
 # ---------------------------------------------------------------------------------------------------------------- (c)
 # "lds44" and "lds128" on a list whose widths are no multiples of four: the padded k steps of a layer read lanes that hold no neuron
-RAGGED_CASES = [("5-7", "lds44"), ("5-7", "lds128")]
+RAGGED_CASES = [("5-7", "lds44"), ("5-7", "lds128")]   # ("5-7", "lds16") and its other ragged lists are among FORM_CASES
 
 
 @pytest.mark.parametrize("K", EC.START_KS)
@@ -136,7 +174,7 @@ def test_non_finite_and_huge_start_states_for_every_form(net, variant, K):
 
 
 # ---------------------------------------------------------------------------------------------------------------- (d)
-TRACE_FORMS = [("32x2", "row_exact"), ("64x2", "oct"), ("64x2", "m44"), ("32x3", "lds44"), ("bf", "bf3")]
+TRACE_FORMS = [("32x2", "row_exact"), ("64x2", "oct"), ("64x2", "m44"), ("32x3", "lds44"), ("bf", "bf3"), ("33-97-66", "lds16")]
 N_TRACED = 16
 
 

@@ -21,10 +21,12 @@ import pytest
 from autorally_amd import capi
 from autorally_amd import params as P
 from oracle import oracle as O
+from tests import branch_cases as BC
 from tests import ref64 as R
 from tests import scenes as SC
 from tests.helpers import noise_for, oracle_mode_for, rel_err, solve_with_iterations
 from tests.scenes import TOL64, TOL_MODE
+from tests.test_lds16_gpu import lds16_name
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +34,7 @@ U32 = np.uint32
 SHIPPED, N32X4, N64X2, N64X4 = "32x2", "32x4", "64x2", "64x4"
 NET_LAYERS = {SHIPPED: None, N32X4: [6, 32, 32, 32, 32, 4], N64X2: [6, 64, 64, 4], N64X4: [6, 64, 64, 64, 64, 4],
               "16-8": [6, 16, 8, 4], "5-7": [6, 5, 7, 4], "24": [6, 24, 4], "bf": None}
+NET_LAYERS.update({n: BC.NET_LAYERS[n] for n in ("65", "128x3")})   # the permutation test (b) of the "lds16" form
 NET_HN = {SHIPPED: (32, 2), N32X4: (32, 4), N64X2: (64, 2), N64X4: (64, 4)}
 _MULTI = ["multi2", "multi2_gen", "multi4", "multi4_gen", "multi4_tree", "multi4_tree_gen"]
 _MFMA = ["quad", "block64", "fused"]
@@ -41,7 +44,7 @@ FORMS = {
     N64X2: ["m44", "m44_chain", "row64_r16", "oct", "oct_gen"] + _MFMA + _MULTI + ["valu", "valu_lds"],
     N64X4: ["m44", "m44_chain", "row64_r16", "oct", "oct_gen"] + _MFMA + ["valu", "valu_lds"],
     "16-8": ["valu_lds"], "5-7": ["valu_lds"], "24": ["valu_lds"],
-    "bf": ["bf3", "quad", "fused"],
+    "bf": ["bf3", "bf_row", "quad", "fused"],
 }
 # groups of 16 rollouts per CU a form keeps resident (csrc/abi_forms.hip: kFormRules, max_groups_per_cu)
 GROUPS_PER_CU = {"row_exact": 2, "row_tree": 2, "m44": 2, "m44_chain": 2, "oct": 2, "oct_gen": 2, "quad": 1, "multi2": 2,
@@ -52,7 +55,10 @@ LONG_T = 300
 def expected_name(variant, net):
     """What mppi_rollout_variant names the form a variant request selects."""
     if net == "bf":
-        return {"bf3": "basis_funcs25_valu_3w", "quad": "basis_funcs25_valu_2w", "fused": "basis_funcs25_valu"}[variant]
+        return {"bf3": "basis_funcs25_valu_3w", "bf_row": "basis_funcs25_row8w", "quad": "basis_funcs25_valu_2w",
+                "fused": "basis_funcs25_valu"}[variant]
+    if variant == "lds16":
+        return lds16_name(NET_LAYERS[net] or [6, 32, 32, 4])
     if net not in NET_HN:
         return "valu_lds"
     if variant in ("valu", "valu_lds"):
@@ -187,10 +193,11 @@ def _solve(net, K, T, variant):
 # ---------------------------------------------------------------------------------------------------------------- (a)
 def _capacity(variant, net):
     """Rollouts the form keeps resident at once: CUs x groups per CU x 16 where the selection table limits the form; the
-    basis-function forms one wave per SIMD (abi_forms.hip form_of: three waves per 64 rollouts, two); forms without a limit at
-    the largest capacity of the table, two groups per CU."""
+    basis-function forms one wave per SIMD (abi_forms.hip form_of: three waves per 64 rollouts, two) -- but "bf_row", the row
+    form's group of 16 rollouts, of which two per CU stay resident, as of the row forms; forms without a limit at
+    the largest capacity of the table, two groups per CU.  Every basis-function form is named: a new one has to say its rule."""
     if net == "bf":
-        return {"bf3": (4 * _cus() // 3) * 64, "quad": 4 * _cus() * 64}.get(variant, 2 * _cus() * 16)
+        return {"bf3": (4 * _cus() // 3) * 64, "quad": 4 * _cus() * 64, "bf_row": 2 * _cus() * 16, "fused": 2 * _cus() * 16}[variant]
     return GROUPS_PER_CU.get(variant, 2) * _cus() * 16
 
 
@@ -250,6 +257,9 @@ def _perm_in_classes(K, how, rng):
 
 
 B_FORMS = [(net, v) for net, vs in FORMS.items() if net in (SHIPPED, N64X2, N64X4, "5-7", "bf") for v in vs]
+# "lds16": at K = 1984 a workgroup of 256 threads holds four waves and the last workgroup is three-quarters full -- a rollout that
+# reads another wave's operand shows here; a list narrower than a tile, an odd tile count, the 8-tile instance on its largest image
+B_FORMS += [("5-7", "lds16"), ("65", "lds16"), ("128x3", "lds16")]
 
 
 @pytest.mark.parametrize("net,variant", B_FORMS)
