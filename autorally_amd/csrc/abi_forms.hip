@@ -85,6 +85,7 @@ Form form_of(const mppi_handle *h)
   if (h->forced == Form::Lds44) return Form::Lds44;  // by name only, for every layer list it serves (the standard shapes too)
   if (h->forced == Form::Lds128) return Form::Lds128;  // by name only, as lds44
   if (h->forced == Form::Lds16) return Form::Lds16;    // by name only, as lds44
+  if (h->forced == Form::Glb16) return Form::Glb16;    // by name only, as lds44
   if (!use_mfma(h)) return use_valu_reg(h) ? Form::ValuReg : Form::ValuLds;
   if (h->forced != Form::Auto) return h->forced;
   const int groups = h->K / kRolloutsPerWave, cus = h->num_simds / 4;
@@ -171,6 +172,12 @@ const char *mppi_rollout_variant(const mppi_handle *h)
       snprintf(buf, sizeof(buf), "mfma16x16x4_lds_l%d_w%d", h->net.n_layers - 2, wmax);
       break;
     }
+    case Form::Glb16: {
+      int wmax = 0;  // the widest hidden layer
+      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
+      snprintf(buf, sizeof(buf), "mfma16x16x4_glb_l%d_w%d", h->net.n_layers - 2, wmax);
+      break;
+    }
     case Form::Oct: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_oct8w%s", h->hidden, h->n_hidden, gen); break;
     case Form::Quad: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_quad4w", h->hidden, h->n_hidden); break;
     case Form::Fused256: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_fused_b256", h->hidden, h->n_hidden); break;
@@ -244,6 +251,22 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
     }
     if ((rc = need(h->d_lds16pack != nullptr, "lds16 form: this handle has no image"))) return rc;
     h->forced = Form::Lds16;
+  }
+  else if (strncmp(name, "glb16", 5) == 0) {  // lds16's wave for every layer list up to 256 wide; "glb16_r<N>": at most N stream blocks resident
+    int cap = -1;
+    if (name[5] != 0) {
+      const char *p = name + 7;
+      if (strncmp(name + 5, "_r", 2) != 0 || *p == 0 || strlen(p) > 9) return fail(h, MPPI_ERR_INVALID, "unknown variant");
+      for (const char *q = p; *q; q++)
+        if (*q < '0' || *q > '9') return fail(h, MPPI_ERR_INVALID, "unknown variant");
+      cap = atoi(p);
+    }
+    if ((rc = need(!h->basis, "glb16 is a form of the network model"))) return rc;
+    if ((rc = need(glb16_supported(h->net), "glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer"))) return rc;
+    if ((rc = need(h->K % 64 == 0, "glb16 form needs K to be a multiple of 64"))) return rc;
+    if (!h->d_glb16pack && h->have_nn && (rc = upload_glb16_image(h))) return rc;  // without parameters yet: mppi_set_nn_params builds it
+    h->glb16_cap = cap;
+    h->forced = Form::Glb16;
   }
   else if (strcmp(name, "row64") == 0 || strcmp(name, "row64_r16") == 0) {  // the vector-ALU arm of the 64-wide A/B
     if ((rc = need(h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden), "row64 form exists for 6-64x2-4 and 6-64x4-4"))) return rc;

@@ -333,11 +333,10 @@ std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const Ne
 //            for tile m = 2 P + h of a pair, and (MT_j - 1) MT_in + mi for an odd last tile (MT_in = MT_(j-1) input tiles)
 //   then kLds16Ahead = 2 blocks the kernel's read-ahead may touch.
 // Every entry without a weight (a neuron or an input that does not exist) is 0.
-std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const NetDesc &net)
+// pack_mfma16_image: the image of descriptor d (lds16_net_of / glb16_net_of: up to 8 / 16 tiles per layer) in `floats` floats
+static std::vector<float> pack_mfma16_image(const std::vector<float> &theta, const NetDesc &net, const Lds16Net &d, size_t floats)
 {
-  std::vector<float> out((size_t)lds16_pack_floats(net), 0.0f);
-  if (out.empty()) return out;
-  const Lds16Net d = lds16_net_of(net);
+  std::vector<float> out(floats, 0.0f);
   const float *p = theta.data();
   for (int j = 0; j < d.n_w; j++) {
     const int nin = net.layers[j], nout = net.layers[j + 1];
@@ -378,6 +377,33 @@ std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const Net
     p += (size_t)nout * nin + nout;
   }
   return out;
+}
+std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  const size_t floats = (size_t)lds16_pack_floats(net);
+  return floats ? pack_mfma16_image(theta, net, lds16_net_of(net), floats) : std::vector<float>();
+}
+// Image of rollout_glb16.hip, any layer list with hidden widths <= 256: the layout above with up to 16 tiles per layer and
+// kGlb16Ahead blocks of zeros behind the stream
+std::vector<float> pack_glb16_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  const size_t floats = (size_t)glb16_pack_floats(net);
+  return floats ? pack_mfma16_image(theta, net, glb16_net_of(net), floats) : std::vector<float>();
+}
+// the device image of a handle that asked for "glb16": allocated at the first call, rebuilt from h->theta at every call
+int upload_glb16_image(mppi_handle *h)
+{
+  const std::vector<float> pk = pack_glb16_weights(h->theta, h->net);
+  if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, "glb16 image size");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (!h->d_glb16pack) {
+    h->glb16_bytes = pk.size() * sizeof(float);
+    HIPCHK(h, hipMalloc(&h->d_glb16pack, h->glb16_bytes));
+  }
+  if (pk.size() * sizeof(float) != h->glb16_bytes) return fail(h, MPPI_ERR_INVALID, "glb16 image size");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(h->d_glb16pack, pk.data(), h->glb16_bytes, hipMemcpyHostToDevice));
+  return MPPI_OK;
 }
 
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)

@@ -59,7 +59,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.costs = h->d_costs;
   const Form f = form_of(h);
   a.wpack = f == Form::BfRow ? h->d_bfrowpack : form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
-            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : f == Form::Lds16 ? h->d_lds16pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
+            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : f == Form::Lds16 ? h->d_lds16pack : f == Form::Glb16 ? h->d_glb16pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
   a.inv_t = h->d_invt;
   a.K = h->K;
   a.T = h->T;
@@ -128,6 +128,7 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
     case Form::Lds44: e = launch_rollout_lds44(h->net, a, h->stream); break;
     case Form::Lds128: e = launch_rollout_lds128(h->net, a, h->stream); break;
     case Form::Lds16: e = launch_rollout_lds16(h->net, a, h->num_simds / 4, h->stream); break;
+    case Form::Glb16: e = launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, h->stream); break;
     case Form::Row64R16: e = launch_rollout_row64(h->hidden, h->n_hidden, a, 16, h->stream); break;
     case Form::Row: case Form::RowTree: e = launch_rollout_row(h->hidden, h->n_hidden, a, f == Form::RowTree, h->stream); break;
     case Form::Quad: case Form::Fused64: case Form::Fused256:

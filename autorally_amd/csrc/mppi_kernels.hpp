@@ -193,6 +193,26 @@ size_t lds16_lds_limit();                     // the dynamic LDS a workgroup may
 int lds16_block_threads(const NetDesc &net, int K, int cus);
 hipError_t launch_rollout_lds16(const NetDesc &net, const RolloutArgs &a, int cus, hipStream_t stream);  // cus: the device's CUs (the handle's)
 
+// rollout_glb16.hip: lds16's wave for EVERY layer list 6 -> hidden widths 1..256 -> 4 (3 <= n_layers <= 8): the image is lds16's
+// with up to 16 tiles per layer; its head (biases + layer 0) and the first R blocks of its stream are resident in LDS, the other
+// blocks are read from the image in global memory; a.wpack = pack_glb16_weights (abi_pack.hip).  cap: the cap on R given by
+// name ("glb16_r<N>"), < 0 for none
+#ifndef MPPI_GLB16_AHEAD
+#define MPPI_GLB16_AHEAD 2
+#endif
+constexpr int kGlb16Ahead = MPPI_GLB16_AHEAD;  // blocks requested ahead of their use, and blocks of zeros behind the stream (2 or 4)
+Lds16Net glb16_net_of(const NetDesc &net);     // of a list glb16_supported accepts
+bool glb16_supported(const NetDesc &net);
+int glb16_pack_floats(const NetDesc &net);
+size_t glb16_head_bytes(const NetDesc &net);             // biases + layer 0: always resident
+int glb16_stream_blocks(const NetDesc &net);             // 1 KB blocks behind the head, the zero blocks included
+int glb16_resident_blocks(const NetDesc &net, int cap);  // R = min(stream blocks, floor((limit - head) / 1 KB), cap)
+size_t glb16_lds_bytes(const NetDesc &net, int cap);     // a workgroup's dynamic LDS: head + R blocks
+size_t glb16_lds_limit();
+// threads per workgroup for K rollouts on a device of `cus` CUs: the smaller of 256 / 512 with every workgroup resident at once, else 512
+int glb16_block_threads(const NetDesc &net, int K, int cus, int cap);
+hipError_t launch_rollout_glb16(const NetDesc &net, const RolloutArgs &a, int cus, int cap, hipStream_t stream);
+
 // rollout_bf.hip (GeneralizedLinear basis-function dynamics, W[4][25] in a.wpack)
 hipError_t launch_rollout_bf(const RolloutArgs &a, int waves, hipStream_t stream);  // waves per 64 rollouts: 1, 2, 3
 // several instances of the three-wave form in one launch (grid: groups of 64 rollouts x instances)

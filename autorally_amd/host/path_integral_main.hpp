@@ -36,7 +36,7 @@ template <class DYNAMICS_T, class MAKE_MODEL>
 int path_integral_main(int argc, char **argv, int default_rollouts, MAKE_MODEL make_model)
 {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s <launch.xml> [--rollouts K] [--layers 6-32-32-4] [--max-iter N] [--no-sleep] [--solve-ahead] [--host-threads 1|2] [--rollout-variant auto|mfma|lds44|lds128|lds16|bf_row|...] "
+    fprintf(stderr, "usage: %s <launch.xml> [--rollouts K] [--layers 6-32-32-4] [--max-iter N] [--no-sleep] [--solve-ahead] [--host-threads 1|2] [--rollout-variant auto|mfma|lds44|lds128|lds16|glb16|bf_row|...] "
                     "[--device D] [--trace file] [--set key=value]\n", argv[0]);
     return 2;
   }

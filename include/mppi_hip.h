@@ -51,6 +51,9 @@ extern "C" {
 /*    (still 5) + rollout variant "bf_row", name "basis_funcs25_row8w": the basis-function model in the row form's group, the bits
  *    of "bf3", by name only; with it the basis-function model has a gated form (mppi_arm, mppi_arm_batch, chained
  *    mppi_control_ticks); no new export, the automatic choice does not change. */
+/*    (still 5) + rollout variant "glb16" (and "glb16_r<N>"), name "mfma16x16x4_glb_l<N>_w<W>": "lds16"'s wavefront for every layer list
+ *    mppi_create accepts (hidden widths up to 256, an image of any size): the front of the image resident in LDS, the rest read
+ *    from global memory; no new export. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -360,6 +363,13 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     128-wide layer does not); workgroups of 256 / 512 / 1024 threads, the smallest with every workgroup resident at once; by
  *     name only; NO gated form (mppi_arm answers MPPI_ERR_UNSUPPORTED) and no batched launch (a batch solves handle by handle);
  *     MPPI_ERR_UNSUPPORTED as "lds128"
+ *     "glb16" mfma16x16x4_glb_l<hidden layers>_w<widest hidden layer>: "lds16"'s wavefront for EVERY layer list of the network model
+ *     (3 <= n_layers <= 8, hidden widths 1..256): the same image with up to 16 tiles per layer; its head (biases, layer 0) and the
+ *     first R of its 1 KB blocks are copied into LDS, the other blocks are read from the image in global memory (it stays in L2),
+ *     R = what fits 160 KB; "glb16_r<N>" (N decimal, >= 0) caps R at N ("glb16_r0": every block from global memory; a test and
+ *     measurement knob, same bits for every N); by name only; the device image is built at this call and held only by handles
+ *     that asked for the form; NO gated form and no batched launch, as "lds16"; MPPI_ERR_UNSUPPORTED for the basis-function
+ *     model and a list without a hidden layer, MPPI_ERR_INVALID ("unknown variant") for a malformed suffix
  *   A/B arms and cross-checks (never chosen automatically)
  *     "valu" valu_reg_lds (lane = rollout, the independent implementation every parity test also runs; config 4's untuned
  *     vector-ALU reference), "valu_lds" (the generic kernel on a standard shape), "row64" = "row64_r16"
