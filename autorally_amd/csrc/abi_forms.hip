@@ -86,6 +86,7 @@ Form form_of(const mppi_handle *h)
   if (h->forced == Form::Lds128) return Form::Lds128;  // by name only, as lds44
   if (h->forced == Form::Lds16) return Form::Lds16;    // by name only, as lds44
   if (h->forced == Form::Glb16) return Form::Glb16;    // by name only, as lds44
+  if (h->forced == Form::Glb44) return Form::Glb44;    // by name only, as lds44
   if (!use_mfma(h)) return use_valu_reg(h) ? Form::ValuReg : Form::ValuLds;
   if (h->forced != Form::Auto) return h->forced;
   const int groups = h->K / kRolloutsPerWave, cus = h->num_simds / 4;
@@ -112,7 +113,7 @@ bool has_noise_wave(const mppi_handle *h)
 {
   switch (form_of(h)) {
     case Form::Bf3: case Form::Quad: case Form::Row: case Form::RowTree: case Form::Row64R16: case Form::M44: case Form::M44Chain:
-    case Form::Lds44: case Form::Lds128: case Form::BfRow:
+    case Form::Lds44: case Form::Lds128: case Form::Glb44: case Form::BfRow:
       return true;
     case Form::Oct: case Form::Multi2: case Form::Multi4: case Form::Multi4Tree:
       return !form_generator_noise(h);
@@ -176,6 +177,12 @@ const char *mppi_rollout_variant(const mppi_handle *h)
       int wmax = 0;  // the widest hidden layer
       for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
       snprintf(buf, sizeof(buf), "mfma16x16x4_glb_l%d_w%d", h->net.n_layers - 2, wmax);
+      break;
+    }
+    case Form::Glb44: {
+      int wmax = 0;  // the widest hidden layer
+      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
+      snprintf(buf, sizeof(buf), "mfma4x4x1_glb_l%d_w%d", h->net.n_layers - 2, wmax);
       break;
     }
     case Form::Oct: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_oct8w%s", h->hidden, h->n_hidden, gen); break;
@@ -267,6 +274,22 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
     if (!h->d_glb16pack && h->have_nn && (rc = upload_glb16_image(h))) return rc;  // without parameters yet: mppi_set_nn_params builds it
     h->glb16_cap = cap;
     h->forced = Form::Glb16;
+  }
+  else if (strncmp(name, "glb44", 5) == 0) {  // lds128's group for every layer list up to 256 wide; "glb44_r<N>": at most N stream quads resident
+    int cap = -1;
+    if (name[5] != 0) {
+      const char *p = name + 7;
+      if (strncmp(name + 5, "_r", 2) != 0 || *p == 0 || strlen(p) > 9) return fail(h, MPPI_ERR_INVALID, "unknown variant");
+      for (const char *q = p; *q; q++)
+        if (*q < '0' || *q > '9') return fail(h, MPPI_ERR_INVALID, "unknown variant");
+      cap = atoi(p);
+    }
+    if ((rc = need(!h->basis, "glb44 is a form of the network model"))) return rc;
+    if ((rc = need(glb44_supported(h->net), "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer"))) return rc;
+    if ((rc = need(h->K % kRolloutsPerWave == 0, "glb44 form needs K to be a multiple of 16"))) return rc;
+    if (!h->d_glb44pack && h->have_nn && (rc = upload_glb44_image(h))) return rc;  // without parameters yet: mppi_set_nn_params builds it
+    h->glb44_cap = cap;
+    h->forced = Form::Glb44;
   }
   else if (strcmp(name, "row64") == 0 || strcmp(name, "row64_r16") == 0) {  // the vector-ALU arm of the 64-wide A/B
     if ((rc = need(h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden), "row64 form exists for 6-64x2-4 and 6-64x4-4"))) return rc;

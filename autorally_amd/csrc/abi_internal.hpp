@@ -57,6 +57,9 @@ enum class Form : int {
                                     // v_mfma_f32_16x16x4, the A operands from an LDS image, the reference's order; by name only ("lds16")
   Glb16,                            // rollout_glb16.hip: lds16's wave for every layer list up to 256 wide: the head and the first R blocks of
                                     // the image resident in LDS, the other blocks read from global memory; by name only ("glb16", "glb16_r<N>")
+  Glb44,                            // rollout_glb44.hip: lds128's group for every layer list up to 256 wide: a layer as one to four halves, the head
+                                    // and the first R quads of the image resident in LDS, the other quads read from global memory; by name
+                                    // only ("glb44", "glb44_r<N>")
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
   BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
@@ -160,6 +163,9 @@ struct mppi_handle {
   float *d_glb16pack = nullptr;  // image of rollout_glb16.hip: only a handle that asked for "glb16" has one (built at that call)
   size_t glb16_bytes = 0;        // ... and its size
   int glb16_cap = -1;            // "glb16_r<N>": the cap on the resident stream blocks; -1: none
+  float *d_glb44pack = nullptr;  // image of rollout_glb44.hip: only a handle that asked for "glb44" has one (built at that call)
+  size_t glb44_bytes = 0;        // ... and its size
+  int glb44_cap = -1;            // "glb44_r<N>": the cap on the resident stream quads; -1: none
   float *d_tracepack = nullptr;  // network model: k-major image of rollout_trace.hip (every layer's W transposed)
   // mppi_trace_rollouts: the records of one chunk of trace_chunk rollouts -- states [c][T][7], controls [c][T][2], step costs
   // [c][T], costs [c], first_crash [c] (int) -- allocated with the handle (nothing is allocated or freed while armed); the
@@ -261,6 +267,8 @@ std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const mp
 std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 std::vector<float> pack_glb16_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int upload_glb16_image(mppi_handle *h);  // (re)builds d_glb16pack from h->theta (allocates it at the first call)
+std::vector<float> pack_glb44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
+int upload_glb44_image(mppi_handle *h);  // (re)builds d_glb44pack from h->theta (allocates it at the first call)
 std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
 int upload_rng_tables(mppi_handle *h);

@@ -406,6 +406,53 @@ int upload_glb16_image(mppi_handle *h)
   return MPPI_OK;
 }
 
+// Image of rollout_glb44.hip, any layer list with hidden widths <= 256, in 1 KB quads: float4 q of lane l at float4 index q * 64 + l.
+// First kGlb44BiasQuads quads: float h of quad j of lane l = bias of neuron 64 h + l of weight layer j (hidden layers: b x
+// kTanhScale, 0 where the neuron does not exist; output layer, float 0: b_out[l >> 4]).  Then per weight layer ceil(nin / 4) x H
+// quads, H = ceil(nout / 64) halves (1 for the output layer), interleaved in the order of their use: quad q' H + h of the layer is
+// (W[64 h + l][4 q'] .. W[64 h + l][4 q' + 3]), the output layer's row c at lane 16 c.  Then kGlb44Ahead quads of zeros.  Every entry
+// without a weight is 0.  Behind the bias quads the weights are pack_lds128_weights' float for float on a list that form serves.
+std::vector<float> pack_glb44_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  std::vector<float> out((size_t)glb44_pack_floats(net), 0.0f);
+  if (out.empty()) return out;
+  const int n_w = net.n_layers - 1;
+  const float *p = theta.data();
+  int q0 = kGlb44BiasQuads;
+  for (int j = 0; j < n_w; j++) {
+    const int nin = net.layers[j], nout = net.layers[j + 1];
+    const float *W = p, *B = p + (size_t)nout * nin;
+    const bool last = j == n_w - 1;
+    const int H = last ? 1 : (nout + 63) / 64;
+    for (int h = 0; h < H; h++)
+      for (int l = 0; l < 64; l++) {
+        auto at = [&](int q, int c) -> float & { return out[((size_t)q * 64 + l) * 4 + c]; };
+        const int n = last ? ((l & 15) == 0 ? (l >> 4) : -1) : (64 * h + l < nout ? 64 * h + l : -1);  // the neuron whose row lane l holds
+        at(j, h) = last ? B[l >> 4] : (n >= 0 ? B[n] * kTanhScale : 0.0f);
+        if (n >= 0)
+          for (int k = 0; k < nin; k++) at(q0 + (k >> 2) * H + h, k & 3) = W[(size_t)n * nin + k];
+      }
+    q0 += ((nin + 3) / 4) * H;
+    p += (size_t)nout * nin + nout;
+  }
+  return out;
+}
+// the device image of a handle that asked for "glb44": allocated at the first call, rebuilt from h->theta at every call
+int upload_glb44_image(mppi_handle *h)
+{
+  const std::vector<float> pk = pack_glb44_weights(h->theta, h->net);
+  if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, "glb44 image size");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (!h->d_glb44pack) {
+    h->glb44_bytes = pk.size() * sizeof(float);
+    HIPCHK(h, hipMalloc(&h->d_glb44pack, h->glb44_bytes));
+  }
+  if (pk.size() * sizeof(float) != h->glb44_bytes) return fail(h, MPPI_ERR_INVALID, "glb44 image size");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(h->d_glb44pack, pk.data(), h->glb44_bytes, hipMemcpyHostToDevice));
+  return MPPI_OK;
+}
+
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)
 {
   // base state: L'Ecuyer's default 12345 x 6, scrambled by the seed (DESIGN.md noise spec)

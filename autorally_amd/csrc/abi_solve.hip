@@ -59,7 +59,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.costs = h->d_costs;
   const Form f = form_of(h);
   a.wpack = f == Form::BfRow ? h->d_bfrowpack : form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
-            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : f == Form::Lds16 ? h->d_lds16pack : f == Form::Glb16 ? h->d_glb16pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
+            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : f == Form::Lds16 ? h->d_lds16pack : f == Form::Glb16 ? h->d_glb16pack : f == Form::Glb44 ? h->d_glb44pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
   a.inv_t = h->d_invt;
   a.K = h->K;
   a.T = h->T;
@@ -129,6 +129,7 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
     case Form::Lds128: e = launch_rollout_lds128(h->net, a, h->stream); break;
     case Form::Lds16: e = launch_rollout_lds16(h->net, a, h->num_simds / 4, h->stream); break;
     case Form::Glb16: e = launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, h->stream); break;
+    case Form::Glb44: e = launch_rollout_glb44(h->net, a, h->glb44_cap, h->stream); break;
     case Form::Row64R16: e = launch_rollout_row64(h->hidden, h->n_hidden, a, 16, h->stream); break;
     case Form::Row: case Form::RowTree: e = launch_rollout_row(h->hidden, h->n_hidden, a, f == Form::RowTree, h->stream); break;
     case Form::Quad: case Form::Fused64: case Form::Fused256:
@@ -585,7 +586,7 @@ int enqueue_solve(mppi_handle *h, const float *state)
 // d_in at the one it smooths into.
 
 // The forms that have a gated rollout and gain from it (one iteration, no stage events, no capture): 1: a latency form with
-// riders (the row forms, the automatic m44 form, the lds44 and lds128 forms, the basis-function model's bf_row form) and its in-kernel generator; 2: the automatic multi4-tree form with the
+// riders (the row forms, the automatic m44 form, the lds44, lds128 and glb44 forms, the basis-function model's bf_row form) and its in-kernel generator; 2: the automatic multi4-tree form with the
 // stand-alone generator kernel prefetched on a second stream; 0: none
 static int arm_kind(const mppi_handle *h)
 {
@@ -593,7 +594,7 @@ static int arm_kind(const mppi_handle *h)
   if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
         h->explicit_iters == 0 && (!h->basis || f == Form::BfRow) && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
     return 0;
-  if ((form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::BfRow) && has_noise_wave(h) && !h->prefetch_valid) return 1;
+  if ((form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44 || f == Form::BfRow) && has_noise_wave(h) && !h->prefetch_valid) return 1;
   // (where the generator kernel runs beside the rollout.  Where it runs behind it -- 32-wide nets at K = 65 536 -- the phase
   // between two rollouts is the generator's own 41 us whatever the launches cost: chained 0.3139, unchained 0.3131 ms)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;
@@ -822,6 +823,7 @@ static hipError_t launch_rollout_batch(mppi_handle *const *hs, int n, const Quad
                        : f == Form::M44   ? launch_rollout_m44_batch(h0->n_hidden, qb, S)
                        : f == Form::Lds44 ? launch_rollout_lds44_batch(h0->net, qb, S)
                        : f == Form::Lds128 ? launch_rollout_lds128_batch(h0->net, qb, S)
+                       : f == Form::Glb44 ? launch_rollout_glb44_batch(h0->net, qb, h0->glb44_cap, S)
                                           : launch_rollout_quad_batch(h0->hidden, h0->n_hidden, qb, S);
   if (e != hipSuccess) return e;
   for (int i = 0; i < n; i++) {
@@ -832,13 +834,13 @@ static hipError_t launch_rollout_batch(mppi_handle *const *hs, int n, const Quad
 }
 
 // mppi_arm_batch: one launch for the batch where mppi_compute_control_batch would use one and the form has a gated batched kernel
-// (the row forms; the pair of the automatic m44 form, of the lds44 form, of the lds128 form and of the bf_row form)
+// (the row forms; the pair of the automatic m44 form, of the lds44 form, of the lds128 form, of the glb44 form and of the bf_row form)
 static bool batch_together(mppi_handle *const *hs, int n);
 static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
 {
   mppi_handle *h0 = hs[0];
   const Form f0 = form_of(h0);
-  if (!(form_is_row(f0) || f0 == Form::M44 || f0 == Form::Lds44 || f0 == Form::Lds128 || f0 == Form::BfRow))
+  if (!(form_is_row(f0) || f0 == Form::M44 || f0 == Form::Lds44 || f0 == Form::Lds128 || f0 == Form::Glb44 || f0 == Form::BfRow))
     return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
   for (int i = 0; i < n; i++)
     if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");
@@ -893,16 +895,18 @@ static bool batch_together(mppi_handle *const *hs, int n)
     // network model: the four-wavefront form; basis-function model: its three-wavefront form (in-kernel generator)
     const Form f = form_of(h);
     // the pair of a tick only (their batched kernels exist for two instances): the automatic m44 form of one network shape; the
-    // lds44 / lds128 form (by name only: forced on every handle) of one WHOLE layer list -- one layer list and one image size
+    // lds44 / lds128 / glb44 form (by name only: forced on every handle) of one WHOLE layer list -- one layer list and one image size
     // serve the launch
-    const bool by_list = f == Form::Lds44 || f == Form::Lds128;
+    // (glb44: and one cap on the resident quads -- one dynamic-LDS size)
+    const bool by_list = f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44;
     const bool wide = f == Form::M44 || by_list;
     bool same_list = h->net.n_layers == h0->net.n_layers;
     for (int l = 0; l < h->net.n_layers && same_list; l++) same_list = h->net.layers[l] == h0->net.layers[l];
     // (... or the pair of its bf_row form, by name only: forced on both handles)
     const bool form_ok = h->basis ? (h0->basis && (f == Form::Bf3 || (f == Form::BfRow && n == 2)) && f == form_of(h0))
                                   : (!h0->basis && (f == Form::Quad || form_is_row(f) || (wide && n == 2)) && f == form_of(h0) &&
-                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden && (!by_list || same_list));
+                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden && (!by_list || same_list) &&
+                                     (f != Form::Glb44 || h->glb44_cap == h0->glb44_cap));
     // one kernel instance serves the whole batch: the instances must agree on what it is specialised for (affine / projective
     // costmap transform, control cost or none) -- a superset kernel would compute 0 * x where the single solve computes
     // nothing, which differs for a non-finite x; such a pair is solved one by one.

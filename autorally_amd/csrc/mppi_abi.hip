@@ -44,7 +44,7 @@ void free_all(mppi_handle *h)
 {
   if (!h) return;
   float *fp[] = {h->d_theta_s, h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
-                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_bfrowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_lds128pack, h->d_lds16pack, h->d_glb16pack, h->d_cap, h->d_tracepack, h->d_trace};
+                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_bfrowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_lds128pack, h->d_lds16pack, h->d_glb16pack, h->d_glb44pack, h->d_cap, h->d_tracepack, h->d_trace};
   for (float *p : fp)
     if (p) (void)hipFree(p);
   if (h->d_invt) (void)hipFree(h->d_invt);
@@ -401,6 +401,9 @@ int mppi_set_nn_params(mppi_handle *h, const float *theta, size_t n)
   }
   if (h->d_glb16pack || h->forced == Form::Glb16) {
     if (int rc = upload_glb16_image(h)) return rc;
+  }
+  if (h->d_glb44pack || h->forced == Form::Glb44) {
+    if (int rc = upload_glb44_image(h)) return rc;
   }
   {
     const std::vector<float> pk = pack_trace_weights(h->theta, h->net);

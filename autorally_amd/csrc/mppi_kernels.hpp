@@ -213,6 +213,31 @@ size_t glb16_lds_limit();
 int glb16_block_threads(const NetDesc &net, int K, int cus, int cap);
 hipError_t launch_rollout_glb16(const NetDesc &net, const RolloutArgs &a, int cus, int cap, hipStream_t stream);
 
+// rollout_glb44.hip: lds128's group (m44_group.hpp) for EVERY layer list 6 -> hidden widths 1..256 -> 4 (3 <= n_layers <= 8): a hidden
+// layer is one to four halves of 64 neurons with an accumulator each, its inputs one to four transposed activation sets; the
+// image is lds128's layout in 1 KB quads with four halves per layer; its head (bias quads + layer 0) and the first R quads of the
+// stream behind it are resident in LDS, the other quads are read from the image in global memory; a.wpack = pack_glb44_weights
+// (abi_pack.hip).  cap: the cap on R given by name ("glb44_r<N>"), < 0 for none
+#ifndef MPPI_GLB44_AHEAD
+#define MPPI_GLB44_AHEAD 8
+#endif
+#ifndef MPPI_GLB44_AHEAD_LDS
+#define MPPI_GLB44_AHEAD_LDS 3
+#endif
+constexpr int kGlb44Ahead = MPPI_GLB44_AHEAD;         // streamed quads requested ahead of their use, and quads of zeros behind the stream
+constexpr int kGlb44AheadLds = MPPI_GLB44_AHEAD_LDS;  // resident quads requested ahead of their use (kLds44Ahead)
+constexpr int kGlb44BiasQuads = 7;             // float4 per lane in front of the weights: quad j, float h = bias of half h of weight layer j
+bool glb44_supported(const NetDesc &net);
+int glb44_pack_floats(const NetDesc &net);
+size_t glb44_head_bytes(const NetDesc &net);             // bias quads + layer 0: always resident
+int glb44_stream_quads(const NetDesc &net);              // 1 KB quads behind the head, the zero quads included
+int glb44_resident_quads(const NetDesc &net, int cap);   // R = min(stream quads, floor((limit - shared state - head) / 1 KB), cap)
+size_t glb44_lds_bytes(const NetDesc &net, int cap);     // a group's dynamic LDS: shared state + head + R quads
+size_t glb44_lds_limit();
+hipError_t launch_rollout_glb44(const NetDesc &net, const RolloutArgs &a, int cap, hipStream_t stream);
+// two instances of the SAME layer list and cap in one launch: b.n == 2, grid (groups of the larger instance, 2)
+hipError_t launch_rollout_glb44_batch(const NetDesc &net, const QuadBatchArgs &b, int cap, hipStream_t stream);
+
 // rollout_bf.hip (GeneralizedLinear basis-function dynamics, W[4][25] in a.wpack)
 hipError_t launch_rollout_bf(const RolloutArgs &a, int waves, hipStream_t stream);  // waves per 64 rollouts: 1, 2, 3
 // several instances of the three-wave form in one launch (grid: groups of 64 rollouts x instances)

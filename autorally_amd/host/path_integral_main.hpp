@@ -36,7 +36,7 @@ template <class DYNAMICS_T, class MAKE_MODEL>
 int path_integral_main(int argc, char **argv, int default_rollouts, MAKE_MODEL make_model)
 {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s <launch.xml> [--rollouts K] [--layers 6-32-32-4] [--max-iter N] [--no-sleep] [--solve-ahead] [--host-threads 1|2] [--rollout-variant auto|mfma|lds44|lds128|lds16|glb16|bf_row|...] "
+    fprintf(stderr, "usage: %s <launch.xml> [--rollouts K] [--layers 6-32-32-4] [--max-iter N] [--no-sleep] [--solve-ahead] [--host-threads 1|2] [--rollout-variant auto|mfma|lds44|lds128|lds16|glb16|glb44|bf_row|...] "
                     "[--device D] [--trace file] [--set key=value]\n", argv[0]);
     return 2;
   }
@@ -62,7 +62,8 @@ int path_integral_main(int argc, char **argv, int default_rollouts, MAKE_MODEL m
   // --rollout-variant NAME: mppi_set_rollout_variant on both controllers ("mfma": the reference's summation order in every layer;
   // "lds44": the latency form of any --layers list with hidden widths up to 64, e.g. --layers 6-32-32-32-4; "lds128": the same up
   // to 128 wide, e.g. --layers 6-128-128-4; "lds16": the throughput form of those lists, for --rollouts beyond two 16-rollout
-  // groups per CU, and the only fast form of 6-128-128-128-4; "bf_row": path_integral_bf's form with a gated kernel -- with it
+  // groups per CU; "glb16": that wavefront for every --layers list (hidden widths up to 256); "glb44": the latency form of every
+  // such list, with a gated kernel and a pair launch -- with it --solve-ahead arms the next tick's pair in one launch; "bf_row": path_integral_bf's form with a gated kernel -- with it
   // --solve-ahead arms the next tick's pair, handle by handle at the default 2 x 2560 rollouts)
   const char *rollout_variant = nullptr;
   for (int i = 2; i < argc; i++) {

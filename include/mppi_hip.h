@@ -54,6 +54,10 @@ extern "C" {
 /*    (still 5) + rollout variant "glb16" (and "glb16_r<N>"), name "mfma16x16x4_glb_l<N>_w<W>": "lds16"'s wavefront for every layer list
  *    mppi_create accepts (hidden widths up to 256, an image of any size): the front of the image resident in LDS, the rest read
  *    from global memory; no new export. */
+/*    (still 5) + rollout variant "glb44" (and "glb44_r<N>"), name "mfma4x4x1_glb_l<N>_w<W>": "lds128"'s group (the latency form, with
+ *    mppi_arm, mppi_arm_batch, chained mppi_control_ticks and the pair in one launch) for every layer list mppi_create accepts
+ *    (hidden widths up to 256, an image of any size): the front of the image resident in LDS, the rest read from global memory;
+ *    no new export. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -198,7 +202,7 @@ int mppi_synchronize(mppi_handle *h);
  * -- states is [n][7], handles[i] solves from states + 7 i.  Where the handles' rollout kernels can share a launch
  * (network model, same layer list and num_iters, all groups of 16 rollouts together at most one per CU: 2 x K=1920 on
  * 256 CUs; the forms that have a batched kernel: the four-wavefront form and the row forms for n <= 4, the automatic
- * "m44" form of 64-wide nets and "lds44" / "lds128" -- forced on every handle, the whole layer list equal -- for n == 2; the
+ * "m44" form of 64-wide nets and "lds44" / "lds128" / "glb44" -- forced on every handle, the whole layer list (and "glb44"'s cap) equal -- for n == 2; the
  * basis-function model's three-wavefront form, or its "bf_row" form forced on both handles of a pair under the row forms' rule:
  * 2 x K=1920 shares a launch, 2 x K=2560 does not) the n solves cost TWO kernel launches in all, on a stream of the library
  * shared by the device's handles; otherwise ("m44_chain", three m44 handles ...) this is n calls of
@@ -212,7 +216,7 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
  * mppi_compute_control[_async] to supply the state -- that call does not launch, it writes its state, the host's U and hist into
  * the gate and opens it.  May be called with a solve pending (the armed one goes behind it) or idle.  MPPI_ERR_UNSUPPORTED
  * (nothing enqueued, handle unchanged) where the handle's form / configuration has no gated form: num_iters > 1, the
- * basis-function model in any form but "bf_row", forms other than the row forms, the automatic m44 form, "lds44", "lds128", "bf_row"
+ * basis-function model in any form but "bf_row", forms other than the row forms, the automatic m44 form, "lds44", "lds128", "glb44", "bf_row"
  * and the automatic multi4-tree form with its generator kernel, stage timing, capture, explicit noise.  Results are bit for bit those of the same calls without mppi_arm;
  * the slide stride between ticks may vary, and mppi_set_control_seq / _hist between arm and compute go through the gate.
  * Every call that changes what the armed solve would compute (model, cost, costmap, limits, seed, noise, variant, timing,
@@ -224,7 +228,7 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
 int mppi_arm(mppi_handle *h, double max_wait_s);
 /* The same for the solves of one mppi_compute_control_batch[_async](handles, states, n) call: the shared one-launch form where
  * the batch would use it and the form has a gated batched kernel (the row forms; two handles of the automatic "m44" form or of
- * "lds44" or of "lds128" or of "bf_row"), otherwise each handle armed on its own where it can be
+ * "lds44" or of "lds128" or of "glb44" or of "bf_row"), otherwise each handle armed on its own where it can be
  * (MPPI_ERR_UNSUPPORTED if one could not be; the others stay armed).  Only a batch call with the same handles in the same order
  * opens the gates; any other call on one of them calls the whole armed launch off first. */
 int mppi_arm_batch(mppi_handle *const *handles, int n, double max_wait_s);
@@ -255,7 +259,7 @@ int mppi_get_applied_controls(mppi_handle *h, float *V, size_t n);
  * afterwards change nothing it returns.  While armed the handle stays armed and the trace is enqueued on the generator stream
  * in FRONT of the armed kernels, not behind them -- but its workgroups (four wavefronts of 160 / 192 VGPRs, up to 64 KB of LDS)
  * still need room on the chip beside the gated kernels, which hold theirs until the gate opens: there is room on every CU
- * beside an armed row launch; an armed "m44" / "lds44" / "lds128" launch fills the SIMDs of the CUs it occupies, and the trace
+ * beside an armed row launch; an armed "m44" / "lds44" / "lds128" / "glb44" launch fills the SIMDs of the CUs it occupies, and the trace
  * runs on the CUs it left free (16 of 256 for the pair of K = 1920).  Where an armed launch occupies every CU the trace ends
  * only once the gate opens or max_wait_s runs out: trace before arming there.
  * Duplicate indices are allowed, n == 0 does nothing.  MPPI_ERR_STATE before the first solve (mppi_rollout_only counts: its
@@ -370,6 +374,16 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     measurement knob, same bits for every N); by name only; the device image is built at this call and held only by handles
  *     that asked for the form; NO gated form and no batched launch, as "lds16"; MPPI_ERR_UNSUPPORTED for the basis-function
  *     model and a list without a hidden layer, MPPI_ERR_INVALID ("unknown variant") for a malformed suffix
+ *     "glb44" mfma4x4x1_glb_l<hidden layers>_w<widest hidden layer>: "lds128"'s group (512 threads per 16 rollouts, four dynamics
+ *     waves on v_mfma_f32_4x4x1 + the riders) for EVERY layer list of the network model (3 <= n_layers <= 8, hidden widths 1..256): a
+ *     layer is one to four halves of 64 neurons with an accumulator each, the reference's order (the bits of "valu_lds", "lds128" and
+ *     "glb16"); the head of the image (biases, layer 0) and the first R of its 1 KB quads are copied into LDS behind the group's
+ *     shared state, the other quads are read from the image in global memory, R = what fits 160 KB; "glb44_r<N>" caps R at N (a
+ *     test and measurement knob, same bits for every N); by name only; the device image is built at this call and held only by
+ *     handles that asked for the form; it HAS a gated form (mppi_arm, chained mppi_control_ticks) and two handles forced to it
+ *     with the same whole layer list and the same cap share one launch (mppi_compute_control_batch, mppi_arm_batch);
+ *     MPPI_ERR_UNSUPPORTED for the basis-function model and a list without a hidden layer, MPPI_ERR_INVALID ("unknown variant")
+ *     for a malformed suffix
  *   A/B arms and cross-checks (never chosen automatically)
  *     "valu" valu_reg_lds (lane = rollout, the independent implementation every parity test also runs; config 4's untuned
  *     vector-ALU reference), "valu_lds" (the generic kernel on a standard shape), "row64" = "row64_r16"
