@@ -72,6 +72,12 @@ const FormRule kFormRules[] = {
 
 }  // namespace
 
+// the forms of the network model that run by name only, for every layer list they serve (the standard shapes too)
+static bool form_by_name_only(Form f)
+{
+  return f == Form::Lds44 || f == Form::Lds128 || f == Form::Lds16 || f == Form::Glb16 || f == Form::Glb44;
+}
+
 Form form_of(const mppi_handle *h)
 {
   if (h->basis) {
@@ -82,11 +88,7 @@ Form form_of(const mppi_handle *h)
     if (3 * (h->K / 64) <= h->num_simds) return Form::Bf3;
     return (2 * (h->K / 64) <= 2 * h->num_simds) ? Form::Bf2 : Form::Bf1;
   }
-  if (h->forced == Form::Lds44) return Form::Lds44;  // by name only, for every layer list it serves (the standard shapes too)
-  if (h->forced == Form::Lds128) return Form::Lds128;  // by name only, as lds44
-  if (h->forced == Form::Lds16) return Form::Lds16;    // by name only, as lds44
-  if (h->forced == Form::Glb16) return Form::Glb16;    // by name only, as lds44
-  if (h->forced == Form::Glb44) return Form::Glb44;    // by name only, as lds44
+  if (form_by_name_only(h->forced)) return h->forced;
   if (!use_mfma(h)) return use_valu_reg(h) ? Form::ValuReg : Form::ValuLds;
   if (h->forced != Form::Auto) return h->forced;
   const int groups = h->K / kRolloutsPerWave, cus = h->num_simds / 4;
@@ -131,6 +133,24 @@ int form_fused_threads(Form f) { return f == Form::Quad ? 512 : f == Form::Fused
 
 }  // namespace mppi_abi
 
+static int widest_hidden(const NetDesc &net)
+{
+  int wmax = 0;
+  for (int l = 1; l + 1 < net.n_layers; l++) wmax = std::max(wmax, net.layers[l]);
+  return wmax;
+}
+
+// the cap of "<form>_r<N>" (suffix = what follows the form's name): -1 for no suffix, -2 for anything else ("unknown variant")
+static int resident_cap_of(const char *suffix)
+{
+  if (*suffix == 0) return -1;
+  const char *p = suffix + 2;
+  if (strncmp(suffix, "_r", 2) != 0 || *p == 0 || strlen(p) > 9) return -2;
+  for (const char *q = p; *q; q++)
+    if (*q < '0' || *q > '9') return -2;
+  return atoi(p);
+}
+
 extern "C" {
 
 const char *mppi_rollout_variant(const mppi_handle *h)
@@ -155,34 +175,10 @@ const char *mppi_rollout_variant(const mppi_handle *h)
     case Form::Row64R16: snprintf(buf, sizeof(buf), "valu_row64_r16_tree_h%d_l%d", h->hidden, h->n_hidden); break;
     case Form::M44: snprintf(buf, sizeof(buf), "mfma4x4x1_h%d_l%d_m44_split_tree", h->hidden, h->n_hidden); break;
     case Form::M44Chain: snprintf(buf, sizeof(buf), "mfma4x4x1_h%d_l%d_m44_tree", h->hidden, h->n_hidden); break;
-    case Form::Lds44: {
-      int wmax = 0;  // the widest hidden layer
-      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
-      snprintf(buf, sizeof(buf), "mfma4x4x1_lds_l%d_w%d", h->n_hidden, wmax);
-      break;
-    }
-    case Form::Lds128: {
-      int wmax = 0;  // the widest hidden layer
-      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
-      snprintf(buf, sizeof(buf), "mfma4x4x1_lds2h_l%d_w%d", h->net.n_layers - 2, wmax);
-      break;
-    }
-    case Form::Lds16: {
-      int wmax = 0;  // the widest hidden layer
-      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
-      snprintf(buf, sizeof(buf), "mfma16x16x4_lds_l%d_w%d", h->net.n_layers - 2, wmax);
-      break;
-    }
-    case Form::Glb16: {
-      int wmax = 0;  // the widest hidden layer
-      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
-      snprintf(buf, sizeof(buf), "mfma16x16x4_glb_l%d_w%d", h->net.n_layers - 2, wmax);
-      break;
-    }
-    case Form::Glb44: {
-      int wmax = 0;  // the widest hidden layer
-      for (int l = 1; l + 1 < h->net.n_layers; l++) wmax = std::max(wmax, h->net.layers[l]);
-      snprintf(buf, sizeof(buf), "mfma4x4x1_glb_l%d_w%d", h->net.n_layers - 2, wmax);
+    case Form::Lds44: case Form::Lds128: case Form::Lds16: case Form::Glb16: case Form::Glb44: {  // the forms of a layer list
+      const char *stem = f == Form::Lds44 ? "mfma4x4x1_lds" : f == Form::Lds128 ? "mfma4x4x1_lds2h" : f == Form::Lds16 ? "mfma16x16x4_lds"
+                         : f == Form::Glb16 ? "mfma16x16x4_glb" : "mfma4x4x1_glb";
+      snprintf(buf, sizeof(buf), "%s_l%d_w%d", stem, h->net.n_layers - 2, widest_hidden(h->net));
       break;
     }
     case Form::Oct: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_oct8w%s", h->hidden, h->n_hidden, gen); break;
@@ -260,14 +256,8 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
     h->forced = Form::Lds16;
   }
   else if (strncmp(name, "glb16", 5) == 0) {  // lds16's wave for every layer list up to 256 wide; "glb16_r<N>": at most N stream blocks resident
-    int cap = -1;
-    if (name[5] != 0) {
-      const char *p = name + 7;
-      if (strncmp(name + 5, "_r", 2) != 0 || *p == 0 || strlen(p) > 9) return fail(h, MPPI_ERR_INVALID, "unknown variant");
-      for (const char *q = p; *q; q++)
-        if (*q < '0' || *q > '9') return fail(h, MPPI_ERR_INVALID, "unknown variant");
-      cap = atoi(p);
-    }
+    const int cap = resident_cap_of(name + 5);
+    if (cap < -1) return fail(h, MPPI_ERR_INVALID, "unknown variant");
     if ((rc = need(!h->basis, "glb16 is a form of the network model"))) return rc;
     if ((rc = need(glb16_supported(h->net), "glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer"))) return rc;
     if ((rc = need(h->K % 64 == 0, "glb16 form needs K to be a multiple of 64"))) return rc;
@@ -276,14 +266,8 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
     h->forced = Form::Glb16;
   }
   else if (strncmp(name, "glb44", 5) == 0) {  // lds128's group for every layer list up to 256 wide; "glb44_r<N>": at most N stream quads resident
-    int cap = -1;
-    if (name[5] != 0) {
-      const char *p = name + 7;
-      if (strncmp(name + 5, "_r", 2) != 0 || *p == 0 || strlen(p) > 9) return fail(h, MPPI_ERR_INVALID, "unknown variant");
-      for (const char *q = p; *q; q++)
-        if (*q < '0' || *q > '9') return fail(h, MPPI_ERR_INVALID, "unknown variant");
-      cap = atoi(p);
-    }
+    const int cap = resident_cap_of(name + 5);
+    if (cap < -1) return fail(h, MPPI_ERR_INVALID, "unknown variant");
     if ((rc = need(!h->basis, "glb44 is a form of the network model"))) return rc;
     if ((rc = need(glb44_supported(h->net), "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer"))) return rc;
     if ((rc = need(h->K % kRolloutsPerWave == 0, "glb44 form needs K to be a multiple of 16"))) return rc;

@@ -282,6 +282,11 @@ int form_multi_nd(Form f);
 int form_fused_threads(Form f);
 inline bool form_is_row(Form f) { return f == Form::Row || f == Form::RowTree; }
 inline bool form_is_row64(Form f) { return f == Form::Row64R16; }
+// the latency forms with riders, which have a gated kernel: the row forms, the automatic m44 form, lds44, lds128, glb44, bf_row
+inline bool form_has_gate(Form f)
+{
+  return form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44 || f == Form::BfRow;
+}
 hipStream_t batch_stream(int device);
 void fill_cost_args(const mppi_handle *h, CostArgs &c);
 void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, RolloutArgs &a);

@@ -390,20 +390,24 @@ std::vector<float> pack_glb16_weights(const std::vector<float> &theta, const Net
   const size_t floats = (size_t)glb16_pack_floats(net);
   return floats ? pack_mfma16_image(theta, net, glb16_net_of(net), floats) : std::vector<float>();
 }
-// the device image of a handle that asked for "glb16": allocated at the first call, rebuilt from h->theta at every call
+// the device image of a handle that asked for a partly resident form by name: allocated at the first call, rebuilt from h->theta
+// at every call.  pk: the packed image; what: "<form> image size"
+static int upload_named_image(mppi_handle *h, const std::vector<float> &pk, float *&d_img, size_t &bytes, const char *what)
+{
+  if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, what);
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if (!d_img) {
+    bytes = pk.size() * sizeof(float);
+    HIPCHK(h, hipMalloc(&d_img, bytes));
+  }
+  if (pk.size() * sizeof(float) != bytes) return fail(h, MPPI_ERR_INVALID, what);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(d_img, pk.data(), bytes, hipMemcpyHostToDevice));
+  return MPPI_OK;
+}
 int upload_glb16_image(mppi_handle *h)
 {
-  const std::vector<float> pk = pack_glb16_weights(h->theta, h->net);
-  if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, "glb16 image size");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (!h->d_glb16pack) {
-    h->glb16_bytes = pk.size() * sizeof(float);
-    HIPCHK(h, hipMalloc(&h->d_glb16pack, h->glb16_bytes));
-  }
-  if (pk.size() * sizeof(float) != h->glb16_bytes) return fail(h, MPPI_ERR_INVALID, "glb16 image size");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(h->d_glb16pack, pk.data(), h->glb16_bytes, hipMemcpyHostToDevice));
-  return MPPI_OK;
+  return upload_named_image(h, pack_glb16_weights(h->theta, h->net), h->d_glb16pack, h->glb16_bytes, "glb16 image size");
 }
 
 // Image of rollout_glb44.hip, any layer list with hidden widths <= 256, in 1 KB quads: float4 q of lane l at float4 index q * 64 + l.
@@ -437,20 +441,9 @@ std::vector<float> pack_glb44_weights(const std::vector<float> &theta, const Net
   }
   return out;
 }
-// the device image of a handle that asked for "glb44": allocated at the first call, rebuilt from h->theta at every call
 int upload_glb44_image(mppi_handle *h)
 {
-  const std::vector<float> pk = pack_glb44_weights(h->theta, h->net);
-  if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, "glb44 image size");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (!h->d_glb44pack) {
-    h->glb44_bytes = pk.size() * sizeof(float);
-    HIPCHK(h, hipMalloc(&h->d_glb44pack, h->glb44_bytes));
-  }
-  if (pk.size() * sizeof(float) != h->glb44_bytes) return fail(h, MPPI_ERR_INVALID, "glb44 image size");
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(h->d_glb44pack, pk.data(), h->glb44_bytes, hipMemcpyHostToDevice));
-  return MPPI_OK;
+  return upload_named_image(h, pack_glb44_weights(h->theta, h->net), h->d_glb44pack, h->glb44_bytes, "glb44 image size");
 }
 
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)

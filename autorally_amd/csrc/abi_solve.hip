@@ -594,7 +594,7 @@ static int arm_kind(const mppi_handle *h)
   if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
         h->explicit_iters == 0 && (!h->basis || f == Form::BfRow) && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
     return 0;
-  if ((form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44 || f == Form::BfRow) && has_noise_wave(h) && !h->prefetch_valid) return 1;
+  if (form_has_gate(f) && has_noise_wave(h) && !h->prefetch_valid) return 1;
   // (where the generator kernel runs beside the rollout.  Where it runs behind it -- 32-wide nets at K = 65 536 -- the phase
   // between two rollouts is the generator's own 41 us whatever the launches cost: chained 0.3139, unchained 0.3131 ms)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;
@@ -840,7 +840,7 @@ static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
 {
   mppi_handle *h0 = hs[0];
   const Form f0 = form_of(h0);
-  if (!(form_is_row(f0) || f0 == Form::M44 || f0 == Form::Lds44 || f0 == Form::Lds128 || f0 == Form::Glb44 || f0 == Form::BfRow))
+  if (!form_has_gate(f0))
     return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
   for (int i = 0; i < n; i++)
     if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");

@@ -172,7 +172,7 @@ hipError_t launch_rollout_lds128(const NetDesc &net, const RolloutArgs &a, hipSt
 hipError_t launch_rollout_lds128_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
 
 // rollout_lds16.hip: the THROUGHPUT form for ANY layer list 6 -> hidden widths 1..128 -> 4 whose image fits one workgroup's LDS:
-// rollout_mfma_kernel's wave (16 rollouts, the whole step, v_mfma_f32_16x16x4_f32, eps from the stand-alone generator) with the
+// rollout_mfma_kernel's wave (wave16_step.hpp: 16 rollouts, the whole step, v_mfma_f32_16x16x4_f32, eps from the stand-alone generator) with the
 // layer list a kernel argument and the A operands read from an LDS image, every layer in the reference's order (bit-identical
 // to the other exact forms); a.wpack = pack_lds16_weights (abi_pack.hip)
 struct Lds16Net {
@@ -184,7 +184,7 @@ struct Lds16Net {
   int boff[7];  // float4 index of its biases
   int nout[7];  // its outputs
 };
-Lds16Net lds16_net_of(const NetDesc &net);    // of a list lds16_lds_bytes(net) != 0
+Lds16Net lds16_net_of(const NetDesc &net);    // of a list lds16_lds_bytes(net) != 0 (wave16_image.hpp builds it, for glb16 too)
 bool lds16_supported(const NetDesc &net);
 int lds16_pack_floats(const NetDesc &net);
 size_t lds16_lds_bytes(const NetDesc &net);   // a workgroup's dynamic LDS = the image of a list 6 -> 1..128 -> 4 (0 for any other list)

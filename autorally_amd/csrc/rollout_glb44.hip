@@ -19,7 +19,7 @@
 //       R = min(stream quads (the zero quads included), floor((160 KB - kM44GroupImageOffset - head bytes) / 1 KB), the cap by name)
 //     quads are copied into LDS behind the group's shared state; quad b is read with ds_read_b128 if b < R, else with
 //     global_load_dwordx4 from the image (it stays in each XCD's L2), the two pointers typed by their address space;
-//   * the choice is wave-uniform and made per BODY, not per load (rollout_glb16.hip: glb16_mode says why).  One body is one input
+//   * the choice is wave-uniform and made per BODY, not per load (wave16_image.hpp: kWave16Lds / Glb / Seam says why).  One body is one input
 //     set (up to 16 quads of k-steps) of one layer, instantiated per (H, resident | streamed | seam); the set's A operand is
 //     chosen by a wave-uniform select in front of it;
 //   * quads are always requested ahead of their use -- across bodies, layers and the seam: a ring of kGlb44Ahead float4 with static

@@ -15,104 +15,43 @@
 //     of a rollout holds the full 7-float state redundantly.
 //   * noise/control buffer is time-major [T][K][2]: a wave's 16 rollouts read/write one
 //     contiguous 128-B line per step; the weighted reduction later streams it row by row.
+//   * the step of rollout_mfma_kernel ("block64" / "block256") is wave16_step.hpp's, shared with rollout_lds16.hip and
+//     rollout_glb16.hip; this file adds the network with its weights in registers (MfmaRegisterNet).  rollout_quad_kernel and
+//     the batch kernel below split the step over four waves and are programs of their own.
 #include "mfma_net.hpp"
 #include "noise_device.hpp"
 #include "mppi_kernels.hpp"
+#include "wave16_step.hpp"
 
 namespace mppi {
 
 
+// the wave's network (wave16_step.hpp) with the weights in registers: nothing to request, the three pieces of mfma_net.hpp
+template <int H, int NHID>
+struct MfmaRegisterNet {
+  using N = MfmaNet<H, NHID>;
+  struct Step {
+    f32x4 acc[N::MT];
+  };
+  const float *const wpack;
+  float A[N::nA], Bi[N::nBias];
+  __device__ __forceinline__ explicit MfmaRegisterNet(const float *wpack_) : wpack(wpack_) {}
+  __device__ __forceinline__ void load(const int lane) { load_weights<H, NHID>(wpack, lane, A, Bi); }
+  __device__ __forceinline__ void request(Step &) const {}
+  __device__ __forceinline__ void layer0(Step &x, const int g, const float s3, const float s4, const float s5, const float s6, const float u0,
+                                         const float u1) const
+  {
+    nn_layer0<H, NHID>(A, g, s3, s4, s5, s6, u0, u1, x.acc);
+  }
+  __device__ __forceinline__ void hidden(Step &x, int) const { nn_hidden<H, NHID>(A, Bi, x.acc); }
+  __device__ __forceinline__ void output(Step &x, float (&d)[4]) const { nn_last<H, NHID>(A, Bi, x.acc, d); }
+};
+
 template <int H, int NHID, bool AFFINE, bool CTRL>
 __global__ __launch_bounds__(256) void rollout_mfma_kernel(const RolloutArgs a)
 {
-  using N = MfmaNet<H, NHID>;
-  const int lane = threadIdx.x & 63;
-  const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-  if (wave * kRolloutsPerWave >= a.K) return;  // whole wave (K is a multiple of 64)
-  const int j = lane & 15, g = lane >> 4;
-  const int k = wave * kRolloutsPerWave + j;
-
-  float A[N::nA], Bi[N::nBias];
-  load_weights<H, NHID>(a.wpack, lane, A, Bi);
-
-  float s[kStateDim];
-#pragma unroll
-  for (int i = 0; i < kStateDim; i++) s[i] = a.state[i];
-  int crash = 0;
-  float J = 0.0f;
-
-  const int K = a.K, T = a.T;
-  float2 *const noise = reinterpret_cast<float2 *>(a.noise);
-  const float2 *const Useq = reinterpret_cast<const float2 *>(a.U);
-  const bool noise_free_k = (k == 0);       // mppi_controller.cu:136
-  const bool pure_noise_k = (k >= a.k99);   // :141, k >= .99*NUM_ROLLOUTS in double (host)
-
-  // Everything a step reads from memory is requested ahead of its use (noise line, nominal
-  // control and 1/t one step ahead; the two costmap texels two network layers ahead), so no
-  // load latency sits on the T-step recurrence.  A step is branch-free and cut into four
-  // scheduling regions: in each, the MFMAs of one network piece run next to independent
-  // cost / kinematics arithmetic.
-  float2 eps = noise[(size_t)k];            // t = 0
-  float2 Unext = Useq[0];
-  double rt_next = a.inv_t[0];
-  for (int t = 0; t < T; t++) {
-    // ---- region 1: controls, layer 0, sin/cos, costmap addresses and fetches ----
-    const float2 e = eps;
-    const float2 Ut = Unext;
-    const double rt = rt_next;
-    const int tn = min(t + 1, T - 1);
-    eps = noise[(size_t)tn * K + k];
-    Unext = Useq[tn];
-    rt_next = a.inv_t[tn];
-    // control perturbation, mppi_controller.cu:136-153
-    const bool nf = noise_free_k | (t < a.opt_delay);
-    const float n0 = e.x * a.nu[0], n1 = e.y * a.nu[1];
-    const float du0 = nf ? 0.0f : n0, du1 = nf ? 0.0f : n1;
-    float u0 = nf ? Ut.x : (pure_noise_k ? n0 : Ut.x + n0);
-    float u1 = nf ? Ut.y : (pure_noise_k ? n1 : Ut.y + n1);
-    // stored before the clamp (Q3); the four lanes of a rollout write the same value
-    noise[(size_t)t * K + k] = make_float2(u0, u1);
-    u0 = clampf(u0, a.u_lo[0], a.u_hi[0]);
-    u1 = clampf(u1, a.u_lo[1], a.u_hi[1]);
-    f32x4 acc[N::MT];
-    nn_layer0<H, NHID>(A, g, s[3], s[4], s[5], s[6], u0, u1, acc);
-    float spsi, cpsi;
-    sincos_fast(s[2], spsi, cpsi);
-    float tf, tb;
-    track_fetch<AFFINE>(a.cost, s, cpsi, spsi, tf, tb);
-    __builtin_amdgcn_sched_barrier(0);
-
-    // ---- region 2: hidden layers next to kinematics and the texel-free cost terms ----
-    nn_hidden<H, NHID>(A, Bi, acc);
-    float sd[kStateDim];
-    sd[0] = fmaf(cpsi, s[4], -(spsi * s[5]));  // computeKinematics, neural_net_model.cu:346-355
-    sd[1] = fmaf(spsi, s[4], cpsi * s[5]);
-    sd[2] = a.negate_yaw_der ? -s[6] : s[6];
-    CostTerms ct;
-    cost_terms_a<CTRL>(a.cost, a.nu, s[4], s[5], u0, u1, du0, du1, ct);
-    __builtin_amdgcn_sched_barrier(0);
-
-    // ---- region 3: output layer next to the track / crash terms and the running mean ----
-    float d[4];
-    nn_last<H, NHID>(A, Bi, acc, d);
-    {
-      // running mean over t = 1..T-1 of the cost of the state before the update (Q5); the
-      // t = 0 evaluation is computed and discarded
-      int crash_new = crash;
-      const float c = cost_terms_b(a.cost, ct, tf, tb, crash_new);
-      const float Jn = running_mean(J, c, t, rt);
-      J = (t > 0) ? Jn : J;
-      crash = (t > 0) ? crash_new : crash;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-
-    // ---- region 4: incrementState (:334-344) and getCrash (costs.cu:301-305) ----
-    sd[3] = d[0]; sd[4] = d[1]; sd[5] = d[2]; sd[6] = d[3];
-#pragma unroll
-    for (int i = 0; i < kStateDim; i++) s[i] = fmaf(sd[i], a.dt, s[i]);
-    crash |= (int)(fabsf(s[3]) >= kRollCrash);
-  }
-  if (g == 0) a.costs[k] = J + 0.0f;  // + terminalCost (= 0), costs.cu:411-414
+  MfmaRegisterNet<H, NHID> nn(a.wpack);
+  wave16_rollout<AFFINE, CTRL>(a, nn);  // the step: wave16_step.hpp
 }
 
 // ---------------------------------------------------------------------------------------------
