@@ -75,7 +75,7 @@ const FormRule kFormRules[] = {
 // the forms of the network model that run by name only, for every layer list they serve (the standard shapes too)
 static bool form_by_name_only(Form f)
 {
-  return f == Form::Lds44 || f == Form::Lds128 || f == Form::Lds16 || f == Form::Glb16 || f == Form::Glb44;
+  return f == Form::Lds44 || f == Form::Lds128 || f == Form::Lds16 || f == Form::Glb16 || f == Form::Glb44 || f == Form::Fleet16;
 }
 
 Form form_of(const mppi_handle *h)
@@ -175,9 +175,9 @@ const char *mppi_rollout_variant(const mppi_handle *h)
     case Form::Row64R16: snprintf(buf, sizeof(buf), "valu_row64_r16_tree_h%d_l%d", h->hidden, h->n_hidden); break;
     case Form::M44: snprintf(buf, sizeof(buf), "mfma4x4x1_h%d_l%d_m44_split_tree", h->hidden, h->n_hidden); break;
     case Form::M44Chain: snprintf(buf, sizeof(buf), "mfma4x4x1_h%d_l%d_m44_tree", h->hidden, h->n_hidden); break;
-    case Form::Lds44: case Form::Lds128: case Form::Lds16: case Form::Glb16: case Form::Glb44: {  // the forms of a layer list
+    case Form::Lds44: case Form::Lds128: case Form::Lds16: case Form::Glb16: case Form::Glb44: case Form::Fleet16: {  // the forms of a layer list
       const char *stem = f == Form::Lds44 ? "mfma4x4x1_lds" : f == Form::Lds128 ? "mfma4x4x1_lds2h" : f == Form::Lds16 ? "mfma16x16x4_lds"
-                         : f == Form::Glb16 ? "mfma16x16x4_glb" : "mfma4x4x1_glb";
+                         : f == Form::Glb16 ? "mfma16x16x4_glb" : f == Form::Fleet16 ? "mfma16x16x4_fleet" : "mfma4x4x1_glb";
       snprintf(buf, sizeof(buf), "%s_l%d_w%d", stem, h->net.n_layers - 2, widest_hidden(h->net));
       break;
     }
@@ -254,6 +254,20 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
     }
     if ((rc = need(h->d_lds16pack != nullptr, "lds16 form: this handle has no image"))) return rc;
     h->forced = Form::Lds16;
+  }
+  else if (strcmp(name, "fleet16") == 0) {  // lds16's wave, image and lists; up to 64 such handles share the launches of a batched solve
+    if ((rc = need(!h->basis, "fleet16 is a form of the network model"))) return rc;
+    const size_t bytes = lds16_lds_bytes(h->net);
+    if ((rc = need(bytes != 0, "fleet16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer"))) return rc;
+    if (bytes > lds16_lds_limit()) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "fleet16 form: the weights of this layer list need %zu bytes of LDS per workgroup, %zu are available",
+               bytes, lds16_lds_limit());
+      return fail(h, MPPI_ERR_UNSUPPORTED, msg);
+    }
+    if ((rc = need(h->d_lds16pack != nullptr, "fleet16 form: this handle has no image"))) return rc;
+    if ((rc = fleet16_prepare(h))) return rc;
+    h->forced = Form::Fleet16;
   }
   else if (strncmp(name, "glb16", 5) == 0) {  // lds16's wave for every layer list up to 256 wide; "glb16_r<N>": at most N stream blocks resident
     const int cap = resident_cap_of(name + 5);

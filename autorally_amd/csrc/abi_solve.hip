@@ -21,6 +21,96 @@ hipStream_t batch_stream(int device)
   return g_batch_stream[device];
 }
 
+hipError_t arg_block_create(ArgBlock &b, size_t slot_bytes)
+{
+  b.slot = (slot_bytes + 255) & ~(size_t)255;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&b.d), b.slot);
+  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&b.h), b.slot * ArgBlock::kRing, hipHostMallocDefault);
+  for (int i = 0; i < ArgBlock::kRing && e == hipSuccess; i++) e = hipEventCreateWithFlags(&b.ev[i], hipEventDisableTiming);
+  if (e != hipSuccess) arg_block_destroy(b);
+  return e;
+}
+
+void arg_block_destroy(ArgBlock &b)
+{
+  for (hipEvent_t &e : b.ev) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+  if (b.h) (void)hipHostFree(b.h);
+  if (b.d) (void)hipFree(b.d);
+  b.h = b.d = nullptr;
+}
+
+hipError_t arg_block_stage(ArgBlock &b, unsigned char **host)
+{
+  if (b.used[b.cur]) {  // the copy out of this slot, kRing uses ago: long complete as a rule
+    if (hipError_t e = hipEventSynchronize(b.ev[b.cur]); e != hipSuccess) return e;
+    b.used[b.cur] = false;
+  }
+  *host = b.h + b.slot * (size_t)b.cur;
+  return hipSuccess;
+}
+
+hipError_t arg_block_send(ArgBlock &b, size_t bytes, hipStream_t stream)
+{
+  if (bytes > b.slot) return hipErrorInvalidValue;
+  hipError_t e = hipMemcpyAsync(b.d, b.h + b.slot * (size_t)b.cur, bytes, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipEventRecord(b.ev[b.cur], stream);
+  if (e != hipSuccess) return e;
+  b.used[b.cur] = true;
+  b.cur = (b.cur + 1) % ArgBlock::kRing;
+  return hipSuccess;
+}
+
+// The fleet16 form's argument blocks of a batched solve: ONE block per device beside the device's batch stream, shared by every
+// fleet on the device and never destroyed -- per iteration the rollout, tail and generator blocks of up to kMaxFleet instances,
+// packed for the fleet's n.  mu: held while a batched solve stages, sends and launches.
+struct FleetBlock {
+  std::mutex mu;
+  ArgBlock args;
+  bool ready = false;
+};
+static FleetBlock g_fleet[64];
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+static size_t fleet_tail_offset(int n) { return align16(sizeof(RolloutArgs) * (size_t)n); }
+static size_t fleet_noise_offset(int n) { return align16(fleet_tail_offset(n) + solve_tail_fleet_arg_bytes() * (size_t)n); }
+static size_t fleet_bytes(int n) { return align16(fleet_noise_offset(n) + sizeof(NoiseFleetDesc) * (size_t)n); }
+static FleetBlock *fleet_block(int device)
+{
+  if (device < 0 || device >= 64) return nullptr;
+  std::lock_guard<std::mutex> lk(g_batch_mu);
+  FleetBlock &fb = g_fleet[device];
+  if (!fb.ready) fb.ready = arg_block_create(fb.args, fleet_bytes(kMaxFleet)) == hipSuccess;
+  return fb.ready ? &fb : nullptr;
+}
+
+int fleet16_prepare(mppi_handle *h)
+{
+  if (h->fleet_one) return MPPI_OK;
+  HIPCHK(h, ensure_device(h->cfg.device));
+  ArgBlock *b = new (std::nothrow) ArgBlock;
+  if (!b) return fail(h, MPPI_ERR_HIP, "out of memory");
+  const hipError_t e = arg_block_create(*b, sizeof(RolloutArgs));
+  if (e != hipSuccess) {
+    delete b;
+    return fail(h, MPPI_ERR_HIP, "fleet16 form: argument block", e);
+  }
+  h->fleet_one = b;
+  return MPPI_OK;
+}
+
+// a fleet16 handle solved alone: the fleet's kernel with one instance, its argument block sent on the handle's own stream
+static hipError_t launch_rollout_fleet16_one(mppi_handle *h, const RolloutArgs &a)
+{
+  if (!h->fleet_one) return hipErrorInvalidValue;
+  unsigned char *host = nullptr;
+  if (hipError_t e = arg_block_stage(*h->fleet_one, &host); e != hipSuccess) return e;
+  memcpy(host, &a, sizeof(RolloutArgs));
+  if (hipError_t e = arg_block_send(*h->fleet_one, sizeof(RolloutArgs), h->stream); e != hipSuccess) return e;
+  return launch_rollout_fleet16(h->net, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), 1, h->num_simds / 4, h->stream);
+}
+
 void fill_cost_args(const mppi_handle *h, CostArgs &c)
 {
   const mppi_cost_params &p = h->cost;
@@ -59,7 +149,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.costs = h->d_costs;
   const Form f = form_of(h);
   a.wpack = f == Form::BfRow ? h->d_bfrowpack : form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
-            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : f == Form::Lds16 ? h->d_lds16pack : f == Form::Glb16 ? h->d_glb16pack : f == Form::Glb44 ? h->d_glb44pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
+            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : (f == Form::Lds16 || f == Form::Fleet16) ? h->d_lds16pack : f == Form::Glb16 ? h->d_glb16pack : f == Form::Glb44 ? h->d_glb44pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
   a.inv_t = h->d_invt;
   a.K = h->K;
   a.T = h->T;
@@ -128,6 +218,7 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
     case Form::Lds44: e = launch_rollout_lds44(h->net, a, h->stream); break;
     case Form::Lds128: e = launch_rollout_lds128(h->net, a, h->stream); break;
     case Form::Lds16: e = launch_rollout_lds16(h->net, a, h->num_simds / 4, h->stream); break;
+    case Form::Fleet16: e = launch_rollout_fleet16_one(h, a); break;
     case Form::Glb16: e = launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, h->stream); break;
     case Form::Glb44: e = launch_rollout_glb44(h->net, a, h->glb44_cap, h->stream); break;
     case Form::Row64R16: e = launch_rollout_row64(h->hidden, h->n_hidden, a, 16, h->stream); break;
@@ -928,6 +1019,120 @@ static bool batch_together(mppi_handle *const *hs, int n)
   return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
 }
 
+// The fleet: 2..kMaxFleet handles forced to "fleet16" on one device with one whole layer list, one num_iters and one pair (affine
+// costmap transform, control cost needed) -- one kernel instance serves the launch, and a superset kernel would not keep every
+// instance's bits (batch_together) -- K <= 4096 each (the one-workgroup-per-row tail), no stage timing, capture or prefetched
+// draws, every handle ready.  Such a set shares its launches: per iteration one generator, one rollout and one tail launch on
+// the device's batch stream.  Anything else about the instances may differ.
+static bool fleet_together(mppi_handle *const *hs, int n)
+{
+  if (n < 2 || n > kMaxFleet) return false;
+  const mppi_handle *h0 = hs[0];
+  CostArgs c0;
+  fill_cost_args(h0, c0);
+  for (int i = 0; i < n; i++) {
+    const mppi_handle *h = hs[i];
+    if (h->basis || h->forced != Form::Fleet16 || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
+    if (h->net.n_layers != h0->net.n_layers) return false;
+    for (int l = 0; l < h->net.n_layers; l++)
+      if (h->net.layers[l] != h0->net.layers[l]) return false;
+    CostArgs ci;
+    fill_cost_args(h, ci);
+    if (ci.affine != c0.affine || ci.need_control_cost != c0.need_control_cost) return false;
+    if (h->K > 4096 || h->K % 64 != 0 || h->timing || h->capture || h->prefetch_valid || h->armed || !h->have_nn || !h->have_map || !h->have_cost) return false;
+  }
+  return true;
+}
+
+// The batched solve of a fleet (fleet_together).  The argument blocks of an iteration -- rollout, tail, generator -- are staged in
+// the device's block and sent with one copy in front of the iteration's three launches.
+static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
+{
+  mppi_handle *h0 = hs[0];
+  HIPCHK(h0, ensure_device(h0->cfg.device));
+  if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
+  const hipStream_t S = h0->batch_s;
+  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+  FleetBlock *fb = fleet_block(h0->cfg.device);
+  if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
+  const int iters = h0->cfg.num_iters;
+  // First pass, as in the batch call: whatever can fail is checked before any handle is changed.
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    int rc = recover_timed_out(h);
+    if (rc == MPPI_OK) rc = wait_pending(h);
+    if (rc) return rc;
+    if (h->explicit_iters > 0 && h->explicit_iters != iters)
+      return fail(h, MPPI_ERR_STATE, "explicit noise holds a different number of iterations");
+  }
+  auto poison = [&](int rc_) {
+    for (int i = 0; i < n; i++) {
+      hs[i]->slid_valid = false;
+      hs[i]->u_dirty = true;
+      hs[i]->pending = false;
+    }
+    return rc_;
+  };
+  std::lock_guard<std::mutex> lk(fb->mu);
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    int rc = hand_over(h, S);
+    if (rc == MPPI_OK) rc = upload_controls_if_dirty(h, S);
+    if (rc) return poison(rc);
+    h->seq = next_seq(h);
+    forget_solve_state(h);
+  }
+  TailLaunch tl[kMaxFleet];
+  for (int it = 0; it < iters; it++) {
+    const bool last = (it == iters - 1);
+    unsigned char *host = nullptr;
+    hipError_t e = arg_block_stage(fb->args, &host);
+    if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "fleet argument block", e));
+    RolloutArgs *ra = reinterpret_cast<RolloutArgs *>(host);
+    NoiseFleetDesc *nd = reinterpret_cast<NoiseFleetDesc *>(host + fleet_noise_offset(n));
+    for (int i = 0; i < n; i++) {
+      mppi_handle *h = hs[i];
+      const bool explicit_noise = h->explicit_iters > 0;
+      float *noise;
+      nd[i] = NoiseFleetDesc{};  // explicit noise: draws nothing
+      if (explicit_noise) {
+        noise = h->d_noise + (size_t)it * ((size_t)h->K * h->T * 2);
+      } else {
+        // the handle's generator stream and buffers move exactly as acquire_noise moves them for its own solve
+        h->gen_cur = 1 - h->gen_cur;
+        noise = h->d_gen[h->gen_cur];
+        nd[i] = NoiseFleetDesc{h->d_rng[h->rng_cur], h->d_rng[1 - h->rng_cur], h->d_jump, noise, h->K, h->T, h->noise_L, h->noise_C};
+        h->rng_cur = 1 - h->rng_cur;
+      }
+      h->v_buf = noise;
+      fill_rollout_args(h, states + (size_t)MPPI_STATE_DIM * i, noise, ra[i]);
+      if (int trc = tag_min_cost(h, ra[i], S)) return poison(trc);
+      next_tail_epoch(h);
+      tl[i] = tail_launch(h, noise, last);
+      if (last) h->slid_valid = wants_slid_copy(h);
+    }
+    fill_solve_tail_fleet(host + fleet_tail_offset(n), tl, n);
+    e = arg_block_send(fb->args, fleet_bytes(n), S);
+    const unsigned char *dev = fb->args.d;
+    if (e == hipSuccess) e = launch_noise_fleet(nd, reinterpret_cast<const NoiseFleetDesc *>(dev + fleet_noise_offset(n)), n, S);
+    if (e == hipSuccess)
+      e = launch_rollout_fleet16(h0->net, ra, reinterpret_cast<const RolloutArgs *>(dev), n, h0->num_simds / 4, S);
+    if (e == hipSuccess) e = launch_solve_tail_fleet(tl, n, dev + fleet_tail_offset(n), S);
+    if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "fleet launch", e));
+    for (int i = 0; i < n; i++) {
+      hs[i]->launch_instances = n;
+      hs[i]->launch_gated = false;
+    }
+  }
+  for (int i = 0; i < n; i++) {
+    hs[i]->explicit_iters = 0;
+    hs[i]->pending = true;
+    note_solve_state(hs[i], states + (size_t)MPPI_STATE_DIM * i, true);
+    hs[i]->pending_timed = false;
+  }
+  return MPPI_OK;
+}
+
 static bool armed_as_batch(mppi_handle *const *hs, int n)
 {
   for (int i = 0; i < n; i++) {
@@ -1012,6 +1217,14 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     }
   }
   mppi_handle *h0 = hs[0];
+  if (!together && fleet_together(hs, n)) return enqueue_fleet(hs, states, n);  // the "fleet16" form: 2..64 handles, three launches
+  if (!together && n >= 2) {
+    // a set of "fleet16" handles with one that is not ready: its error before any of the others has moved
+    bool all_fleet = true;
+    for (int i = 0; i < n; i++) all_fleet = all_fleet && hs[i]->forced == Form::Fleet16;
+    for (int i = 0; i < n && all_fleet; i++)
+      if (const int rc = check_ready(hs[i])) return rc;
+  }
   if (!together) {
     for (int i = 0; i < n; i++) {
       const int rc = mppi_compute_control_async(hs[i], states + (size_t)MPPI_STATE_DIM * i);

@@ -69,6 +69,10 @@ void free_all(mppi_handle *h)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_s1) (void)hipEventDestroy(h->ev_s1);
   if (h->ev_arm) (void)hipEventDestroy(h->ev_arm);
+  if (h->fleet_one) {
+    arg_block_destroy(*h->fleet_one);
+    delete h->fleet_one;
+  }
   if (h->gstream) (void)hipStreamDestroy(h->gstream);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

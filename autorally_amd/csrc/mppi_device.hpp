@@ -187,6 +187,16 @@ static_assert(kMaxBatch == 4, "MPPI_BATCH_DISPATCH");
     }                                       \
   } while (0)
 
+// A pointer a kernel LOADS (from an argument block in device memory: the fleet kernels) is a generic pointer to the compiler, and
+// every access through it a flat instruction, which counts against the LDS counter too.  Pointers in the kernel-argument segment
+// are known to be global; a field read through this is loaded AS a global pointer, so its accesses are global ones again.
+template <class T>
+__device__ __forceinline__ T *load_global_ptr(T *const &field)
+{
+  using G = __attribute__((address_space(1))) T *;
+  return (T *)*static_cast<const G *>(static_cast<const void *>(&field));
+}
+
 // Thresholds for the reference's float-vs-double-literal comparisons, as floats:
 //   (double)x > 1.57   <=>  x >= kRollCrash   (costs.cu:302)
 //   (double)x > 0.001  <=>  x >= kMinSpeed    (costs.cu:340)

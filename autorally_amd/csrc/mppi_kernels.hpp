@@ -193,6 +193,18 @@ size_t lds16_lds_limit();                     // the dynamic LDS a workgroup may
 int lds16_block_threads(const NetDesc &net, int K, int cus);
 hipError_t launch_rollout_lds16(const NetDesc &net, const RolloutArgs &a, int cus, hipStream_t stream);  // cus: the device's CUs (the handle's)
 
+// rollout_fleet16.hip: lds16's wave and image for up to kMaxFleet independent controllers of ONE layer list in one launch -- grid
+// (workgroups of the largest instance, instances), the instances' argument blocks an array in device memory
+constexpr int kMaxFleet = 64;
+struct Fleet16Plan {
+  int threads, grid_x, grid_y;  // one workgroup size for the launch; all zero: no launch (a list lds16 refuses, n outside 1..kMaxFleet)
+  size_t lds_bytes;             // a workgroup's dynamic LDS: lds16_lds_bytes
+};
+// Ks: the instances' rollouts; threads: wave16_image_block_threads' rule on all workgroups of the fleet (n = 1: lds16_block_threads)
+Fleet16Plan fleet16_plan(const NetDesc &net, const int *Ks, int n, int cus);
+// h_inst: the n argument blocks on the host (K and the cost flags are read there); d_inst: the same blocks in device memory
+hipError_t launch_rollout_fleet16(const NetDesc &net, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, int cus, hipStream_t stream);
+
 // rollout_glb16.hip: lds16's wave for EVERY layer list 6 -> hidden widths 1..256 -> 4 (3 <= n_layers <= 8): the image is lds16's
 // with up to 16 tiles per layer; its head (biases + layer 0) and the first R blocks of its stream are resident in LDS, the other
 // blocks are read from the image in global memory; a.wpack = pack_glb16_weights (abi_pack.hip).  cap: the cap on R given by
@@ -311,6 +323,12 @@ constexpr int kTailExchangeGranules = 3 * 64 + 32 * 16 + 32 * 64;  // solve_kern
 hipError_t launch_solve_tail(const TailLaunch &l, hipStream_t stream);
 // the tails of n <= kMaxBatch instances (K <= 4096 each) in one launch
 hipError_t launch_solve_tail_batch(const TailLaunch *l, int n, hipStream_t stream);
+// the tails of n <= kMaxFleet instances (K <= 4096 each) in one launch, their argument blocks an array in device memory
+// (solve_tail_fleet_kernel): fill_solve_tail_fleet writes the n blocks, solve_tail_fleet_arg_bytes() each, where the host
+// stages them; d_args: the same blocks in device memory, complete once `stream` reaches the launch
+size_t solve_tail_fleet_arg_bytes();
+void fill_solve_tail_fleet(void *dst, const TailLaunch *l, int n);
+hipError_t launch_solve_tail_fleet(const TailLaunch *l, int n, const void *d_args, hipStream_t stream);
 hipError_t launch_debug_cost(const CostArgs &c, float x, float y, float heading, int width_m, int height_m,
                              int ppm, float *out, hipStream_t stream);
 hipError_t launch_slide(float *in, int T, int stride, float init0, float init1, hipStream_t stream);
@@ -320,6 +338,16 @@ hipError_t launch_tk_to_kt(const float *src, float *dst, int K, int T, hipStream
 // noise_mrg32k3a.hip
 hipError_t launch_noise(const uint32_t *rng_in, uint32_t *rng_out, const uint32_t *jump, int K, int T,
                         int L, int C, float *eps, hipStream_t stream);
+// the draws of n <= kMaxFleet instances in one launch (noise_fleet_kernel): noise_kernel over an array of descriptors in device
+// memory, grid (blocks of the largest instance, instances).  K == 0: an instance that draws nothing (explicit noise)
+struct NoiseFleetDesc {
+  const uint32_t *rng_in;
+  uint32_t *rng_out;
+  const uint32_t *jump;
+  float *eps;
+  int K, T, L, C;
+};
+hipError_t launch_noise_fleet(const NoiseFleetDesc *h_desc, const NoiseFleetDesc *d_desc, int n, hipStream_t stream);
 hipError_t launch_noise_init(uint32_t *rng, int K, const uint32_t base[6], const uint32_t *sub,
                              int sub_bits, const uint32_t *one, uint64_t offset, hipStream_t stream);
 

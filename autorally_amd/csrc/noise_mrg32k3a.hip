@@ -12,16 +12,16 @@
 // chunk writes the state after 2T draws to the ping-pong state buffer.  Output is written
 // time-major [T][K][2] (coalesced 8-B per lane, consecutive k).
 #include "noise_device.hpp"
+#include "mppi_kernels.hpp"
 
 namespace mppi {
 
-// rng: [6][K] current per-rollout states (SoA). jump: [C][18] = A1^(2Lc) | A2^(2Lc).
-__global__ __launch_bounds__(256) void noise_kernel(const uint32_t *__restrict__ rng_in,
-                                                    uint32_t *__restrict__ rng_out,
-                                                    const uint32_t *__restrict__ jump, int K, int T,
-                                                    int L, int C, float2 *__restrict__ eps)
+// rng: [6][K] current per-rollout states (SoA). jump: [C][18] = A1^(2Lc) | A2^(2Lc).  block: the workgroup's index in its instance
+__device__ __forceinline__ void noise_body(const int block, const uint32_t *__restrict__ rng_in, uint32_t *__restrict__ rng_out,
+                                           const uint32_t *__restrict__ jump, const int K, const int T, const int L, const int C,
+                                           float2 *__restrict__ eps)
 {
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int tid = block * blockDim.x + threadIdx.x;
   if (tid >= K * C) return;
   const int c = tid / K;  // wave-uniform (K % 64 == 0)
   const int k = tid - c * K;
@@ -41,6 +41,24 @@ __global__ __launch_bounds__(256) void noise_kernel(const uint32_t *__restrict__
     rng_out[k] = g.s10; rng_out[K + k] = g.s11; rng_out[2 * K + k] = g.s12;
     rng_out[3 * K + k] = g.s20; rng_out[4 * K + k] = g.s21; rng_out[5 * K + k] = g.s22;
   }
+}
+
+__global__ __launch_bounds__(256) void noise_kernel(const uint32_t *__restrict__ rng_in,
+                                                    uint32_t *__restrict__ rng_out,
+                                                    const uint32_t *__restrict__ jump, int K, int T,
+                                                    int L, int C, float2 *__restrict__ eps)
+{
+  noise_body((int)blockIdx.x, rng_in, rng_out, jump, K, T, L, C, eps);
+}
+
+// noise_kernel for the instances of a fleet (abi_solve.hip): grid (blocks of the largest instance, instances), workgroup (x, y) is
+// block x of desc[y]; an instance with K == 0 (explicit noise) and the blocks beyond an instance's own draw nothing
+__global__ __launch_bounds__(256) void noise_fleet_kernel(const NoiseFleetDesc *__restrict__ desc, const int n)
+{
+  if ((int)blockIdx.y >= n) return;
+  const NoiseFleetDesc &d = desc[blockIdx.y];
+  noise_body((int)blockIdx.x, load_global_ptr(d.rng_in), load_global_ptr(d.rng_out), load_global_ptr(d.jump), d.K, d.T, d.L, d.C,
+             reinterpret_cast<float2 *>(load_global_ptr(d.eps)));
 }
 
 // Per-rollout start states: base advanced by k*2^76 (binary expansion of k over sub[b] =
@@ -72,6 +90,20 @@ hipError_t launch_noise(const uint32_t *rng_in, uint32_t *rng_out, const uint32_
   const int total = K * C;
   hipLaunchKernelGGL(noise_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, rng_in, rng_out,
                      jump, K, T, L, C, reinterpret_cast<float2 *>(eps));
+  return hipGetLastError();
+}
+
+hipError_t launch_noise_fleet(const NoiseFleetDesc *h_desc, const NoiseFleetDesc *d_desc, int n, hipStream_t stream)
+{
+  if (!h_desc || !d_desc || n < 1 || n > kMaxFleet) return hipErrorInvalidValue;
+  int blocks = 0;
+  for (int i = 0; i < n; i++) {
+    if (h_desc[i].K % 64 != 0) return hipErrorInvalidValue;
+    const int b = (h_desc[i].K * h_desc[i].C + 255) / 256;
+    blocks = b > blocks ? b : blocks;
+  }
+  if (blocks == 0) return hipSuccess;  // nobody draws
+  hipLaunchKernelGGL(noise_fleet_kernel, dim3(blocks, n), dim3(256), 0, stream, d_desc, n);
   return hipGetLastError();
 }
 

@@ -2,8 +2,8 @@
 // widths up to 128 whose image fits the LDS: the 16x16x4 wave (wave16_step.hpp: one wavefront = 16 rollouts, the whole step in the
 // wave, eps from the stand-alone generator, no rings, no riders, no barrier in the T loop) with the layer list a kernel ARGUMENT
 // and the A operands of v_mfma_f32_16x16x4_f32 read from an LDS image (wave16_image.hpp: the walk over the image, shared with
-// rollout_glb16.hip) instead of kept in registers.  This file: the capacity rule, the stream of an image that is in LDS as a
-// whole, the kernel and the launcher.  Layout and order:
+// rollout_glb16.hip) instead of kept in registers.  This file: the capacity rule, the kernel and the launcher (the stream of an image
+// that is in LDS as a whole, Lds16Stream, is in wave16_image.hpp: rollout_fleet16.hip runs the same wave).  Layout and order:
 //   * lane l = (rollout j = l & 15, k-slot / row group g = l >> 4).  A hidden layer of nout outputs is MT = ceil(nout / 16) M tiles
 //     with an accumulator (4 registers) each; D row 16 m + 4 g + r carries neuron 16 m + 4 r + g (the row permutation of
 //     pack_mfma_weights, per tile), which is k-slot g of k-step 4 m + r of the next layer: a layer's D registers are the next
@@ -34,12 +34,6 @@
 
 namespace mppi {
 
-constexpr size_t kLds16MaxBytes = 160 * 1024;  // the dynamic-LDS limit the launcher requests
-constexpr int kLds16Ahead = 2;                 // blocks requested ahead of their use
-// registers per lane of the instances (ISA) as waves per SIMD (512 / allocation): what the workgroup rule counts with
-constexpr int kLds16WavesPerSimd4 = 4, kLds16WavesPerSimd8 = 3;
-constexpr int kLds16MaxThreads8 = 512;         // the largest workgroup of the 8-tile instance
-
 // offsets and counts of a list lds_list_ok(net, 128) accepts
 Lds16Net lds16_net_of(const NetDesc &net) { return wave16_image_net_of(net, kLds16Ahead); }
 
@@ -60,19 +54,6 @@ int lds16_block_threads(const NetDesc &net, int K, int cus)
   return wave16_image_block_threads(K, cus, lds16_lds_bytes(net), kLds16MaxBytes, wide ? kLds16WavesPerSimd8 : kLds16WavesPerSimd4,
                                     wide ? kLds16MaxThreads8 : 1024);
 }
-
-// the stream (wave16_image.hpp) of an image that is in LDS as a whole: a pointer to this lane's quad of the next block to use.
-// With two blocks ahead a pair leaves the ring as it found it and an odd tile count swaps w[0] and w[1]
-struct Lds16Stream {
-  static constexpr int kAhead = kLds16Ahead;
-  static constexpr bool kResident = true;
-  const f32x4 *p;
-  static __device__ __forceinline__ Lds16Stream at(const f32x4 *lds, const f32x4 *, int) { return Lds16Stream{lds}; }
-  template <int MODE>
-  __device__ __forceinline__ f32x4 fetch(const int i) const { return p[i * 64]; }
-  __device__ __forceinline__ void advance(const int n) { p += 64 * n; }
-  static __device__ __forceinline__ void keep_vector(int &) {}
-};
 
 extern __shared__ __attribute__((aligned(16))) unsigned char lds16_smem[];
 

@@ -888,6 +888,21 @@ __global__ __launch_bounds__(kTailThreads) void solve_tail_batch_kernel(const Ta
 #undef MPPI_TAIL_BODY
 }
 
+// The tails of a fleet (abi_solve.hip: up to kMaxFleet instances, K <= kRedChunk each): solve_tail_body over an array of argument
+// blocks in device memory, grid (T + 1 of the longest instance, instances).  The index is workgroup-uniform and the array
+// read-only: the block is read with scalar loads, as the kernel-argument segment is.  No hand-over between workgroups beyond
+// solve_tail_kernel's own (the arrival counter of an instance's T + 1 workgroups).
+__global__ __launch_bounds__(kTailThreads) void solve_tail_fleet_kernel(const TailArgs *__restrict__ inst, const int n)
+{
+  if ((int)blockIdx.y >= n) return;
+  TailArgs a = inst[blockIdx.y];
+  if ((int)blockIdx.x > a.T) return;
+  a.costs = load_global_ptr(inst[blockIdx.y].costs); a.V = load_global_ptr(inst[blockIdx.y].V); a.U = load_global_ptr(inst[blockIdx.y].U); a.hist = load_global_ptr(inst[blockIdx.y].hist); a.w = load_global_ptr(inst[blockIdx.y].w);
+  a.scal = load_global_ptr(inst[blockIdx.y].scal); a.res = load_global_ptr(inst[blockIdx.y].res); a.hist_out = load_global_ptr(inst[blockIdx.y].hist_out); a.ug = load_global_ptr(inst[blockIdx.y].ug);
+  a.counter = load_global_ptr(inst[blockIdx.y].counter); a.slid = load_global_ptr(inst[blockIdx.y].slid); a.min_cost = load_global_ptr(inst[blockIdx.y].min_cost);
+  solve_tail_body(a, (int)blockIdx.x, a.V, a.costs, a.K, a.T);
+}
+
 // slideControlSeq (mppi_controller.cu:527-554) on the device copy of [U(2T) | hist(4)], so that a
 // solve -> slide -> solve loop never re-uploads the sequence.  One workgroup; mirrors the host code.
 __global__ void slide_kernel(float *__restrict__ in, int T, int stride, float init0, float init1)
@@ -1047,6 +1062,26 @@ hipError_t launch_solve_tail_batch(const TailLaunch *l, int n, hipStream_t strea
   }
   if (n <= 2) launch_tail_batch_nb<2>(l, n, tmax, dyn, stream);
   else launch_tail_batch_nb<4>(l, n, tmax, dyn, stream);
+  return hipGetLastError();
+}
+
+size_t solve_tail_fleet_arg_bytes() { return sizeof(TailArgs); }
+void fill_solve_tail_fleet(void *dst, const TailLaunch *l, int n)
+{
+  TailArgs *a = static_cast<TailArgs *>(dst);
+  for (int i = 0; i < n; i++) a[i] = fill_tail(l[i]);
+}
+hipError_t launch_solve_tail_fleet(const TailLaunch *l, int n, const void *d_args, hipStream_t stream)
+{
+  if (!l || !d_args || n < 1 || n > kMaxFleet) return hipErrorInvalidValue;
+  size_t dyn = 0;
+  int tmax = 0;
+  for (int i = 0; i < n; i++) {
+    if (l[i].K > kRedChunk) return hipErrorInvalidValue;  // one workgroup per row only
+    dyn = tail_dyn_bytes(l[i].K, l[i].T) > dyn ? tail_dyn_bytes(l[i].K, l[i].T) : dyn;
+    tmax = l[i].T > tmax ? l[i].T : tmax;
+  }
+  hipLaunchKernelGGL(solve_tail_fleet_kernel, dim3(tmax + 1, n), dim3(kTailThreads), dyn, stream, static_cast<const TailArgs *>(d_args), n);
   return hipGetLastError();
 }
 

@@ -49,16 +49,23 @@ inline int wave16_image_tiles_max(const NetDesc &net, int small)
 // The workgroup: the image is per workgroup, so small workgroups spread a modest K over all CUs and a big image leaves one
 // workgroup per CU -- the smallest of 256 / 512 / .. / largest threads for which every workgroup of the launch is resident at
 // once (LDS: floor(limit / requested bytes) workgroups per CU; registers: the instance's waves per SIMD), else the largest.
-inline int wave16_image_block_threads(int K, int cus, size_t lds_bytes, size_t lds_limit, int waves_per_simd, int largest)
+// Several instances in one launch (rollout_fleet16.hip): a workgroup serves one instance, so the launch's workgroups are the sum
+// of the instances' own.
+inline int wave16_image_block_threads(const int *Ks, int n, int cus, size_t lds_bytes, size_t lds_limit, int waves_per_simd, int largest)
 {
-  const int waves = K / kRolloutsPerWave;
   const int by_lds = (int)(lds_limit / lds_bytes);
   for (int threads = 256; threads <= largest; threads *= 2) {
     const int wpb = threads / 64, by_regs = 4 * waves_per_simd / wpb;
     const int per_cu = by_lds < by_regs ? by_lds : by_regs;
-    if ((waves + wpb - 1) / wpb <= (long long)per_cu * cus) return threads;
+    long long blocks = 0;
+    for (int i = 0; i < n; i++) blocks += (Ks[i] / kRolloutsPerWave + wpb - 1) / wpb;
+    if (blocks <= (long long)per_cu * cus) return threads;
   }
   return largest;
+}
+inline int wave16_image_block_threads(int K, int cus, size_t lds_bytes, size_t lds_limit, int waves_per_simd, int largest)
+{
+  return wave16_image_block_threads(&K, 1, cus, lds_bytes, lds_limit, waves_per_simd, largest);
 }
 
 // extra: the kernel's arguments behind the layer list
@@ -333,5 +340,25 @@ struct Wave16ImageNet {
   }
 };
 #undef MPPI_W16_MFMA
+
+// ---- the image that is in LDS as a whole (rollout_lds16.hip, rollout_fleet16.hip) ----
+constexpr size_t kLds16MaxBytes = 160 * 1024;  // the dynamic-LDS limit the launcher requests
+constexpr int kLds16Ahead = 2;                 // blocks requested ahead of their use
+// registers per lane of the instances (ISA) as waves per SIMD (512 / allocation): what the workgroup rule counts with
+constexpr int kLds16WavesPerSimd4 = 4, kLds16WavesPerSimd8 = 3;
+constexpr int kLds16MaxThreads8 = 512;         // the largest workgroup of the 8-tile instance
+
+// the stream (wave16_image.hpp) of an image that is in LDS as a whole: a pointer to this lane's quad of the next block to use.
+// With two blocks ahead a pair leaves the ring as it found it and an odd tile count swaps w[0] and w[1]
+struct Lds16Stream {
+  static constexpr int kAhead = kLds16Ahead;
+  static constexpr bool kResident = true;
+  const f32x4 *p;
+  static __device__ __forceinline__ Lds16Stream at(const f32x4 *lds, const f32x4 *, int) { return Lds16Stream{lds}; }
+  template <int MODE>
+  __device__ __forceinline__ f32x4 fetch(const int i) const { return p[i * 64]; }
+  __device__ __forceinline__ void advance(const int n) { p += 64 * n; }
+  static __device__ __forceinline__ void keep_vector(int &) {}
+};
 
 }  // namespace mppi

@@ -668,6 +668,39 @@ class MPPIControllerT {
       throw std::runtime_error(std::string("libmppi_hip: ") + mppi_strerror(rc) + " (" + mppi_last_error(actual->h_) +
                                " | " + mppi_last_error(predicted->h_) + ")");
   }
+  // The solves of n independent controllers (a simulation's cars, a sweep over cost parameters) enqueued TOGETHER; states: n x
+  // STATE_DIM.  Where every controller runs the "fleet16" rollout variant on one layer list (include/mppi_hip.h: the sharing
+  // rule of mppi_compute_control_batch, 2 <= n <= 64) the whole fleet is one generator, one rollout and one tail launch per
+  // iteration; any other set is n startControl calls.  Results per controller are bit for bit those of startControl.
+  static void startControlFleet(MPPIControllerT *const *controllers, int n, const float *states)
+  {
+    if (n < 1) return;
+    std::vector<mppi_handle *> hs((size_t)n);
+    for (int c = 0; c < n; c++) {
+      controllers[c]->syncParams(false);
+      for (int i = 0; i < STATE_DIM; i++) controllers[c]->solve_state_[i] = states[(size_t)c * STATE_DIM + i];
+      hs[(size_t)c] = controllers[c]->h_;
+    }
+    const int rc = mppi_compute_control_batch_async(hs.data(), states, n);
+    if (rc != MPPI_OK) {  // the text sits on whichever handle recorded it
+      std::string msg = std::string("libmppi_hip: ") + mppi_strerror(rc) + " (";
+      for (int c = 0; c < n; c++) {
+        const char *e = mppi_last_error(controllers[c]->h_);
+        if (e && *e) msg += std::string(msg.back() == '(' ? "" : " | ") + e;
+      }
+      throw std::runtime_error(msg + ")");
+    }
+  }
+  // finishControl() of every controller of the fleet: all solves collected, then each nominal trajectory replayed on the host
+  static void finishControlFleet(MPPIControllerT *const *controllers, int n)
+  {
+    for (int c = 0; c < n; c++) {
+      float tc = 0.0f;
+      controllers[c]->ck(mppi_get_results(controllers[c]->h_, nullptr, &tc, nullptr, nullptr));
+      controllers[c]->trajectory_cost_ = tc;
+    }
+    for (int c = 0; c < n; c++) controllers[c]->computeNominalTraj(controllers[c]->solve_state_);
+  }
   // Solve-ahead (mppi_arm): this controller's NEXT solve is enqueued now, gated -- its kernels start and wait at most max_wait_s
   // for the next startControl / computeControl, which then opens the gate with its state instead of launching.  Results are
   // bit for bit the same.  MPPI_ERR_UNSUPPORTED (no gated form for this configuration) is no error: the solve launches as before.

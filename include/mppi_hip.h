@@ -58,6 +58,9 @@ extern "C" {
  *    mppi_arm, mppi_arm_batch, chained mppi_control_ticks and the pair in one launch) for every layer list mppi_create accepts
  *    (hidden widths up to 256, an image of any size): the front of the image resident in LDS, the rest read from global memory;
  *    no new export. */
+/*    (still 5) + rollout variant "fleet16", name "mfma16x16x4_fleet_l<N>_w<W>": "lds16"'s wavefront, image and lists with the argument
+ *    block read from device memory; 2..64 handles forced to it share the launches of mppi_compute_control_batch (one generator, one
+ *    rollout, one tail launch per iteration); no new export, no gated form, the automatic choice does not change. */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -206,7 +209,15 @@ int mppi_synchronize(mppi_handle *h);
  * basis-function model's three-wavefront form, or its "bf_row" form forced on both handles of a pair under the row forms' rule:
  * 2 x K=1920 shares a launch, 2 x K=2560 does not) the n solves cost TWO kernel launches in all, on a stream of the library
  * shared by the device's handles; otherwise ("m44_chain", three m44 handles ...) this is n calls of
- * mppi_compute_control_async.  mppi_debug_launch_info tells which it was.  Either way every
+ * mppi_compute_control_async.
+ * The "fleet16" variant: 2 <= n <= 64 handles share their launches when every handle is forced to "fleet16", all are on one device,
+ * have the same whole layer list, the same num_iters and the same pair (affine costmap transform, control cost needed), K <= 4096
+ * each, none has stage timing, capture or prefetched draws, and every handle is ready.  Each iteration of such a batch is THREE
+ * launches in all on the library's stream of the device -- one generator launch, one rollout launch, one tail launch -- whatever
+ * else differs between the instances (K, T, state, U and hist, weights, costmap and transform, cost parameters, limits, nu,
+ * gamma, seed, explicit noise or the generator).  Any other set of such handles (n > 64, a mixed set, a K above 4096) is n
+ * per-handle solves; a set of "fleet16" handles with one that is not ready returns that handle's error before any has moved.
+ * mppi_debug_launch_info tells which it was.  Either way every
  * handle's results are bit for bit those of its own mppi_compute_control, collected per handle with
  * mppi_synchronize / mppi_get_results.  The blocking form waits for all of them. */
 int mppi_compute_control_batch_async(mppi_handle *const *handles, const float *states, int n);
@@ -367,6 +378,10 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     128-wide layer does not); workgroups of 256 / 512 / 1024 threads, the smallest with every workgroup resident at once; by
  *     name only; NO gated form (mppi_arm answers MPPI_ERR_UNSUPPORTED) and no batched launch (a batch solves handle by handle);
  *     MPPI_ERR_UNSUPPORTED as "lds128"
+ *     "fleet16" mfma16x16x4_fleet_l<hidden layers>_w<widest hidden layer>: "lds16"'s wavefront, image and lists (hidden widths 1..128,
+ *     the image fits 160 KB of LDS; the same refusals) with the argument block read from device memory, so that up to 64 handles of
+ *     one layer list share ONE rollout launch (mppi_compute_control_batch: the sharing rule is stated there); the bits of "lds16"
+ *     and "valu_lds"; NO gated form; a handle solved alone runs the same kernel with one instance; by name only.
  *     "glb16" mfma16x16x4_glb_l<hidden layers>_w<widest hidden layer>: "lds16"'s wavefront for EVERY layer list of the network model
  *     (3 <= n_layers <= 8, hidden widths 1..256): the same image with up to 16 tiles per layer; its head (biases, layer 0) and the
  *     first R of its 1 KB blocks are copied into LDS, the other blocks are read from the image in global memory (it stays in L2),
@@ -450,7 +465,7 @@ int mppi_debug_set_chained_ticks(mppi_handle *h, int on);
 int mppi_debug_min_cost(mppi_handle *h, int on, int *from_rollout);
 
 /* Test / tooling hook: *instances = how many instances the rollout launch of this handle's most recently ENQUEUED solve served
- * (an armed solve that is not yet opened counts; 1: a launch of its own; 2..4: shared with the other handles of a
+ * (an armed solve that is not yet opened counts; 1: a launch of its own; 2..64: shared with the other handles of a
  * mppi_compute_control_batch / mppi_arm_batch call; 0: no solve yet), *gated = 1 if that launch was a gated one (mppi_arm,
  * mppi_arm_batch, the chained mppi_control_ticks).  Recorded where the launch is made.  MPPI_ERR_INVALID for a NULL argument. */
 int mppi_debug_launch_info(mppi_handle *h, int *instances, int *gated);

@@ -1,0 +1,99 @@
+"""Tick time of a fleet of controllers on one GPU: the "fleet16" rollout form (one generator, one rollout and one tail launch per
+tick for the whole fleet) against the same handles solved one by one.
+
+    python tools/fleet_time.py [--n 16] [--K 1920] [--T 100] [--ticks 200] [--warm 20] [--ways abc] [--net 6-32-32-4 ...]
+
+n distinct oval instances with generator noise; the median wall time of a tick (mppi_control_ticks_batch, one tick, stride 1) over
+`ticks` ticks after `warm` warm ones, three ways: (a) every handle forced to "fleet16"; (b) forced to "lds16" -- the same
+wavefront, handle by handle; (c) "auto" (row_tree / m44, handle by handle).  Prints one line per network and a JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+WAYS = (("a", "fleet16"), ("b", "lds16"), ("c", "auto"))
+
+
+def fleet(net, variant, n, K, T):
+    """n solvers on n distinct oval instances (one map: the instances differ in the start state, the model's scale, the cost
+    parameters and the seed), forced to `variant`, and their states."""
+    from autorally_amd import capi
+    from autorally_amd import synthetic as S
+    base = S.make_config(K, T, layers=list(net), track="oval", opt_stride=1)
+    sols, states = [], []
+    for i in range(n):
+        st = np.array(base["start_state"], np.float32)
+        st[0] += np.float32(0.4 * i)
+        st[4] += np.float32(0.1 * (i % 5))
+        cfg = dict(base, theta=(np.asarray(base["theta"], np.float32) * np.float32(1.0 + 0.005 * i)),
+                   cost=dict(base["cost"], desired_speed=6.0 + 0.25 * i), start_state=st)
+        sol = capi.Solver(cfg)
+        if variant != "auto":
+            sol.set_rollout_variant(variant)
+        sol.seed(1000 + i, 0)
+        sols.append(sol)
+        states.append(st)
+    return sols, states
+
+
+def tick_ms(net, variant, n=16, K=1920, T=100, ticks=200, warm=20):
+    """-> (median ms per tick, instances per rollout launch, the form's name)"""
+    from autorally_amd import capi
+    sols, states = fleet(net, variant, n, K, T)
+    try:
+        capi.control_ticks_batch(sols, states, warm, 1)
+        dt = []
+        for _ in range(ticks):
+            t0 = time.perf_counter()
+            capi.control_ticks_batch(sols, states, 1, 1)
+            dt.append(time.perf_counter() - t0)
+        return 1e3 * float(np.median(dt)), sols[0].debug_launch_info()[0], sols[0].rollout_variant()
+    finally:
+        for s in sols:
+            s.close()
+
+
+def table(nets, n=16, K=1920, T=100, ticks=200, warm=20, ways="abc"):
+    rows = []
+    for net in nets:
+        row = {"net": "-".join(map(str, net)), "n": n, "K": K, "T": T}
+        for key, variant in WAYS:
+            if key not in ways:
+                continue
+            ms, inst, name = tick_ms(net, variant, n, K, T, ticks, warm)
+            row[key + "_ms"], row[key + "_instances"], row[key + "_form"] = ms, inst, name
+        rows.append(row)
+        if set("abc") - set(ways):
+            print("FLEET n=%d K=%d T=%d net=%s: %s" % (n, K, T, row["net"], {k: v for k, v in row.items() if k.endswith("_ms")}), flush=True)
+            continue
+        print("FLEET n=%d K=%d T=%d net=%s: (a) fleet16 %.4f ms [%d per launch]  (b) lds16 %.4f ms  (c) auto (%s) %.4f ms;  b/a %.2f  c/a %.2f" % (
+            n, K, T, row["net"], row["a_ms"], row["a_instances"], row["b_ms"], row["c_form"], row["c_ms"], row["b_ms"] / row["a_ms"],
+            row["c_ms"] / row["a_ms"]), flush=True)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=16)
+    ap.add_argument("--K", type=int, default=1920)
+    ap.add_argument("--T", type=int, default=100)
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--warm", type=int, default=20)
+    ap.add_argument("--ways", default="abc", help="which of (a) fleet16, (b) lds16, (c) auto to run")
+    ap.add_argument("--net", nargs="*", default=["6-32-32-4", "6-64-64-64-64-4"])
+    a = ap.parse_args()
+    from autorally_amd import build as B
+    B.build()
+    rows = table([[int(x) for x in s.split("-")] for s in a.net], a.n, a.K, a.T, a.ticks, a.warm, a.ways)
+    print(json.dumps(rows))
+
+
+if __name__ == "__main__":
+    main()
