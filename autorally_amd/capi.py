@@ -67,6 +67,7 @@ SYMBOLS = [
     "mppi_debug_set_chained_ticks", "mppi_debug_min_cost",
     "mppi_arm", "mppi_arm_batch", "mppi_disarm", "mppi_is_armed", "mppi_debug_launch_info",
     "mppi_trace_rollouts", "mppi_top_rollouts",
+    "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -78,7 +79,8 @@ ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost", "mppi_arm
                 "mppi_is_armed")
 
 # added to version 5 as compatible additions: an older version-5 library (a kernel A/B through MPPI_LIB_PATH) lacks them
-UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_top_rollouts")
+UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_top_rollouts",
+                       "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf")
 
 _lib = None
 
@@ -177,6 +179,11 @@ def lib():
             ip = C.POINTER(C.c_int)
             L.mppi_trace_rollouts.argtypes = [hp, ip, C.c_int, fp, fp, fp, fp, ip]
             L.mppi_top_rollouts.argtypes = [hp, C.c_int, ip]
+        if hasattr(L, "mppi_compute_feedback_gains_batch"):  # added without a version step, like mppi_debug_launch_info
+            fpp = C.POINTER(fp)
+            L.mppi_compute_feedback_gains_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
+            L.mppi_debug_ddp_info.argtypes = [hp, C.POINTER(C.c_int)]
+            L.mppi_debug_device_tanhf.argtypes = [C.c_int, fp, fp, C.c_size_t]
         for s in SYMBOLS:  # every declared symbol of the library's ABI version must be there
             if (v2 or s not in ABI2_SYMBOLS) and (v3 or s not in ABI3_SYMBOLS) and (v4 or s not in ABI4_SYMBOLS) and \
                     (v5 or s not in ABI5_SYMBOLS) and s not in UNVERSIONED_SYMBOLS:
@@ -456,6 +463,12 @@ class Solver:
         self._ck(self.L.mppi_get_feedback_gains(self.h, _fp(fb), _fp(ff), _fp(x), _fp(u), _fp(tc)))
         return dict(feedback=fb, feedforward=ff, x=x, u=u, total_cost=float(tc[0]))
 
+    def debug_ddp_info(self):
+        """mppi_debug_ddp_info: 1 if the handle's last DDP pass ran in the fleet's kernel, 0 if on the host."""
+        on = C.c_int(-1)
+        self._ck(self.L.mppi_debug_ddp_info(self.h, C.byref(on)))
+        return on.value
+
     def debug_cost_raster(self, x, y, heading, width_m=10, height_m=10, ppm=50):
         out = np.zeros((height_m * ppm, width_m * ppm), dtype=np.float32)
         self._ck(self.L.mppi_debug_cost_raster(self.h, x, y, heading, width_m, height_m, ppm, _fp(out), out.size))
@@ -568,6 +581,39 @@ def compute_feedback_gains_pair(sol_a, state_a, sol_b, state_b, targets_a=None, 
                                                   sol_b.h, _fp(_f32(state_b, (7,))), tb[0], tb[1])
     if rc != OK:
         raise MppiError(rc, sol_a.L.mppi_last_error(sol_a.h).decode() + " | " + sol_b.L.mppi_last_error(sol_b.h).decode())
+
+
+def compute_feedback_gains_batch(solvers, states, targets=None):
+    """mppi_compute_feedback_gains_batch: the DDP passes of several Solver objects in one call (one launch per 64 where the library
+    can share it).  targets: None, or one entry per solver -- (state_seq [T][7], control_seq [T][2]) or None (that handle's own
+    nominal replay).  Raises MppiError with every handle's message; the results are read with Solver.feedback_gains()."""
+    n = len(solvers)
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    st = np.ascontiguousarray(np.stack([_f32(x, (7,)) for x in states]), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    txp = tup = None
+    keep = []
+    if targets is not None:
+        txp, tup = (fp * n)(), (fp * n)()
+        for i, (s, t) in enumerate(zip(solvers, targets)):
+            if t is None:
+                continue
+            keep.append((_f32(t[0], (s.T, 7)), _f32(t[1], (s.T, 2))))
+            txp[i], tup[i] = _fp(keep[-1][0]), _fp(keep[-1][1])
+    L = solvers[0].L
+    rc = L.mppi_compute_feedback_gains_batch(hs, _fp(st), txp, tup, n)
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
+
+
+def device_tanhf(x, device=0):
+    """mppi_debug_device_tanhf: the DDP kernel's tanhf of every element of x, computed on the device."""
+    x = _f32(x).ravel()
+    out = np.zeros_like(x)
+    rc = lib().mppi_debug_device_tanhf(int(device), _fp(x), _fp(out), x.size)
+    if rc != OK:
+        raise MppiError(rc, "mppi_debug_device_tanhf")
+    return out
 
 
 def nominal_traj_pair(sol_a, state_a, sol_b, state_b):

@@ -1,5 +1,6 @@
 // abi_host.hip -- the host-side halves of a control tick: nominal trajectory replays (mppi_controller.cu:501-519), DDP
-// feedback gains (:402-445), and the helper thread that takes one of a pair (mppi_set_host_threads).
+// feedback gains (:402-445), and the helper thread that takes one of a pair (mppi_set_host_threads); the DDP passes of a whole
+// fleet in one launch of ddp_fleet_kernel (mppi_compute_feedback_gains_batch: the one entry here that computes on the device).
 #include "abi_internal.hpp"
 
 #include <stdexcept>
@@ -114,6 +115,137 @@ HostHelper &host_helper()
 }
 
 void host_helper_arm() { host_helper().arm(); }
+
+// The batched DDP pass (mppi_compute_feedback_gains_batch -> ddp_fleet_kernel): ONE set of buffers per device beside the device's
+// batch stream, grown on demand and never destroyed -- the instances' inputs (pinned staging -> device, one copy), their results
+// (device -> pinned, one copy) and the kernel's records.  Used under the device's FleetBlock::mu, from staging until the results
+// are unpacked; the stream is idle in them whenever the mutex is free.
+struct DdpFleetWork {
+  float *d_in = nullptr, *d_out = nullptr, *d_work = nullptr, *h_in = nullptr, *h_out = nullptr;
+  size_t in_cap = 0, out_cap = 0, work_cap = 0;  // floats
+};
+static DdpFleetWork g_ddp_work[64];
+
+static hipError_t ddp_grow(float **d, float **h, size_t *cap, size_t need)
+{
+  if (need <= *cap) return hipSuccess;
+  const size_t want = need + need / 2;
+  if (*d) (void)hipFree(*d);
+  if (h && *h) (void)hipHostFree(*h);
+  *d = nullptr;
+  if (h) *h = nullptr;
+  *cap = 0;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(d), sizeof(float) * want);
+  if (e == hipSuccess && h) e = hipHostMalloc(reinterpret_cast<void **>(h), sizeof(float) * want, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    if (*d) (void)hipFree(*d);
+    *d = nullptr;
+    return e;
+  }
+  *cap = want;
+  return hipSuccess;
+}
+
+// The sharing rule of the batched DDP pass, next to fleet_together: two or more handles of the network model with parameters set,
+// all on one device.  Layer lists, T, hz, limits and weights may differ: they are data.  (The basis-function model stays on the
+// host: its Jacobian is fp32 central differences through powf, which is ulp-sensitive.)
+static bool ddp_fleet_together(mppi_handle *const *hs, int n)
+{
+  if (n < 2) return false;
+  for (int i = 0; i < n; i++) {
+    const mppi_handle *h = hs[i];
+    if (h->basis || !h->have_nn || !h->d_theta || !h->d_tracepack || h->cfg.device != hs[0]->cfg.device) return false;
+  }
+  return true;
+}
+
+static size_t align4(size_t floats) { return (floats + 3) & ~(size_t)3; }
+
+// n <= kMaxFleet handles of a ddp_fleet_together set: one launch.  xs / us: every handle's target sequences.  Returns MPPI_OK,
+// MPPI_ERR_STATE when a handle's factorisation failed (that handle alone has no result), or the error that stopped the launch.
+static int ddp_fleet_launch(mppi_handle *const *hs, const float *states, const float *const *xs, const float *const *us, int n)
+{
+  mppi_handle *h0 = hs[0];
+  const int dev = h0->cfg.device;
+  HIPCHK(h0, ensure_device(dev));
+  const hipStream_t S = batch_stream(dev);
+  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+  FleetBlock *fb = fleet_block(dev);
+  if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
+  size_t in_off[kMaxFleet + 1], out_off[kMaxFleet + 1], work_off[kMaxFleet + 1];
+  in_off[0] = out_off[0] = work_off[0] = 0;
+  for (int i = 0; i < n; i++) {
+    in_off[i + 1] = in_off[i] + align4(ddp_fleet_in_floats(hs[i]->T));
+    out_off[i + 1] = out_off[i] + align4(ddp_fleet_out_floats(hs[i]->T));
+    work_off[i + 1] = work_off[i] + align4(ddp_fleet_work_floats(hs[i]->T, hs[i]->net));
+  }
+  std::lock_guard<std::mutex> lk(fb->mu);
+  DdpFleetWork &w = g_ddp_work[dev];
+  if (in_off[n] > w.in_cap || out_off[n] > w.out_cap || work_off[n] > w.work_cap) {
+    HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier pass is behind the buffers; a solve on the stream never reads them
+    HIPCHK(h0, ddp_grow(&w.d_in, &w.h_in, &w.in_cap, in_off[n]));
+    HIPCHK(h0, ddp_grow(&w.d_out, &w.h_out, &w.out_cap, out_off[n]));
+    HIPCHK(h0, ddp_grow(&w.d_work, nullptr, &w.work_cap, work_off[n]));
+  }
+  unsigned char *host = nullptr;
+  HIPCHK(h0, arg_block_stage(fb->args, &host));
+  DdpFleetArgs *da = reinterpret_cast<DdpFleetArgs *>(host);
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    const int T = h->T;
+    float *in = w.h_in + in_off[i];
+    memcpy(in, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+    memcpy(in + 7, xs[i], sizeof(float) * (size_t)T * kStateDim);
+    memcpy(in + 7 + (size_t)7 * T, us[i], sizeof(float) * (size_t)T * kControlDim);
+    DdpFleetArgs &a = da[i];
+    a = DdpFleetArgs{};
+    a.theta = h->d_theta;
+    a.wimg = h->d_tracepack;
+    a.in = w.d_in + in_off[i];
+    a.out = w.d_out + out_off[i];
+    a.work = w.d_work + work_off[i];
+    a.T = T;
+    a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
+    a.img_lds = ddp_fleet_image_in_lds(h->net) ? 1 : 0;
+    a.dt = (float)(1.0 / h->cfg.hz);  // mppi_controller.cu:408
+    for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; a.R[j] = h->ddp_R[j]; }
+    for (int q = 0; q < kStateDim; q++) { a.Q[q] = h->ddp_Q[q]; a.Qf[q] = h->ddp_Qf[q]; }
+    a.net = h->net;
+    h->have_ddp = false;
+    h->ddp_on_device = 1;
+  }
+  hipError_t e = hipMemcpyAsync(w.d_in, w.h_in, sizeof(float) * in_off[n], hipMemcpyHostToDevice, S);
+  if (e == hipSuccess) e = arg_block_send(fb->args, sizeof(DdpFleetArgs) * (size_t)n, S);
+  if (e == hipSuccess) e = launch_ddp_fleet(da, reinterpret_cast<const DdpFleetArgs *>(fb->args.d), n, S);
+  if (e == hipSuccess) e = hipMemcpyAsync(w.h_out, w.d_out, sizeof(float) * out_off[n], hipMemcpyDeviceToHost, S);
+  if (e == hipSuccess) e = hipStreamSynchronize(S);
+  if (e != hipSuccess) {
+    for (int i = 0; i < n; i++) fail(hs[i], MPPI_ERR_HIP, "batched DDP pass", e);
+    return MPPI_ERR_HIP;
+  }
+  int rc = MPPI_OK;
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    const size_t T = (size_t)h->T;
+    const float *o = w.h_out + out_off[i];
+    int status = 0;
+    memcpy(&status, o + 26 * T + 1, sizeof(int));
+    if (status != 0) {
+      rc = fail(h, MPPI_ERR_STATE, "DDP: control Hessian could not be factorised");
+      continue;
+    }
+    DdpResult &r = h->ddp;
+    r.feedback.assign(o, o + 14 * T);
+    r.feedforward.assign(o + 14 * T, o + 16 * T);
+    r.x.assign(o + 16 * T, o + 23 * T);
+    r.u.assign(o + 23 * T, o + 25 * T);
+    r.cost.assign(o + 25 * T, o + 26 * T);
+    r.total_cost = o[26 * T];
+    r.iterations = 1;
+    h->have_ddp = true;
+  }
+  return rc;
+}
 
 }  // namespace mppi_abi
 
@@ -268,6 +400,7 @@ int mppi_compute_feedback_gains(mppi_handle *h, const float state[MPPI_STATE_DIM
   for (int i = 0; i < kStateDim; i++) { p.Q[i] = h->ddp_Q[i]; p.Qf[i] = h->ddp_Qf[i]; }
   p.negate_yaw_der = h->cfg.negate_yaw_der;
   h->have_ddp = false;
+  h->ddp_on_device = 0;
   if (ddp_feedback_gains(net, p, state, xs.data(), us.data(), h->ddp) != 0)
     return fail(h, MPPI_ERR_STATE, "DDP: control Hessian could not be factorised");
   h->have_ddp = true;
@@ -297,6 +430,78 @@ int mppi_compute_feedback_gains_pair(mppi_handle *ha, const float state_a[MPPI_S
   }
   const int rc = mppi_compute_feedback_gains(ha, state_a, target_state_seq_a, target_control_seq_a);
   return rc ? rc : mppi_compute_feedback_gains(hb, state_b, target_state_seq_b, target_control_seq_b);
+}
+
+int mppi_compute_feedback_gains_batch(mppi_handle *const *handles, const float *states, const float *const *target_state_seqs,
+                                      const float *const *target_control_seqs, int n)
+{
+  if (!handles || !states || n < 1) return MPPI_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!handles[i]) return MPPI_ERR_INVALID;
+    for (int q = 0; q < i; q++)
+      if (handles[q] == handles[i]) return fail(handles[i], MPPI_ERR_INVALID, "the same handle twice in one batch");
+  }
+  auto target = [n](const float *const *seqs, int i) -> const float * { return (seqs && i < n) ? seqs[i] : nullptr; };
+  for (int i = 0; i < n; i++)
+    if ((target(target_state_seqs, i) == nullptr) != (target(target_control_seqs, i) == nullptr))
+      return fail(handles[i], MPPI_ERR_INVALID, "give both target sequences or neither");
+  if (!ddp_fleet_together(handles, n)) {
+    // n host passes, the bits of n single calls; every handle is tried, the first error is the call's
+    int rc = MPPI_OK;
+    for (int i = 0; i < n; i++) {
+      const int rci = mppi_compute_feedback_gains(handles[i], states + (size_t)MPPI_STATE_DIM * i, target(target_state_seqs, i),
+                                                  target(target_control_seqs, i));
+      if (rci && !rc) rc = rci;
+    }
+    return rc;
+  }
+  // targets: the caller's, or the handle's nominal trajectory from the host replay, as in the single call
+  std::vector<std::vector<float>> own_x(n), own_u(n);
+  std::vector<const float *> xs(n), us(n);
+  for (int i = 0; i < n; i++) {
+    xs[i] = target(target_state_seqs, i);
+    us[i] = target(target_control_seqs, i);
+    if (xs[i]) continue;
+    mppi_handle *h = handles[i];
+    own_x[i].resize((size_t)h->T * kStateDim);
+    own_u[i].resize((size_t)h->T * kControlDim);
+    const int rc = mppi_nominal_traj(h, states + (size_t)MPPI_STATE_DIM * i, own_x[i].data(), own_u[i].data());
+    if (rc) return rc;
+    xs[i] = own_x[i].data();
+    us[i] = own_u[i].data();
+  }
+  int rc = MPPI_OK;
+  for (int at = 0; at < n; at += kMaxFleet) {  // more than kMaxFleet handles: launches of up to kMaxFleet
+    const int m = std::min(kMaxFleet, n - at);
+    const int rcm = ddp_fleet_launch(handles + at, states + (size_t)MPPI_STATE_DIM * at, xs.data() + at, us.data() + at, m);
+    if (rcm == MPPI_ERR_HIP) return rcm;
+    if (rcm && !rc) rc = rcm;
+  }
+  return rc;
+}
+
+int mppi_debug_ddp_info(const mppi_handle *h, int *on_device)
+{
+  if (!h || !on_device) return MPPI_ERR_INVALID;
+  *on_device = h->ddp_on_device;
+  return MPPI_OK;
+}
+
+int mppi_debug_device_tanhf(int device, const float *in, float *out, size_t n)
+{
+  if (device < 0 || !in || !out || n == 0) return MPPI_ERR_INVALID;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return MPPI_ERR_NO_DEVICE;
+  if (ensure_device(device) != hipSuccess) return MPPI_ERR_HIP;
+  float *d_in = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_in), sizeof(float) * n);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(float) * n);
+  if (e == hipSuccess) e = hipMemcpy(d_in, in, sizeof(float) * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_device_tanhf(d_in, d_out, n, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(float) * n, hipMemcpyDeviceToHost);
+  if (d_in) (void)hipFree(d_in);
+  if (d_out) (void)hipFree(d_out);
+  return e == hipSuccess ? MPPI_OK : MPPI_ERR_HIP;
 }
 
 int mppi_set_host_threads(int n)

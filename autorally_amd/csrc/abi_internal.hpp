@@ -2,7 +2,8 @@
 // functions of one another.  mppi_abi.hip: handle life cycle, setters, getters; abi_forms.hip: which kernel form runs
 // (selection table, names); abi_pack.hip: weight images and generator tables; abi_solve.hip: the solve pipeline (noise,
 // rollout + tail launches, result polling, batched solves); abi_host.hip: the host-side halves of a tick (nominal replays,
-// DDP feedback gains, the helper thread); abi_trace.hip: chosen rollouts of the last solve replayed with their records.
+// DDP feedback gains, the helper thread, the batched DDP pass of a fleet on the device); abi_trace.hip: chosen rollouts of the last
+// solve replayed with their records.
 #pragma once
 // mppi_abi.hip -- host side of libmppi_hip.so: the C ABI of include/mppi_hip.h.
 //
@@ -124,6 +125,7 @@ struct mppi_handle {
   float ddp_Qf[7] = {0, 0, 0, 0, 0, 0, 0};
   DdpResult ddp;
   bool have_ddp = false;
+  int ddp_on_device = 0;  // the last DDP pass ran in ddp_fleet_kernel (mppi_compute_feedback_gains_batch), not on the host
   hipStream_t batch_s = nullptr;  // the device's batch stream, looked up once (mppi_compute_control_batch)
   unsigned *d_counter = nullptr;  // [1 + T] arrival counters of the tail kernel
   float *d_part = nullptr;        // [T][K/64][2] chain results of the tail kernel when K > 4096
@@ -309,6 +311,14 @@ inline bool form_has_gate(Form f)
   return form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44 || f == Form::BfRow;
 }
 hipStream_t batch_stream(int device);
+// abi_solve.hip: the argument block beside a device's batch stream, shared by every fleet on the device and never destroyed.
+// mu: held while a batched solve, or a batched DDP pass, stages, sends and launches (the DDP pass: until its results are back)
+struct FleetBlock {
+  std::mutex mu;
+  ArgBlock args;
+  bool ready = false;
+};
+FleetBlock *fleet_block(int device);
 void fill_cost_args(const mppi_handle *h, CostArgs &c);
 void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, RolloutArgs &a);
 // a rollout launch that is followed by its tail kernel: the tag its minimum cost travels under (a.min_cost, a.min_cost_tag)

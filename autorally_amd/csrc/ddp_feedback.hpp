@@ -5,6 +5,8 @@
 // TrackingTerminalCost (ddp/ddp_tracking_costs.h:7-117) and the analytic network Jacobian
 // NeuralNetModel::computeGrad (PI/neural_net_model.cu:233-264).  Like the reference this is host
 // code: one forward rollout, T Jacobians, T-1 sequential 7x7 / 2x7 Riccati steps, one forward pass.
+// ddp_fleet.hip restates this pass for the network model on the device, operation for operation (one workgroup per controller of
+// a fleet): a change to the arithmetic of ddp_feedback.cpp -- an order, an association, a clamp -- has to be made there too.
 #pragma once
 
 #include <vector>

@@ -351,4 +351,35 @@ hipError_t launch_noise_fleet(const NoiseFleetDesc *h_desc, const NoiseFleetDesc
 hipError_t launch_noise_init(uint32_t *rng, int K, const uint32_t base[6], const uint32_t *sub,
                              int sub_bits, const uint32_t *one, uint64_t offset, hipStream_t stream);
 
+// ddp_fleet.hip: the DDP feedback gains (ddp_feedback.cpp's pass for the network model) of n <= kMaxFleet independent controllers
+// in one launch, one workgroup per controller, the instances' argument blocks an array in device memory.
+//   in:   [7] x0 | [T][7] target_x | [T][2] target_u
+//   out:  DdpResult's arrays -- [T][2][7] feedback | [T][2] feedforward | [T][7] x | [T][2] u | [T] cost -- then total_cost and one
+//         status word (0: done; 1: a 2 x 2 control Hessian could not be factorised, the arrays are void)
+//   work: [T][7] x and [T][2] u of the initial rollout | [T][2] sin, cos of its headings | [T][72] df and dL | [T][hidden] tanh values
+struct DdpFleetArgs {
+  const float *theta;  // the weights as the reference packs them (row-major; the Jacobians)
+  const float *wimg;   // pack_trace_weights: every W transposed (the forward passes)
+  const float *in;
+  float *out, *work;
+  int T, negate_yaw_der;
+  int img_lds;         // the image is copied to LDS (ddp_fleet_image_in_lds)
+  float dt;
+  float u_lo[2], u_hi[2], Q[7], R[2], Qf[7];
+  NetDesc net;
+};
+__host__ __device__ inline int ddp_fleet_hidden(const NetDesc &net)
+{
+  int s = 0;
+  for (int l = 1; l + 1 < net.n_layers; l++) s += net.layers[l];
+  return s;
+}
+inline size_t ddp_fleet_in_floats(int T) { return 7 + (size_t)9 * T; }
+inline size_t ddp_fleet_out_floats(int T) { return (size_t)26 * T + 2; }
+inline size_t ddp_fleet_work_floats(int T, const NetDesc &net) { return (size_t)T * (7 + 2 + 2 + 72 + ddp_fleet_hidden(net)); }
+bool ddp_fleet_image_in_lds(const NetDesc &net);
+hipError_t launch_ddp_fleet(const DdpFleetArgs *h_inst, const DdpFleetArgs *d_inst, int n, hipStream_t stream);
+// out[i] = tanhf_scalar(in[i]) on the device (mppi_debug_device_tanhf)
+hipError_t launch_device_tanhf(const float *in, float *out, size_t n, hipStream_t stream);
+
 }  // namespace mppi

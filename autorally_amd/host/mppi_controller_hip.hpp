@@ -701,6 +701,35 @@ class MPPIControllerT {
     }
     for (int c = 0; c < n; c++) controllers[c]->computeNominalTraj(controllers[c]->solve_state_);
   }
+  // computeFeedbackGains(state) of every controller of the fleet in one call (mppi_compute_feedback_gains_batch): each tracks its
+  // own state_solution_ / control_solution_ from states[c].  Two or more network-model controllers on one device run in ONE kernel
+  // launch, one workgroup per controller; any other set runs the host passes of n single calls.  A controller whose control
+  // Hessian cannot be factorised makes the call throw (the reference exits); the others' gains are fetched first.
+  static void computeFeedbackGainsFleet(MPPIControllerT *const *controllers, int n, const float *states)
+  {
+    if (n < 1) return;
+    std::vector<mppi_handle *> hs((size_t)n);
+    std::vector<const float *> xs((size_t)n), us((size_t)n);
+    for (int c = 0; c < n; c++) {
+      controllers[c]->syncParams(false);
+      hs[(size_t)c] = controllers[c]->h_;
+      xs[(size_t)c] = controllers[c]->state_solution_.data();
+      us[(size_t)c] = controllers[c]->control_solution_.data();
+    }
+    const int rc = mppi_compute_feedback_gains_batch(hs.data(), states, xs.data(), us.data(), n);
+    if (rc != MPPI_OK && rc != MPPI_ERR_STATE) controllers[0]->ck(rc);
+    std::string failed;
+    for (int c = 0; c < n; c++) {
+      const char *e = mppi_last_error(controllers[c]->h_);
+      const std::string why = e ? e : "";  // (the getter below leaves its own message on a handle without a result)
+      if (mppi_get_feedback_gains(controllers[c]->h_, nullptr, nullptr, nullptr, nullptr, nullptr) == MPPI_OK) {
+        controllers[c]->fetchFeedbackGains();
+      } else {
+        failed += std::string(failed.empty() ? "" : " | ") + "controller " + std::to_string(c) + ": " + why;
+      }
+    }
+    if (rc != MPPI_OK) throw std::runtime_error(std::string("libmppi_hip: ") + mppi_strerror(rc) + " (" + failed + ")");
+  }
   // Solve-ahead (mppi_arm): this controller's NEXT solve is enqueued now, gated -- its kernels start and wait at most max_wait_s
   // for the next startControl / computeControl, which then opens the gate with its state instead of launching.  Results are
   // bit for bit the same.  MPPI_ERR_UNSUPPORTED (no gated form for this configuration) is no error: the solve launches as before.

@@ -61,6 +61,8 @@ extern "C" {
 /*    (still 5) + rollout variant "fleet16", name "mfma16x16x4_fleet_l<N>_w<W>": "lds16"'s wavefront, image and lists with the argument
  *    block read from device memory; 2..64 handles forced to it share the launches of mppi_compute_control_batch (one generator, one
  *    rollout, one tail launch per iteration); no new export, no gated form, the automatic choice does not change. */
+/*    (still 5) + mppi_compute_feedback_gains_batch, mppi_debug_ddp_info, mppi_debug_device_tanhf (the DDP feedback gains of a fleet
+ *    in one launch; compatible additions, the single and the pair call are unchanged). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -322,6 +324,30 @@ int mppi_get_feedback_gains(mppi_handle *h, float *feedback, float *feedforward,
 int mppi_compute_feedback_gains_pair(mppi_handle *ha, const float state_a[MPPI_STATE_DIM], const float *target_state_seq_a,
                                      const float *target_control_seq_a, mppi_handle *hb, const float state_b[MPPI_STATE_DIM],
                                      const float *target_state_seq_b, const float *target_control_seq_b);
+
+/* computeFeedbackGains of a whole fleet in one call: handles[n], states [n][7], the targets of handle i at
+ * target_state_seqs[i] / target_control_seqs[i].  Either array may be NULL as a whole, and entry i of both may be NULL together:
+ * that handle tracks its nominal trajectory from the host replay, as in the single call.  Results land in every handle as after
+ * its own mppi_compute_feedback_gains (mppi_get_feedback_gains is unchanged).
+ * Sharing rule: n >= 2 handles of the network model with parameters set, all on one device, run ON THE DEVICE, one workgroup per
+ * controller in one launch (ddp_fleet_kernel; more than 64 handles: launches of up to 64) -- layer lists, T, hz, limits and
+ * weights may differ per handle.  The kernel restates the host pass operation for operation (its tanhf returns libm's bits); only
+ * sinf / cosf of the heading are the rounded double results, not glibc's floats (1 ulp apart in 1.3 % of headings), so the gains
+ * agree with the single call's far inside the bound both are held to, not bit for bit.  Anything else -- n = 1, a basis-function
+ * handle in the set, handles on several devices, a handle without parameters -- runs n host passes with the bits (and errors) of n
+ * single calls; mppi_debug_ddp_info tells which it was.
+ * A handle whose factorisation fails has no result (mppi_get_feedback_gains fails) and its own mppi_last_error; the call then
+ * returns MPPI_ERR_STATE and every other handle keeps a valid result.  The call uses the device's batch stream and blocks until
+ * the results are back; it touches no handle's solve state (with targets given a pending or armed solve of the same handles is
+ * untouched; without, the nominal replay collects the handle's pending solve as the single call does). */
+int mppi_compute_feedback_gains_batch(mppi_handle *const *handles, const float *states, const float *const *target_state_seqs,
+                                      const float *const *target_control_seqs, int n);
+/* Test / tooling hook: *on_device = 1 if the handle's most recent DDP pass ran in the fleet's kernel, 0 if on the host (or none
+ * yet).  MPPI_ERR_INVALID for a NULL argument. */
+int mppi_debug_ddp_info(const mppi_handle *h, int *on_device);
+/* Test hook: out[i] = the DDP kernel's tanhf of in[i], computed on `device` (n floats; the text of csrc/tanhf_scalar.hpp, which has
+ * to return the C library's bits).  MPPI_ERR_INVALID for a NULL pointer, n = 0 or a negative device. */
+int mppi_debug_device_tanhf(int device, const float *in, float *out, size_t n);
 
 /* Host threads the library may use for the host-side work of a tick that comes in pairs (mppi_nominal_traj_pair,
  * mppi_compute_feedback_gains_pair): 1 (default) = the caller's thread only (the reference's optimizer thread does everything,

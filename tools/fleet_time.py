@@ -5,7 +5,12 @@ tick for the whole fleet) against the same handles solved one by one.
 
 n distinct oval instances with generator noise; the median wall time of a tick (mppi_control_ticks_batch, one tick, stride 1) over
 `ticks` ticks after `warm` warm ones, three ways: (a) every handle forced to "fleet16"; (b) forced to "lds16" -- the same
-wavefront, handle by handle; (c) "auto" (row_tree / m44, handle by handle).  Prints one line per network and a JSON line."""
+wavefront, handle by handle; (c) "auto" (row_tree / m44, handle by handle).  Prints one line per network and a JSON line.
+
+    python tools/fleet_time.py --ddp [--T 100] [--ticks 200] [--net ...]
+
+The DDP feedback gains of the fleet instead (n = 2, 4, 16, 64): mppi_compute_feedback_gains_batch -- one launch of ddp_fleet_kernel --
+against n single calls on one host thread and against the pair entry with mppi_set_host_threads(2); median of `ticks` calls."""
 import argparse
 import json
 import os
@@ -79,6 +84,64 @@ def table(nets, n=16, K=1920, T=100, ticks=200, warm=20, ways="abc"):
     return rows
 
 
+def ddp_ms(net, n, K=64, T=100, calls=200, warm=10):
+    """The DDP feedback gains of n handles, three ways, each the median wall time of `calls` calls after `warm` warm ones: the batch
+    entry (one launch for the fleet), n single calls on one host thread, n / 2 pair calls with mppi_set_host_threads(2).  Every way
+    tracks the same given targets (each handle's nominal trajectory), so the time is the DDP pass's alone."""
+    from autorally_amd import capi
+    sols, states = fleet(net, "auto", n, K, T)
+    try:
+        targets = [s.nominal_traj(st) for s, st in zip(sols, states)]
+
+        def median(fn):
+            for _ in range(warm):
+                fn()
+            dt = []
+            for _ in range(calls):
+                t0 = time.perf_counter()
+                fn()
+                dt.append(time.perf_counter() - t0)
+            return 1e3 * float(np.median(dt))
+
+        def single():
+            for s, st, (tx, tu) in zip(sols, states, targets):
+                s.L.mppi_compute_feedback_gains(s.h, capi._fp(st), capi._fp(tx), capi._fp(tu))
+
+        def pairs():
+            for i in range(0, n - 1, 2):
+                capi.compute_feedback_gains_pair(sols[i], states[i], sols[i + 1], states[i + 1], targets[i], targets[i + 1])
+            if n % 2:
+                sols[-1].L.mppi_compute_feedback_gains(sols[-1].h, capi._fp(states[-1]), capi._fp(targets[-1][0]), capi._fp(targets[-1][1]))
+
+        row = {"net": "-".join(map(str, net)), "n": n, "T": T}
+        row["batch_ms"] = median(lambda: capi.compute_feedback_gains_batch(sols, states, targets))
+        row["on_device"] = sols[0].debug_ddp_info()
+        capi.set_host_threads(1)
+        row["host1_ms"] = median(single)
+        capi.set_host_threads(2)
+        try:
+            row["host2_ms"] = median(pairs)
+        finally:
+            capi.set_host_threads(1)
+        return row
+    finally:
+        for s in sols:
+            s.close()
+
+
+def ddp_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
+    rows = []
+    for net in nets:
+        for n in ns:
+            row = ddp_ms(net, n, T=T, calls=calls)
+            rows.append(row)
+            print("FLEET DDP n=%d T=%d net=%s: batch %.4f ms (on_device %d)  host, 1 thread %.4f ms  host, 2 threads (pairs) %.4f ms;  "
+                  "host1/batch %.2f  host2/batch %.2f" % (n, T, row["net"], row["batch_ms"], row["on_device"], row["host1_ms"],
+                                                         row["host2_ms"], row["host1_ms"] / row["batch_ms"], row["host2_ms"] / row["batch_ms"]),
+                  flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=16)
@@ -88,9 +151,14 @@ def main():
     ap.add_argument("--warm", type=int, default=20)
     ap.add_argument("--ways", default="abc", help="which of (a) fleet16, (b) lds16, (c) auto to run")
     ap.add_argument("--net", nargs="*", default=["6-32-32-4", "6-64-64-64-64-4"])
+    ap.add_argument("--ddp", action="store_true", help="the DDP feedback gains of the fleet instead: the batch entry against the host "
+                    "passes, n = 2, 4, 16, 64 (mppi_compute_feedback_gains_batch)")
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
+    if a.ddp:
+        print(json.dumps(ddp_table([[int(x) for x in s.split("-")] for s in a.net], T=a.T, calls=a.ticks)))
+        return
     rows = table([[int(x) for x in s.split("-")] for s in a.net], a.n, a.K, a.T, a.ticks, a.warm, a.ways)
     print(json.dumps(rows))
 
