@@ -68,6 +68,7 @@ SYMBOLS = [
     "mppi_arm", "mppi_arm_batch", "mppi_disarm", "mppi_is_armed", "mppi_debug_launch_info",
     "mppi_trace_rollouts", "mppi_top_rollouts",
     "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
+    "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -80,7 +81,8 @@ ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost", "mppi_arm
 
 # added to version 5 as compatible additions: an older version-5 library (a kernel A/B through MPPI_LIB_PATH) lacks them
 UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_top_rollouts",
-                       "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf")
+                       "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
+                       "mppi_nominal_traj_batch", "mppi_debug_nominal_info")
 
 _lib = None
 
@@ -184,6 +186,10 @@ def lib():
             L.mppi_compute_feedback_gains_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
             L.mppi_debug_ddp_info.argtypes = [hp, C.POINTER(C.c_int)]
             L.mppi_debug_device_tanhf.argtypes = [C.c_int, fp, fp, C.c_size_t]
+        if hasattr(L, "mppi_nominal_traj_batch"):  # added without a version step, like mppi_debug_launch_info
+            fpp = C.POINTER(fp)
+            L.mppi_nominal_traj_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
+            L.mppi_debug_nominal_info.argtypes = [hp, C.POINTER(C.c_int)]
         for s in SYMBOLS:  # every declared symbol of the library's ABI version must be there
             if (v2 or s not in ABI2_SYMBOLS) and (v3 or s not in ABI3_SYMBOLS) and (v4 or s not in ABI4_SYMBOLS) and \
                     (v5 or s not in ABI5_SYMBOLS) and s not in UNVERSIONED_SYMBOLS:
@@ -442,6 +448,12 @@ class Solver:
         self._ck(self.L.mppi_nominal_traj(self.h, _fp(_f32(state, (7,))), _fp(ss), _fp(cs)))
         return ss, cs
 
+    def debug_nominal_info(self):
+        """mppi_debug_nominal_info: 1 if the handle's last nominal replay ran in the fleet's kernel, 0 if on the host."""
+        on = C.c_int(-1)
+        self._ck(self.L.mppi_debug_nominal_info(self.h, C.byref(on)))
+        return on.value
+
     def set_ddp_weights(self, Q, R, Qf):
         self._ck(self.L.mppi_set_ddp_weights(self.h, _fp(_f32(Q, (7,))), _fp(_f32(R, (2,))), _fp(_f32(Qf, (7,)))))
 
@@ -613,6 +625,24 @@ def device_tanhf(x, device=0):
     rc = lib().mppi_debug_device_tanhf(int(device), _fp(x), _fp(out), x.size)
     if rc != OK:
         raise MppiError(rc, "mppi_debug_device_tanhf")
+    return out
+
+
+def nominal_traj_batch(solvers, states):
+    """mppi_nominal_traj_batch: the nominal replays of several Solver objects in one call (one launch per 64 where the library can
+    share it).  Returns [(state_seq [T][7], control_seq [T][2])] in the solvers' order; raises MppiError with every handle's
+    message (an empty fleet: MPPI_ERR_INVALID, as the library answers n < 1)."""
+    n = len(solvers)
+    if n < 1 or len(states) != n:
+        raise MppiError(ERR_INVALID, "nominal_traj_batch: %d solvers, %d states" % (n, len(states)))
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    st = np.ascontiguousarray(np.stack([_f32(x, (7,)) for x in states]), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    out = [(np.zeros((s.T, 7), np.float32), np.zeros((s.T, 2), np.float32)) for s in solvers]
+    ssp, csp = (fp * n)(*[_fp(o[0]) for o in out]), (fp * n)(*[_fp(o[1]) for o in out])
+    rc = solvers[0].L.mppi_nominal_traj_batch(hs, _fp(st), ssp, csp, n)
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
     return out
 
 

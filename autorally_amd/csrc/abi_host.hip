@@ -1,6 +1,7 @@
 // abi_host.hip -- the host-side halves of a control tick: nominal trajectory replays (mppi_controller.cu:501-519), DDP
 // feedback gains (:402-445), and the helper thread that takes one of a pair (mppi_set_host_threads); the DDP passes of a whole
-// fleet in one launch of ddp_fleet_kernel (mppi_compute_feedback_gains_batch: the one entry here that computes on the device).
+// fleet in one launch of ddp_fleet_kernel (mppi_compute_feedback_gains_batch) and its nominal replays in one launch of
+// nominal_fleet_kernel (mppi_nominal_traj_batch): the two entries here that compute on the device.
 #include "abi_internal.hpp"
 
 #include <stdexcept>
@@ -247,6 +248,98 @@ static int ddp_fleet_launch(mppi_handle *const *hs, const float *states, const f
   return rc;
 }
 
+// The batched nominal replay (mppi_nominal_traj_batch -> nominal_fleet_kernel): its own set of buffers per device, used exactly as
+// the DDP pass uses DdpFleetWork -- under the device's FleetBlock::mu, on the batch stream, grown on demand, never destroyed.
+struct NominalFleetWork {
+  float *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
+  size_t in_cap = 0, out_cap = 0;  // floats
+};
+static NominalFleetWork g_nominal_work[64];
+
+// The sharing rule of the batched nominal replay, beside ddp_fleet_together: two or more handles of the network model with
+// parameters set and a trace image, all on one device.  Everything else about a controller is data.  (The basis-function model
+// stays on the host: its functions go through powf, which is ulp-sensitive -- the reason ddp_fleet_together gives.)
+static bool nominal_fleet_together(mppi_handle *const *hs, int n)
+{
+  if (n < 2) return false;
+  for (int i = 0; i < n; i++) {
+    const mppi_handle *h = hs[i];
+    if (h->basis || !h->have_nn || !h->d_tracepack || h->cfg.device != hs[0]->cfg.device) return false;
+  }
+  return true;
+}
+
+// The handles of a nominal_fleet_together set: one input copy, launches of up to kMaxFleet (each with its own slot of the argument
+// ring), one result copy, one synchronise.  Inputs are every handle's HOST control sequence and the call's state; the caller's
+// buffers are written only after EVERY launch has succeeded: an error leaves all of them as they were.
+static int nominal_fleet_launch(mppi_handle *const *hs, const float *states, float *const *state_seqs, float *const *control_seqs, int n)
+{
+  mppi_handle *h0 = hs[0];
+  const int dev = h0->cfg.device;
+  HIPCHK(h0, ensure_device(dev));
+  const hipStream_t S = batch_stream(dev);
+  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+  FleetBlock *fb = fleet_block(dev);
+  if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
+  std::vector<size_t> in_off((size_t)n + 1), out_off((size_t)n + 1);
+  in_off[0] = out_off[0] = 0;
+  for (int i = 0; i < n; i++) {
+    in_off[i + 1] = in_off[i] + align4(nominal_fleet_in_floats(hs[i]->T));
+    out_off[i + 1] = out_off[i] + align4(nominal_fleet_out_floats(hs[i]->T));
+  }
+  std::lock_guard<std::mutex> lk(fb->mu);
+  NominalFleetWork &w = g_nominal_work[dev];
+  if (in_off[n] > w.in_cap || out_off[n] > w.out_cap) {
+    HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier replay is behind the buffers; nothing else on the stream reads them
+    HIPCHK(h0, ddp_grow(&w.d_in, &w.h_in, &w.in_cap, in_off[n]));
+    HIPCHK(h0, ddp_grow(&w.d_out, &w.h_out, &w.out_cap, out_off[n]));
+  }
+  for (int i = 0; i < n; i++) {
+    float *in = w.h_in + in_off[i];
+    memcpy(in, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+    memcpy(in + 7, hs[i]->U.data(), sizeof(float) * (size_t)hs[i]->T * kControlDim);
+  }
+  hipError_t e = hipMemcpyAsync(w.d_in, w.h_in, sizeof(float) * in_off[n], hipMemcpyHostToDevice, S);
+  for (int at = 0; at < n && e == hipSuccess; at += kMaxFleet) {
+    const int m = std::min(kMaxFleet, n - at);
+    unsigned char *host = nullptr;
+    e = arg_block_stage(fb->args, &host);
+    if (e != hipSuccess) break;
+    NominalFleetArgs *na = reinterpret_cast<NominalFleetArgs *>(host);
+    for (int i = at; i < at + m; i++) {
+      const mppi_handle *h = hs[i];
+      NominalFleetArgs &a = na[i - at];
+      a = NominalFleetArgs{};
+      a.wimg = h->d_tracepack;
+      a.in = w.d_in + in_off[i];
+      a.out = w.d_out + out_off[i];
+      a.T = h->T;
+      a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
+      a.img_lds = nominal_fleet_image_in_lds(h->net) ? 1 : 0;
+      a.dt = h->dt;
+      for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; }
+      a.net = h->net;
+    }
+    e = arg_block_send(fb->args, sizeof(NominalFleetArgs) * (size_t)m, S);  // ordered behind the launch before it, which reads the block
+    if (e == hipSuccess) e = launch_nominal_fleet(na, reinterpret_cast<const NominalFleetArgs *>(fb->args.d), m, S);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(w.h_out, w.d_out, sizeof(float) * out_off[n], hipMemcpyDeviceToHost, S);
+  if (e == hipSuccess) e = hipStreamSynchronize(S);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(S);  // nothing enqueued so far is left behind the buffers
+    for (int i = 0; i < n; i++) fail(hs[i], MPPI_ERR_HIP, "batched nominal replay", e);
+    return MPPI_ERR_HIP;
+  }
+  for (int i = 0; i < n; i++) {
+    const size_t T = (size_t)hs[i]->T;
+    const float *o = w.h_out + out_off[i];
+    memcpy(state_seqs[i], o, sizeof(float) * 7 * T);
+    memcpy(control_seqs[i], o + 7 * T, sizeof(float) * 2 * T);
+    hs[i]->nominal_on_device = 1;
+  }
+  return MPPI_OK;
+}
+
 }  // namespace mppi_abi
 
 extern "C" {
@@ -259,6 +352,7 @@ int mppi_nominal_traj(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
     int rc = mppi_synchronize(h);
     if (rc) return rc;
   }
+  h->nominal_on_device = 0;
   // computeNominalTraj (mppi_controller.cu:501-519) -> host updateState (neural_net_model.cu:280-288):
   // like the reference this replay runs on the host (T sequential 1.4k-MAC steps).
   float s[kStateDim];
@@ -330,6 +424,7 @@ int mppi_nominal_traj_pair(mppi_handle *ha, const float state_a[MPPI_STATE_DIM],
       if (rc) return rc;
     }
   mppi_handle *hs[2] = {ha, hb};
+  ha->nominal_on_device = hb->nominal_on_device = 0;
   float *sseq[2] = {state_seq_a, state_seq_b}, *cseq[2] = {control_seq_a, control_seq_b};
   float s[2][kStateDim], sd[2][kStateDim], in6[2][6];
   for (int i = 0; i < kStateDim; i++) { s[0][i] = state_a[i]; s[1][i] = state_b[i]; }
@@ -354,6 +449,41 @@ int mppi_nominal_traj_pair(mppi_handle *ha, const float state_a[MPPI_STATE_DIM],
     for (int q = 0; q < 2; q++)
       for (int i = 0; i < kStateDim; i++) s[q][i] = fmaf(sd[q][i], hs[q]->dt, s[q][i]);
   }
+  return MPPI_OK;
+}
+
+int mppi_nominal_traj_batch(mppi_handle *const *handles, const float *states, float *const *state_seqs, float *const *control_seqs,
+                            int n)
+{
+  // first pass: every argument, then every handle's readiness, then every pending solve; only then an output or a launch
+  if (!handles || !states || !state_seqs || !control_seqs || n < 1) return MPPI_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!handles[i] || !state_seqs[i] || !control_seqs[i]) return MPPI_ERR_INVALID;
+    for (int q = 0; q < i; q++)
+      if (handles[q] == handles[i]) return fail(handles[i], MPPI_ERR_INVALID, "the same handle twice in one batch");
+  }
+  for (int i = 0; i < n; i++)
+    if (!handles[i]->have_nn) return fail(handles[i], MPPI_ERR_STATE, "mppi_set_nn_params has not been called");
+  for (int i = 0; i < n; i++)
+    if (handles[i]->pending) {
+      const int rc = mppi_synchronize(handles[i]);
+      if (rc) return rc;
+    }
+  if (!nominal_fleet_together(handles, n)) {
+    // n host replays, the bits of n single calls
+    for (int i = 0; i < n; i++) {
+      const int rc = mppi_nominal_traj(handles[i], states + (size_t)MPPI_STATE_DIM * i, state_seqs[i], control_seqs[i]);
+      if (rc) return rc;
+    }
+    return MPPI_OK;
+  }
+  return nominal_fleet_launch(handles, states, state_seqs, control_seqs, n);  // more than kMaxFleet handles: launches of up to kMaxFleet
+}
+
+int mppi_debug_nominal_info(const mppi_handle *h, int *on_device)
+{
+  if (!h || !on_device) return MPPI_ERR_INVALID;
+  *on_device = h->nominal_on_device;
   return MPPI_OK;
 }
 

@@ -2,7 +2,7 @@
 // functions of one another.  mppi_abi.hip: handle life cycle, setters, getters; abi_forms.hip: which kernel form runs
 // (selection table, names); abi_pack.hip: weight images and generator tables; abi_solve.hip: the solve pipeline (noise,
 // rollout + tail launches, result polling, batched solves); abi_host.hip: the host-side halves of a tick (nominal replays,
-// DDP feedback gains, the helper thread, the batched DDP pass of a fleet on the device); abi_trace.hip: chosen rollouts of the last
+// DDP feedback gains, the helper thread, the batched DDP pass and the batched nominal replay of a fleet on the device); abi_trace.hip: chosen rollouts of the last
 // solve replayed with their records.
 #pragma once
 // mppi_abi.hip -- host side of libmppi_hip.so: the C ABI of include/mppi_hip.h.
@@ -126,6 +126,7 @@ struct mppi_handle {
   DdpResult ddp;
   bool have_ddp = false;
   int ddp_on_device = 0;  // the last DDP pass ran in ddp_fleet_kernel (mppi_compute_feedback_gains_batch), not on the host
+  int nominal_on_device = 0;  // the last nominal replay ran in nominal_fleet_kernel (mppi_nominal_traj_batch), not on the host
   hipStream_t batch_s = nullptr;  // the device's batch stream, looked up once (mppi_compute_control_batch)
   unsigned *d_counter = nullptr;  // [1 + T] arrival counters of the tail kernel
   float *d_part = nullptr;        // [T][K/64][2] chain results of the tail kernel when K > 4096
@@ -312,7 +313,8 @@ inline bool form_has_gate(Form f)
 }
 hipStream_t batch_stream(int device);
 // abi_solve.hip: the argument block beside a device's batch stream, shared by every fleet on the device and never destroyed.
-// mu: held while a batched solve, or a batched DDP pass, stages, sends and launches (the DDP pass: until its results are back)
+// mu: held while a batched solve, a batched DDP pass or a batched nominal replay stages, sends and launches (the latter two: until
+// their results are back)
 struct FleetBlock {
   std::mutex mu;
   ArgBlock args;

@@ -65,7 +65,8 @@ hipError_t arg_block_send(ArgBlock &b, size_t bytes, hipStream_t stream)
 
 // The fleet16 form's argument blocks of a batched solve: ONE block per device beside the device's batch stream, shared by every
 // fleet on the device and never destroyed -- per iteration the rollout, tail and generator blocks of up to kMaxFleet instances,
-// packed for the fleet's n (FleetBlock: abi_internal.hpp).  A batched DDP pass (abi_host.hip) sends its instances' blocks through it too.
+// packed for the fleet's n (FleetBlock: abi_internal.hpp).  A batched DDP pass and a batched nominal replay (abi_host.hip) send their
+// instances' blocks through it too.
 static FleetBlock g_fleet[64];
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 static size_t fleet_tail_offset(int n) { return align16(sizeof(RolloutArgs) * (size_t)n); }
@@ -76,8 +77,10 @@ FleetBlock *fleet_block(int device)
   if (device < 0 || device >= 64) return nullptr;
   std::lock_guard<std::mutex> lk(g_batch_mu);
   FleetBlock &fb = g_fleet[device];
-  // (the larger of the two uses: a batched solve's blocks, a batched DDP pass's)
-  if (!fb.ready) fb.ready = arg_block_create(fb.args, std::max(fleet_bytes(kMaxFleet), sizeof(DdpFleetArgs) * (size_t)kMaxFleet)) == hipSuccess;
+  // (the largest of the three uses: a batched solve's blocks, a batched DDP pass's, a batched nominal replay's)
+  if (!fb.ready)
+    fb.ready = arg_block_create(fb.args, std::max({fleet_bytes(kMaxFleet), sizeof(DdpFleetArgs) * (size_t)kMaxFleet,
+                                                   sizeof(NominalFleetArgs) * (size_t)kMaxFleet})) == hipSuccess;
   return fb.ready ? &fb : nullptr;
 }
 

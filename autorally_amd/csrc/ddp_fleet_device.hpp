@@ -1,6 +1,8 @@
 // ddp_fleet_device.hpp -- device functions of ddp_fleet.hip: ddp_feedback.cpp's pass for the network model on one workgroup,
 // operation for operation.  Every sum is the host file's: k ascending from 0.0f with a SEPARATE multiply and add (the library is
 // compiled -ffp-contract=off: write no fmaf here), the host's association, IEEE division, tanhf_scalar for tanhf.
+// nominal_fleet.hip shares the forward layer (ddp_layer) with FMA = true: mppi_nominal_traj's arithmetic, where every multiply-add
+// of a neuron's sum is one fmaf (host_net.hpp).  FMA = false is the DDP pass's text, unchanged.
 #pragma once
 #include "mppi_kernels.hpp"
 #include "mppi_device.hpp"
@@ -40,7 +42,7 @@ __device__ __forceinline__ void ddp_sincos(float psi, float &sn, float &cs)
 // b its biases: s = 0, k ascending s = s + W[j][k] * a[k], then s + b[j], then tanhf on a hidden layer.  th: where a hidden layer's
 // tanh values are kept for the Jacobian (nullptr: not kept).  A lane past the layer's width walks the last neuron's weights and
 // stores nothing.  The skeleton (weights requested kDdpAhead k steps ahead, activations as broadcast reads) is rollout_trace.hip's.
-template <int C>
+template <int C, bool FMA = false>
 __device__ __forceinline__ void ddp_layer(const float *Wt, const float *b, int nin, int nout, bool hidden, const float *cur,
                                           float *nxt, float *th, int lane)
 {
@@ -81,12 +83,18 @@ __device__ __forceinline__ void ddp_layer(const float *Wt, const float *b, int n
 #pragma unroll
     for (int u = 0; u < kDdpAhead; u++)
 #pragma unroll
-      for (int c = 0; c < C; c++) acc[c] = acc[c] + wc[u][c] * x[u];
+      for (int c = 0; c < C; c++) {
+        if constexpr (FMA) acc[c] = fmaf(wc[u][c], x[u], acc[c]);
+        else acc[c] = acc[c] + wc[u][c] * x[u];
+      }
   }
   for (int k = full; k < nin; k++) {  // the ragged end, one k at a time
     const float x = cur[k];
 #pragma unroll
-    for (int c = 0; c < C; c++) acc[c] = acc[c] + Wt[k * nout + jj[c]] * x;
+    for (int c = 0; c < C; c++) {
+      if constexpr (FMA) acc[c] = fmaf(Wt[k * nout + jj[c]], x, acc[c]);
+      else acc[c] = acc[c] + Wt[k * nout + jj[c]] * x;
+    }
   }
 #pragma unroll
   for (int c = 0; c < C; c++) {

@@ -382,4 +382,23 @@ hipError_t launch_ddp_fleet(const DdpFleetArgs *h_inst, const DdpFleetArgs *d_in
 // out[i] = tanhf_scalar(in[i]) on the device (mppi_debug_device_tanhf)
 hipError_t launch_device_tanhf(const float *in, float *out, size_t n, hipStream_t stream);
 
+// nominal_fleet.hip: the nominal trajectories (mppi_nominal_traj's replay for the network model) of n <= kMaxFleet independent
+// controllers in one launch, one workgroup per controller, the instances' argument blocks an array in device memory.
+//   in:   [7] state | [T][2] the control sequence (before the clamp)
+//   out:  [T][7] state_seq | [T][2] control_seq (clamped)
+struct NominalFleetArgs {
+  const float *wimg;   // pack_trace_weights: every W transposed
+  const float *in;
+  float *out;
+  int T, negate_yaw_der;
+  int img_lds;         // the image is copied to LDS (nominal_fleet_image_in_lds)
+  float dt;
+  float u_lo[2], u_hi[2];
+  NetDesc net;
+};
+inline size_t nominal_fleet_in_floats(int T) { return 7 + (size_t)2 * T; }
+inline size_t nominal_fleet_out_floats(int T) { return (size_t)9 * T; }
+bool nominal_fleet_image_in_lds(const NetDesc &net);
+hipError_t launch_nominal_fleet(const NominalFleetArgs *h_inst, const NominalFleetArgs *d_inst, int n, hipStream_t stream);
+
 }  // namespace mppi

@@ -1,0 +1,261 @@
+// nominal_fleet.hip -- the nominal trajectories of a whole fleet in ONE launch (mppi_nominal_traj_batch): grid (n), one workgroup
+// per controller, its argument block read from an array in device memory (as ddp_fleet_kernel and rollout_fleet16_kernel read
+// theirs).  The kernel restates mppi_nominal_traj for the network model statement for statement (abi_host.hip, host_net.hpp):
+// record s, clamp u with the host's two branches, the kinematics as two fmaf, per neuron the k-ascending fmaf chain from 0 with
+// the bias added afterwards, tanhf_scalar on hidden layers, s = fmaf(sd, dt, s).  Only sinf / cosf of the heading differ: they
+// are the rounded double results (ddp_sincos), not glibc's floats.  The forward layer is ddp_fleet_device.hpp's with FMA = true.
+//
+// The replay is one recurrence of T dependent steps: latency is the whole cost.  What is NOT on it:
+//   * the heading of step t + 1 is fmaf(-+s6[t], dt, psi[t]), known before step t's network runs, so its sin / cos are computed
+//     a step ahead;
+//   * U[t + 1] is fetched a step ahead;
+//   * control_seq does not depend on the state: the whole workgroup clamps and records it before the loop;
+//   * the state records are stores nobody waits for.
+// MPPI_NOMINAL_FLEET_WAVES = 2: wave 0 runs the network and the Euler step; inside the loop it only LOADS from global memory
+// (U[t + 1]; the image's weights where the image is not in LDS), so no wait of its covers a store.  Wave 1, the rider, takes
+// s[t] from an LDS slot, records it (stores only: it never waits for memory), computes sin / cos of psi[t + 1] in double and
+// hands them over in an LDS slot -- one s_barrier per step, both slots double-buffered.  = 1: one wave does everything, the
+// sin / cos issued ahead of the network.  DESIGN 4.21 has the measurement and which one is kept.
+#include <atomic>
+
+#include "../../include/mppi_hip.h"
+#include "ddp_fleet_device.hpp"
+
+namespace mppi {
+
+#ifndef MPPI_NOMINAL_FLEET_WAVES
+#define MPPI_NOMINAL_FLEET_WAVES 2  // waves per workgroup: 2 = network wave + rider, 1 = one wave (a build knob for A/B)
+#endif
+constexpr int kNomWaves = MPPI_NOMINAL_FLEET_WAVES;
+static_assert(kNomWaves == 1 || kNomWaves == 2, "one wave, or the network wave and its rider");
+constexpr int kNomActFloats = 2 * kDdpMaxWidth;  // the network wave's two activation tiles
+constexpr int kNomX = kNomActFloats;             // [2][8]: s[t] on its way to the rider (slot t & 1; float 7 is padding)
+constexpr int kNomSC = kNomX + 16;               // [2][4]: {sn, cs} of step t on its way to the network wave (slot t & 1; two floats of padding)
+constexpr int kNomFixedFloats = kNomSC + 8;
+constexpr size_t kNomLdsLimit = 96 * 1024;       // tiles + slots + image
+static_assert((kNomFixedFloats & 3) == 0, "the image behind the slots is read in 16-byte pieces");
+
+// mppi_nominal_traj's clamp: the host's two branches, NaN passes through
+__device__ __forceinline__ float nom_clamp(float u, float lo, float hi) { return u < lo ? lo : (u > hi ? hi : u); }
+
+// the two waves meet: what either stored to LDS before is what the other reads after.  Only the LDS counter is waited for: the
+// rider's record stores stay in flight.
+__device__ __forceinline__ void nom_group_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The network of one step for the wave (all 64 lanes hold the same s, u and results): HostNetFma::forward on [s3, s4, s5, s6, u0,
+// u1].  Lane 0 writes the six inputs (no lane-indexed pick among registers: that would put the state into scratch memory).
+__device__ __forceinline__ void nom_net(const NetDesc &net, const float *img, float *tile0, float *tile1, const float (&s)[7],
+                                        float u0, float u1, float (&o)[4], int lane)
+{
+  if (lane == 0) {
+    const f32x4 a = {s[3], s[4], s[5], s[6]};
+    *reinterpret_cast<f32x4 *>(tile0) = a;
+    tile0[4] = u0;
+    tile0[5] = u1;
+  }
+  ddp_wave_sync();
+  float *cur = tile0, *nxt = tile1;
+  int off = 0;
+  for (int l = 0; l + 1 < net.n_layers; l++) {
+    const int nin = net.layers[l], nout = net.layers[l + 1];
+    const float *Wt = img + off, *b = Wt + nin * nout;
+    const bool hidden = l + 2 < net.n_layers;
+    const int chains = (nout + 63) >> 6;
+    if (chains == 1) ddp_layer<1, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
+    else if (chains == 2) ddp_layer<2, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
+    else if (chains == 3) ddp_layer<3, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
+    else ddp_layer<4, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
+    ddp_wave_sync();
+    off += nin * nout + nout;
+    float *sw = cur; cur = nxt; nxt = sw;
+  }
+  const f32x4 d = *reinterpret_cast<const f32x4 *>(cur);
+  o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
+  ddp_wave_sync();  // the next step's inputs go to tile0, which may be the tile just read
+}
+
+// mppi_nominal_traj's update of one step: the kinematics, the network, the Euler step
+__device__ __forceinline__ void nom_step(const NetDesc &net, const float *img, float *tile0, float *tile1, int negate, float dt,
+                                         float (&s)[7], float u0, float u1, float sn, float cs, int lane)
+{
+  float sd[7];
+  sd[0] = fmaf(cs, s[4], -(sn * s[5]));
+  sd[1] = fmaf(sn, s[4], cs * s[5]);
+  sd[2] = negate ? -s[6] : s[6];
+  float o[4];
+  nom_net(net, img, tile0, tile1, s, u0, u1, o, lane);
+  sd[3] = o[0]; sd[4] = o[1]; sd[5] = o[2]; sd[6] = o[3];
+#pragma unroll
+  for (int i = 0; i < 7; i++) s[i] = fmaf(sd[i], dt, s[i]);
+}
+
+// One wave does everything (MPPI_NOMINAL_FLEET_WAVES = 1).  img: the image, in LDS or in global memory -- the caller has one call
+// for each, so that the weights are read with LDS or global instructions, not flat ones.
+__device__ __forceinline__ void nom_single_wave(const NominalFleetArgs &A, const float *img, float *lds, const float *in, float *out,
+                                                int lane)
+{
+  const NetDesc &net = A.net;
+  const int T = A.T, negate = A.negate_yaw_der;
+  const float dt = A.dt;
+  const float ulo0 = A.u_lo[0], ulo1 = A.u_lo[1], uhi0 = A.u_hi[0], uhi1 = A.u_hi[1];
+  const float *U = in + 7;
+  float *o_x = out;
+  float *tile0 = lds, *tile1 = lds + kDdpMaxWidth;
+  float s[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++) s[i] = in[i];
+  float sn, cs;
+  ddp_sincos(s[2], sn, cs);
+  float n0 = U[0], n1 = U[1];
+  for (int t = 0; t < T; t++) {
+    const float u0 = nom_clamp(n0, ulo0, uhi0), u1 = nom_clamp(n1, ulo1, uhi1);
+    if (t + 1 < T) {  // the next step's, requested a step ahead
+      n0 = U[2 * (t + 1)];
+      n1 = U[2 * (t + 1) + 1];
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int q = 0; q < 7; q++) o_x[(size_t)7 * t + q] = s[q];
+    }
+    if (t + 1 == T) break;  // the host's last update is computed and dropped
+    // the next heading is this one's Euler step, whose operands are all here: its sin / cos are issued ahead of the network
+    float sn_n, cs_n;
+    ddp_sincos(fmaf(negate ? -s[6] : s[6], dt, s[2]), sn_n, cs_n);
+    nom_step(net, img, tile0, tile1, negate, dt, s, u0, u1, sn, cs, lane);
+    sn = sn_n;
+    cs = cs_n;
+  }
+}
+
+// The network wave of two (MPPI_NOMINAL_FLEET_WAVES = 2): T - 1 steps; of global memory it reads U[t + 1] a step ahead and the
+// image's weights where the image is not in LDS, and stores nothing
+__device__ __forceinline__ void nom_network_wave(const NominalFleetArgs &A, const float *img, float *lds, const float *in, int lane)
+{
+  const NetDesc &net = A.net;
+  const int T = A.T, negate = A.negate_yaw_der;
+  const float dt = A.dt;
+  const float ulo0 = A.u_lo[0], ulo1 = A.u_lo[1], uhi0 = A.u_hi[0], uhi1 = A.u_hi[1];
+  const float *U = in + 7;
+  float *tile0 = lds, *tile1 = lds + kDdpMaxWidth, *hx = lds + kNomX;
+  const float *hsc = lds + kNomSC;
+  float s[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++) s[i] = in[i];
+  float n0 = U[0], n1 = U[1];
+  for (int t = 0; t + 1 < T; t++) {
+    const float u0 = nom_clamp(n0, ulo0, uhi0), u1 = nom_clamp(n1, ulo1, uhi1);
+    n0 = U[2 * (t + 1)];  // the next step's, requested a step ahead (t + 1 < T)
+    n1 = U[2 * (t + 1) + 1];
+    const float sn = hsc[4 * (t & 1)], cs = hsc[4 * (t & 1) + 1];
+    nom_step(net, img, tile0, tile1, negate, dt, s, u0, u1, sn, cs, lane);
+    if (lane == 0) {
+      float *slot = hx + 8 * ((t + 1) & 1);
+      const f32x4 a = {s[0], s[1], s[2], s[3]}, b = {s[4], s[5], s[6], 0.0f};
+      *reinterpret_cast<f32x4 *>(slot) = a;
+      *reinterpret_cast<f32x4 *>(slot + 4) = b;
+    }
+    nom_group_sync();  // barrier t: s[t + 1] is the rider's, {sn, cs}[t + 1] this wave's
+  }
+}
+
+// The rider: the state records, and step t + 1's sin / cos while step t's network runs.  It loads nothing from global memory, so
+// none of its waits covers a record store.
+__device__ __forceinline__ void nom_rider_wave(const NominalFleetArgs &A, float *lds, float *out, int lane)
+{
+  const int T = A.T, negate = A.negate_yaw_der;
+  const float dt = A.dt;
+  float *o_x = out;
+  const float *hx = lds + kNomX;
+  float *hsc = lds + kNomSC;
+  for (int t = 0; t < T; t++) {
+    const float *slot = hx + 8 * (t & 1);
+    const float v = slot[lane & 7];
+    if (lane < 7) o_x[(size_t)7 * t + lane] = v;
+    if (t + 1 == T) break;
+    const float psi = slot[2], s6 = slot[6];
+    float sn, cs;
+    ddp_sincos(fmaf(negate ? -s6 : s6, dt, psi), sn, cs);  // the network wave's Euler step of the heading, the same bits
+    if (lane == 0) {
+      hsc[4 * ((t + 1) & 1)] = sn;
+      hsc[4 * ((t + 1) & 1) + 1] = cs;
+    }
+    nom_group_sync();  // barrier t
+  }
+}
+
+__global__ __launch_bounds__(64 * kNomWaves) void nominal_fleet_kernel(const NominalFleetArgs *__restrict__ inst)
+{
+  extern __shared__ __attribute__((aligned(16))) float nom_lds[];
+  const NominalFleetArgs &A = inst[blockIdx.x];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float *wimg = load_global_ptr(A.wimg);
+  const float *in = load_global_ptr(A.in);
+  float *out = load_global_ptr(A.out);
+  const bool img_lds = A.img_lds != 0;
+  if (img_lds) {
+    const int np = A.net.num_params;
+    for (int i = threadIdx.x; i < np; i += 64 * kNomWaves) nom_lds[kNomFixedFloats + i] = wimg[i];
+  }
+  {  // control_seq: every control clamped, by the whole workgroup
+    const int T = A.T;
+    const float ulo0 = A.u_lo[0], ulo1 = A.u_lo[1], uhi0 = A.u_hi[0], uhi1 = A.u_hi[1];
+    const float *U = in + 7;
+    float *o_u = out + (size_t)7 * T;
+    for (int i = threadIdx.x; i < 2 * T; i += 64 * kNomWaves) o_u[i] = (i & 1) ? nom_clamp(U[i], ulo1, uhi1) : nom_clamp(U[i], ulo0, uhi0);
+  }
+  if constexpr (kNomWaves == 1) {
+    __syncthreads();
+    if (img_lds) nom_single_wave(A, nom_lds + kNomFixedFloats, nom_lds, in, out, lane);
+    else nom_single_wave(A, wimg, nom_lds, in, out, lane);
+  } else {
+    if (wave == 1) {  // step 0's hand-overs, both directions
+      float *hx = nom_lds + kNomX, *hsc = nom_lds + kNomSC;
+      if (lane < 8) hx[lane] = in[min(lane, 6)];
+      float sn, cs;
+      ddp_sincos(in[2], sn, cs);
+      if (lane == 0) {
+        hsc[0] = sn;
+        hsc[1] = cs;
+      }
+    }
+    __syncthreads();
+    // both waves pass T - 1 barriers, whatever the data
+    if (wave == 1) nom_rider_wave(A, nom_lds, out, lane);
+    else if (img_lds) nom_network_wave(A, nom_lds + kNomFixedFloats, nom_lds, in, lane);
+    else nom_network_wave(A, wimg, nom_lds, in, lane);
+  }
+}
+
+bool nominal_fleet_image_in_lds(const NetDesc &net)
+{
+  return sizeof(float) * ((size_t)kNomFixedFloats + (size_t)net.num_params) <= kNomLdsLimit;
+}
+
+hipError_t launch_nominal_fleet(const NominalFleetArgs *h_inst, const NominalFleetArgs *d_inst, int n, hipStream_t stream)
+{
+  if (n <= 0) return hipSuccess;
+  if (n > kMaxFleet) return hipErrorInvalidValue;
+  size_t lds = sizeof(float) * (size_t)kNomFixedFloats;
+  for (int i = 0; i < n; i++) {
+    const NetDesc &net = h_inst[i].net;
+    if (net.n_layers < 2 || net.n_layers > MPPI_MAX_LAYERS || net.max_width > kDdpMaxWidth || h_inst[i].T < 2) return hipErrorInvalidValue;
+    if (h_inst[i].img_lds) {
+      if (!nominal_fleet_image_in_lds(net)) return hipErrorInvalidValue;
+      lds = std::max(lds, sizeof(float) * ((size_t)kNomFixedFloats + (size_t)net.num_params));
+    }
+  }
+  // the kernel's dynamic-LDS ceiling, once per device
+  static std::atomic<bool> raised[64];
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(nominal_fleet_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNomLdsLimit);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(nominal_fleet_kernel, dim3(n), dim3(64 * kNomWaves), lds, stream, d_inst);
+  return hipGetLastError();
+}
+
+}  // namespace mppi

@@ -701,6 +701,35 @@ class MPPIControllerT {
     }
     for (int c = 0; c < n; c++) controllers[c]->computeNominalTraj(controllers[c]->solve_state_);
   }
+  // finishControlFleet with the replays on the device: all solves collected, then ONE mppi_nominal_traj_batch fills every
+  // controller's state_solution_ / control_solution_ (two or more network-model controllers on one device: one kernel launch,
+  // one workgroup per controller; any other set: the host replays of finishControlFleet).  control_solution_ has the host replay's
+  // bits; state_solution_ differs from it only through sinf / cosf of the heading (include/mppi_hip.h).
+  static void finishControlFleetOnDevice(MPPIControllerT *const *controllers, int n)
+  {
+    if (n < 1) return;
+    std::vector<mppi_handle *> hs((size_t)n);
+    std::vector<float *> xs((size_t)n), us((size_t)n);
+    std::vector<float> states((size_t)n * STATE_DIM);
+    for (int c = 0; c < n; c++) {
+      float tc = 0.0f;
+      controllers[c]->ck(mppi_get_results(controllers[c]->h_, nullptr, &tc, nullptr, nullptr));
+      controllers[c]->trajectory_cost_ = tc;
+      hs[(size_t)c] = controllers[c]->h_;
+      xs[(size_t)c] = controllers[c]->state_solution_.data();
+      us[(size_t)c] = controllers[c]->control_solution_.data();
+      for (int i = 0; i < STATE_DIM; i++) states[(size_t)c * STATE_DIM + i] = controllers[c]->solve_state_[i];
+    }
+    const int rc = mppi_nominal_traj_batch(hs.data(), states.data(), xs.data(), us.data(), n);
+    if (rc != MPPI_OK) {  // the text sits on whichever handle recorded it
+      std::string msg = std::string("libmppi_hip: ") + mppi_strerror(rc) + " (";
+      for (int c = 0; c < n; c++) {
+        const char *e = mppi_last_error(controllers[c]->h_);
+        if (e && *e) msg += std::string(msg.back() == '(' ? "" : " | ") + e;
+      }
+      throw std::runtime_error(msg + ")");
+    }
+  }
   // computeFeedbackGains(state) of every controller of the fleet in one call (mppi_compute_feedback_gains_batch): each tracks its
   // own state_solution_ / control_solution_ from states[c].  Two or more network-model controllers on one device run in ONE kernel
   // launch, one workgroup per controller; any other set runs the host passes of n single calls.  A controller whose control

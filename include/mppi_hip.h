@@ -63,6 +63,8 @@ extern "C" {
  *    rollout, one tail launch per iteration); no new export, no gated form, the automatic choice does not change. */
 /*    (still 5) + mppi_compute_feedback_gains_batch, mppi_debug_ddp_info, mppi_debug_device_tanhf (the DDP feedback gains of a fleet
  *    in one launch; compatible additions, the single and the pair call are unchanged). */
+/*    (still 5) + mppi_nominal_traj_batch, mppi_debug_nominal_info (the nominal trajectories of a fleet in one launch; compatible
+ *    additions, the single and the pair call are unchanged). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -299,6 +301,30 @@ int mppi_nominal_traj(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
  * cost of one; results bit for bit those of two mppi_nominal_traj calls (which is what this does for any other pair). */
 int mppi_nominal_traj_pair(mppi_handle *ha, const float state_a[MPPI_STATE_DIM], float *state_seq_a, float *control_seq_a,
                            mppi_handle *hb, const float state_b[MPPI_STATE_DIM], float *state_seq_b, float *control_seq_b);
+
+/* computeNominalTraj of a whole fleet in one call: handles[n], states [n][7]; handle i's replay of its current control sequence
+ * lands in state_seqs[i] ([T_i][7]) and control_seqs[i] ([T_i][2], clamped).
+ * Sharing rule: n >= 2 handles of the network model with parameters set, all on one device, are replayed ON THE DEVICE, one
+ * workgroup per controller in one launch (nominal_fleet_kernel; more than 64 handles: launches of up to 64) -- layer lists, T,
+ * hz, limits and negate_yaw_der may differ per handle.  The kernel restates mppi_nominal_traj statement for statement (the clamp's
+ * two branches, every fmaf, the bias add, libm's tanhf bits, the Euler step); only sinf / cosf of the heading are the rounded
+ * double results, not glibc's floats (1 ulp apart in 1.3 % of headings): control_seq is bit for bit the single call's, state_seq
+ * agrees far inside the bound both are held to, and bit for bit while the heading stays 0.  Anything else -- n = 1, a
+ * basis-function handle in the set, handles on several devices -- runs n mppi_nominal_traj calls on the host with their bits;
+ * mppi_debug_nominal_info tells which it was.
+ * Order of work: every argument is checked (MPPI_ERR_INVALID for a NULL array, n < 1, a NULL handle or output pointer in the set,
+ * a handle listed twice), then every handle's readiness (MPPI_ERR_STATE without parameters), then every pending solve is collected
+ * (as mppi_nominal_traj does); only then is an output written or anything launched.  The caller's buffers are written after EVERY
+ * launch of the call has succeeded: MPPI_ERR_HIP from any of them leaves all of them as they were.  The inputs are each handle's
+ * HOST control sequence and the call's state.  The call uses the device's batch stream and blocks until the results are back; it touches no
+ * handle's solve state beyond collecting pending solves, and an armed handle stays armed -- but handles armed TOGETHER
+ * (mppi_arm_batch) wait gated on the batch stream, and this call's launch waits behind their gate: replay before arming, or after
+ * the gate has opened. */
+int mppi_nominal_traj_batch(mppi_handle *const *handles, const float *states /* n x 7 */, float *const *state_seqs /* [i]: T_i x 7 */,
+                            float *const *control_seqs /* [i]: T_i x 2 */, int n);
+/* Test / tooling hook: *on_device = 1 if the handle's most recent nominal replay ran in the fleet's kernel, 0 if on the host (or
+ * none yet).  MPPI_ERR_INVALID for a NULL argument. */
+int mppi_debug_nominal_info(const mppi_handle *h, int *on_device);
 
 /* computeFeedbackGains (PI/mppi_controller.cu:431-441) -> DDP::run (ddp/ddp.h:49-157), one
  * iteration, dt = 1/hz, from `state`, tracking target_state_seq [T][7] / target_control_seq [T][2]

@@ -10,7 +10,12 @@ wavefront, handle by handle; (c) "auto" (row_tree / m44, handle by handle).  Pri
     python tools/fleet_time.py --ddp [--T 100] [--ticks 200] [--net ...]
 
 The DDP feedback gains of the fleet instead (n = 2, 4, 16, 64): mppi_compute_feedback_gains_batch -- one launch of ddp_fleet_kernel --
-against n single calls on one host thread and against the pair entry with mppi_set_host_threads(2); median of `ticks` calls."""
+against n single calls on one host thread and against the pair entry with mppi_set_host_threads(2); median of `ticks` calls.
+
+    python tools/fleet_time.py --nominal [--T 100] [--ticks 200] [--net ...]
+
+The nominal trajectories of the fleet (n = 2, 4, 16, 64): mppi_nominal_traj_batch -- one launch of nominal_fleet_kernel -- against
+n mppi_nominal_traj calls on one host thread and n / 2 mppi_nominal_traj_pair calls with mppi_set_host_threads(2)."""
 import argparse
 import json
 import os
@@ -142,6 +147,76 @@ def ddp_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
     return rows
 
 
+def nominal_ms(net, n, K=64, T=100, calls=200, warm=10):
+    """The nominal replays of n handles, three ways, each the median wall time of `calls` calls after `warm` warm ones: the batch
+    entry (one launch for the fleet), n single calls on one host thread, n / 2 pair calls with mppi_set_host_threads(2).  Every
+    handle replays a warm control sequence from its own state into buffers allocated once."""
+    from autorally_amd import capi
+    sols, states = fleet(net, "auto", n, K, T)
+    try:
+        rng = np.random.RandomState(5)
+        for s in sols:
+            s.set_control_seq(np.stack([rng.uniform(-0.5, 0.5, T), rng.uniform(-0.2, 0.6, T)], axis=1).astype(np.float32))
+        out = [(np.zeros((T, 7), np.float32), np.zeros((T, 2), np.float32)) for _ in sols]
+        fp = capi.C.POINTER(capi.C.c_float)
+        hs = (capi.C.c_void_p * n)(*[s.h for s in sols])
+        st = np.ascontiguousarray(np.stack(states), np.float32)
+        ssp, csp = (fp * n)(*[capi._fp(o[0]) for o in out]), (fp * n)(*[capi._fp(o[1]) for o in out])
+        L = sols[0].L
+
+        def median(fn):
+            for _ in range(warm):
+                fn()
+            dt = []
+            for _ in range(calls):
+                t0 = time.perf_counter()
+                fn()
+                dt.append(time.perf_counter() - t0)
+            return 1e3 * float(np.median(dt))
+
+        def batch():
+            assert L.mppi_nominal_traj_batch(hs, capi._fp(st), ssp, csp, n) == capi.OK
+
+        def single():
+            for s, x, o in zip(sols, states, out):
+                assert L.mppi_nominal_traj(s.h, capi._fp(x), capi._fp(o[0]), capi._fp(o[1])) == capi.OK
+
+        def pairs():
+            for i in range(0, n - 1, 2):
+                assert L.mppi_nominal_traj_pair(sols[i].h, capi._fp(states[i]), capi._fp(out[i][0]), capi._fp(out[i][1]), sols[i + 1].h,
+                                                capi._fp(states[i + 1]), capi._fp(out[i + 1][0]), capi._fp(out[i + 1][1])) == capi.OK
+            if n % 2:
+                assert L.mppi_nominal_traj(sols[-1].h, capi._fp(states[-1]), capi._fp(out[-1][0]), capi._fp(out[-1][1])) == capi.OK
+
+        row = {"net": "-".join(map(str, net)), "n": n, "T": T}
+        row["batch_ms"] = median(batch)
+        row["on_device"] = sols[0].debug_nominal_info()
+        capi.set_host_threads(1)
+        row["host1_ms"] = median(single)
+        capi.set_host_threads(2)
+        try:
+            row["host2_ms"] = median(pairs)
+        finally:
+            capi.set_host_threads(1)
+        return row
+    finally:
+        for s in sols:
+            s.close()
+
+
+def nominal_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
+    rows = []
+    for net in nets:
+        for n in ns:
+            row = nominal_ms(net, n, T=T, calls=calls)
+            rows.append(row)
+            print("FLEET NOMINAL n=%d T=%d net=%s: batch %.4f ms (on_device %d)  host, 1 thread %.4f ms  host, 2 threads (pairs) %.4f ms;  "
+                  "host1/batch %.2f  host2/batch %.2f" % (n, T, row["net"], row["batch_ms"], row["on_device"], row["host1_ms"],
+                                                         row["host2_ms"], row["host1_ms"] / row["batch_ms"], row["host2_ms"] / row["batch_ms"]),
+                  flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=16)
@@ -153,9 +228,14 @@ def main():
     ap.add_argument("--net", nargs="*", default=["6-32-32-4", "6-64-64-64-64-4"])
     ap.add_argument("--ddp", action="store_true", help="the DDP feedback gains of the fleet instead: the batch entry against the host "
                     "passes, n = 2, 4, 16, 64 (mppi_compute_feedback_gains_batch)")
+    ap.add_argument("--nominal", action="store_true", help="the nominal trajectories of the fleet instead: the batch entry against the "
+                    "host replays, n = 2, 4, 16, 64 (mppi_nominal_traj_batch)")
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
+    if a.nominal:
+        print(json.dumps(nominal_table([[int(x) for x in s.split("-")] for s in a.net], T=a.T, calls=a.ticks)))
+        return
     if a.ddp:
         print(json.dumps(ddp_table([[int(x) for x in s.split("-")] for s in a.net], T=a.T, calls=a.ticks)))
         return
