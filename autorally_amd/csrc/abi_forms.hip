@@ -75,7 +75,7 @@ const FormRule kFormRules[] = {
 // the forms of the network model that run by name only, for every layer list they serve (the standard shapes too)
 static bool form_by_name_only(Form f)
 {
-  return f == Form::Lds44 || f == Form::Lds128 || f == Form::Lds16 || f == Form::Glb16 || f == Form::Glb44 || f == Form::Fleet16;
+  return f == Form::Lds44 || f == Form::Lds128 || f == Form::Lds16 || f == Form::Glb16 || f == Form::Glb44 || f == Form::Fleet16 || f == Form::FleetMulti4;
 }
 
 Form form_of(const mppi_handle *h)
@@ -167,6 +167,7 @@ const char *mppi_rollout_variant(const mppi_handle *h)
     case Form::ValuReg: return "valu_reg_lds";
     case Form::ValuLds: return "valu_lds";
     case Form::Multi4Tree: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_multi4_tree%s", h->hidden, h->n_hidden, gen); break;
+    case Form::FleetMulti4: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_fleet_multi4_tree%s", h->hidden, h->n_hidden, gen); break;
     case Form::Multi2: case Form::Multi4:
       snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_multi%d%s", h->hidden, h->n_hidden, form_multi_nd(f), gen);
       break;
@@ -266,8 +267,16 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
       return fail(h, MPPI_ERR_UNSUPPORTED, msg);
     }
     if ((rc = need(h->d_lds16pack != nullptr, "fleet16 form: this handle has no image"))) return rc;
-    if ((rc = fleet16_prepare(h))) return rc;
+    if ((rc = fleet_prepare(h))) return rc;
     h->forced = Form::Fleet16;
+  }
+  else if (strcmp(name, "fleet_multi4") == 0) {  // "multi4_tree_gen"'s workgroup and bits; up to 64 such handles share the launches of a batched solve
+    if ((rc = need(!h->basis, "fleet_multi4 is a form of the network model"))) return rc;
+    if ((rc = need(h->mfma_ok && multi_variant_supported(h->hidden, h->n_hidden), "fleet_multi4 form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4"))) return rc;
+    if ((rc = need(h->K % 64 == 0, "fleet_multi4 form needs K to be a multiple of 64"))) return rc;  // a guard: mppi_create refuses such a K
+    if ((rc = fleet_prepare(h))) return rc;
+    h->forced = Form::FleetMulti4;
+    h->multi_standalone_noise = true;  // eps from the stand-alone generator: no form with the in-kernel one
   }
   else if (strncmp(name, "glb16", 5) == 0) {  // lds16's wave for every layer list up to 256 wide; "glb16_r<N>": at most N stream blocks resident
     const int cap = resident_cap_of(name + 5);

@@ -63,6 +63,9 @@ enum class Form : int {
                                     // only ("glb44", "glb44_r<N>")
   Fleet16,                          // rollout_fleet16.hip: lds16's wave and image with the argument block read from device memory: up to 64 handles
                                     // of one layer list share a launch (mppi_compute_control_batch); by name only ("fleet16")
+  FleetMulti4,                      // rollout_fleet_multi.hip: Multi4Tree's workgroup with the stand-alone generator ("multi4_tree_gen"), the argument
+                                    // block read from device memory: up to 64 handles of one standard shape share a launch; by name only
+                                    // ("fleet_multi4"), no gated form
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
   BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
@@ -76,7 +79,7 @@ struct Events {
   hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
-// Argument blocks that kernels read from DEVICE memory (the fleet16 form): one device block, filled through a ring of pinned
+// Argument blocks that kernels read from DEVICE memory (the fleet forms): one device block, filled through a ring of pinned
 // staging slots with one asynchronous copy per use.  All uses of a block go to ONE stream, which orders the copy into the device
 // block behind the kernels that read its previous contents; a staging slot is written again only once the copy out of it has
 // completed (its event).
@@ -182,7 +185,7 @@ struct mppi_handle {
   size_t lds128_bytes = 0;       // ... and its size
   float *d_lds16pack = nullptr;  // the same lists: image of rollout_lds16.hip
   size_t lds16_bytes = 0;        // ... and its size
-  mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16": the argument block of this handle's own launches (on its own stream); only a
+  mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16", "fleet_multi4": the argument block of this handle's own launches (on its own stream); only a
                                  // handle that asked for the form has one
   float *d_glb16pack = nullptr;  // image of rollout_glb16.hip: only a handle that asked for "glb16" has one (built at that call)
   size_t glb16_bytes = 0;        // ... and its size
@@ -326,7 +329,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
 // a rollout launch that is followed by its tail kernel: the tag its minimum cost travels under (a.min_cost, a.min_cost_tag)
 int tag_min_cost(mppi_handle *h, RolloutArgs &a, hipStream_t stream);
 int launch_rollout(mppi_handle *h, const RolloutArgs &a);
-int fleet16_prepare(mppi_handle *h);  // what a handle that asks for "fleet16" needs of its own (fleet_one), once
+int fleet_prepare(mppi_handle *h);  // what a handle that asks for "fleet16" or "fleet_multi4" needs of its own (fleet_one), once
 int check_ready(mppi_handle *h);
 int launch_generator(mppi_handle *h, float *dst);
 int acquire_noise(mppi_handle *h, float **buf_out);

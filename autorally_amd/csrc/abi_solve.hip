@@ -63,7 +63,7 @@ hipError_t arg_block_send(ArgBlock &b, size_t bytes, hipStream_t stream)
   return hipSuccess;
 }
 
-// The fleet16 form's argument blocks of a batched solve: ONE block per device beside the device's batch stream, shared by every
+// The argument blocks of a fleet form's batched solve ("fleet16", "fleet_multi4"): ONE block per device beside the device's batch stream, shared by every
 // fleet on the device and never destroyed -- per iteration the rollout, tail and generator blocks of up to kMaxFleet instances,
 // packed for the fleet's n (FleetBlock: abi_internal.hpp).  A batched DDP pass and a batched nominal replay (abi_host.hip) send their
 // instances' blocks through it too.
@@ -84,7 +84,7 @@ FleetBlock *fleet_block(int device)
   return fb.ready ? &fb : nullptr;
 }
 
-int fleet16_prepare(mppi_handle *h)
+int fleet_prepare(mppi_handle *h)
 {
   if (h->fleet_one) return MPPI_OK;
   HIPCHK(h, ensure_device(h->cfg.device));
@@ -93,21 +93,28 @@ int fleet16_prepare(mppi_handle *h)
   const hipError_t e = arg_block_create(*b, sizeof(RolloutArgs));
   if (e != hipSuccess) {
     delete b;
-    return fail(h, MPPI_ERR_HIP, "fleet16 form: argument block", e);
+    return fail(h, MPPI_ERR_HIP, "fleet form: argument block", e);
   }
   h->fleet_one = b;
   return MPPI_OK;
 }
 
-// a fleet16 handle solved alone: the fleet's kernel with one instance, its argument block sent on the handle's own stream
-static hipError_t launch_rollout_fleet16_one(mppi_handle *h, const RolloutArgs &a)
+// the rollout launch of a fleet form ("fleet16", "fleet_multi4") for the n instances h_inst / d_inst (host and device copies)
+static hipError_t launch_rollout_fleet(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t stream)
+{
+  if (h->forced == Form::FleetMulti4) return launch_rollout_fleet_multi(h->hidden, h->n_hidden, h_inst, d_inst, n, stream);
+  return launch_rollout_fleet16(h->net, h_inst, d_inst, n, h->num_simds / 4, stream);
+}
+
+// a handle of a fleet form solved alone: the fleet's kernel with one instance, its argument block sent on the handle's own stream
+static hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a)
 {
   if (!h->fleet_one) return hipErrorInvalidValue;
   unsigned char *host = nullptr;
   if (hipError_t e = arg_block_stage(*h->fleet_one, &host); e != hipSuccess) return e;
   memcpy(host, &a, sizeof(RolloutArgs));
   if (hipError_t e = arg_block_send(*h->fleet_one, sizeof(RolloutArgs), h->stream); e != hipSuccess) return e;
-  return launch_rollout_fleet16(h->net, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), 1, h->num_simds / 4, h->stream);
+  return launch_rollout_fleet(h, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), 1, h->stream);
 }
 
 void fill_cost_args(const mppi_handle *h, CostArgs &c)
@@ -184,7 +191,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
 static unsigned long long *min_cost_keys(const mppi_handle *h)
 {
   const Form f = form_of(h);
-  const bool publishes = f == Form::Multi2 || f == Form::Multi4 || f == Form::Multi4Tree;  // rollout_multi.hip
+  const bool publishes = f == Form::Multi2 || f == Form::Multi4 || f == Form::Multi4Tree || f == Form::FleetMulti4;  // multi_group.hpp
   return (h->use_min_cost && tail_is_stream(h->K) && publishes) ? h->d_min_cost : nullptr;
 }
 
@@ -217,7 +224,7 @@ int launch_rollout(mppi_handle *h, const RolloutArgs &a)
     case Form::Lds44: e = launch_rollout_lds44(h->net, a, h->stream); break;
     case Form::Lds128: e = launch_rollout_lds128(h->net, a, h->stream); break;
     case Form::Lds16: e = launch_rollout_lds16(h->net, a, h->num_simds / 4, h->stream); break;
-    case Form::Fleet16: e = launch_rollout_fleet16_one(h, a); break;
+    case Form::Fleet16: case Form::FleetMulti4: e = launch_rollout_fleet_one(h, a); break;
     case Form::Glb16: e = launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, h->stream); break;
     case Form::Glb44: e = launch_rollout_glb44(h->net, a, h->glb44_cap, h->stream); break;
     case Form::Row64R16: e = launch_rollout_row64(h->hidden, h->n_hidden, a, 16, h->stream); break;
@@ -1018,7 +1025,8 @@ static bool batch_together(mppi_handle *const *hs, int n)
   return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
 }
 
-// The fleet: 2..kMaxFleet handles forced to "fleet16" on one device with one whole layer list, one num_iters and one pair (affine
+// The fleet: 2..kMaxFleet handles ALL forced to "fleet16" or ALL to "fleet_multi4" (a mixed set is solved handle by handle) on one
+// device with one whole layer list, one num_iters and one pair (affine
 // costmap transform, control cost needed) -- one kernel instance serves the launch, and a superset kernel would not keep every
 // instance's bits (batch_together) -- K <= 4096 each (the one-workgroup-per-row tail), no stage timing, capture or prefetched
 // draws, every handle ready.  Such a set shares its launches: per iteration one generator, one rollout and one tail launch on
@@ -1031,7 +1039,7 @@ static bool fleet_together(mppi_handle *const *hs, int n)
   fill_cost_args(h0, c0);
   for (int i = 0; i < n; i++) {
     const mppi_handle *h = hs[i];
-    if (h->basis || h->forced != Form::Fleet16 || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
+    if (h->basis || (h0->forced != Form::Fleet16 && h0->forced != Form::FleetMulti4) || h->forced != h0->forced || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
     if (h->net.n_layers != h0->net.n_layers) return false;
     for (int l = 0; l < h->net.n_layers; l++)
       if (h->net.layers[l] != h0->net.layers[l]) return false;
@@ -1115,7 +1123,7 @@ static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
     const unsigned char *dev = fb->args.d;
     if (e == hipSuccess) e = launch_noise_fleet(nd, reinterpret_cast<const NoiseFleetDesc *>(dev + fleet_noise_offset(n)), n, S);
     if (e == hipSuccess)
-      e = launch_rollout_fleet16(h0->net, ra, reinterpret_cast<const RolloutArgs *>(dev), n, h0->num_simds / 4, S);
+      e = launch_rollout_fleet(h0, ra, reinterpret_cast<const RolloutArgs *>(dev), n, S);
     if (e == hipSuccess) e = launch_solve_tail_fleet(tl, n, dev + fleet_tail_offset(n), S);
     if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "fleet launch", e));
     for (int i = 0; i < n; i++) {
@@ -1216,11 +1224,11 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     }
   }
   mppi_handle *h0 = hs[0];
-  if (!together && fleet_together(hs, n)) return enqueue_fleet(hs, states, n);  // the "fleet16" form: 2..64 handles, three launches
+  if (!together && fleet_together(hs, n)) return enqueue_fleet(hs, states, n);  // the "fleet16" / "fleet_multi4" forms: 2..64 handles, three launches
   if (!together && n >= 2) {
-    // a set of "fleet16" handles with one that is not ready: its error before any of the others has moved
-    bool all_fleet = true;
-    for (int i = 0; i < n; i++) all_fleet = all_fleet && hs[i]->forced == Form::Fleet16;
+    // a set of "fleet16" (or of "fleet_multi4") handles with one that is not ready: its error before any of the others has moved
+    bool all_fleet = h0->forced == Form::Fleet16 || h0->forced == Form::FleetMulti4;
+    for (int i = 0; i < n; i++) all_fleet = all_fleet && hs[i]->forced == h0->forced;
     for (int i = 0; i < n && all_fleet; i++)
       if (const int rc = check_ready(hs[i])) return rc;
   }

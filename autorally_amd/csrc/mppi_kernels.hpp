@@ -205,6 +205,16 @@ Fleet16Plan fleet16_plan(const NetDesc &net, const int *Ks, int n, int cus);
 // h_inst: the n argument blocks on the host (K and the cost flags are read there); d_inst: the same blocks in device memory
 hipError_t launch_rollout_fleet16(const NetDesc &net, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, int cus, hipStream_t stream);
 
+// rollout_fleet_multi.hip: the workgroup of "multi4_tree_gen" (rollout_multi.hip, nd = 44) for up to kMaxFleet independent
+// controllers of ONE shape multi_variant_supported takes in one launch -- grid (64-rollout groups of the largest instance,
+// instances), eight waves per workgroup, the instances' argument blocks an array in device memory
+struct FleetMultiPlan {
+  int threads, grid_x, grid_y;  // all zero: no launch (another shape, n outside 1..kMaxFleet, a K that is no multiple of 64)
+};
+FleetMultiPlan fleet_multi_plan(int hidden, int n_hidden, const int *Ks, int n);
+// h_inst: the n argument blocks on the host (K is read there); d_inst: the same blocks in device memory
+hipError_t launch_rollout_fleet_multi(int hidden, int n_hidden, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t stream);
+
 // rollout_glb16.hip: lds16's wave for EVERY layer list 6 -> hidden widths 1..256 -> 4 (3 <= n_layers <= 8): the image is lds16's
 // with up to 16 tiles per layer; its head (biases + layer 0) and the first R blocks of its stream are resident in LDS, the other
 // blocks are read from the image in global memory; a.wpack = pack_glb16_weights (abi_pack.hip).  cap: the cap on R given by

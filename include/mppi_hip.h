@@ -61,6 +61,10 @@ extern "C" {
 /*    (still 5) + rollout variant "fleet16", name "mfma16x16x4_fleet_l<N>_w<W>": "lds16"'s wavefront, image and lists with the argument
  *    block read from device memory; 2..64 handles forced to it share the launches of mppi_compute_control_batch (one generator, one
  *    rollout, one tail launch per iteration); no new export, no gated form, the automatic choice does not change. */
+/*    (still 5) + rollout variant "fleet_multi4", name "mfma16x16x4_h<H>_l<N>_fleet_multi4_tree_gen": the workgroup and the bits of
+ *    "multi4_tree_gen" (6-32x2-4, 6-32x4-4, 6-64x2-4) with the argument block read from device memory; 2..64 handles forced to it
+ *    share the launches of mppi_compute_control_batch as "fleet16" handles do; no new export, no gated form, the automatic choice
+ *    does not change. */
 /*    (still 5) + mppi_compute_feedback_gains_batch, mppi_debug_ddp_info, mppi_debug_device_tanhf (the DDP feedback gains of a fleet
  *    in one launch; compatible additions, the single and the pair call are unchanged). */
 /*    (still 5) + mppi_nominal_traj_batch, mppi_debug_nominal_info (the nominal trajectories of a fleet in one launch; compatible
@@ -221,6 +225,8 @@ int mppi_synchronize(mppi_handle *h);
  * else differs between the instances (K, T, state, U and hist, weights, costmap and transform, cost parameters, limits, nu,
  * gamma, seed, explicit noise or the generator).  Any other set of such handles (n > 64, a mixed set, a K above 4096) is n
  * per-handle solves; a set of "fleet16" handles with one that is not ready returns that handle's error before any has moved.
+ * The "fleet_multi4" variant: the same rule and the same three launches for 2 <= n <= 64 handles that are ALL forced to
+ * "fleet_multi4" (one of 6-32x2-4, 6-32x4-4, 6-64x2-4); a set that mixes "fleet16" and "fleet_multi4" handles is n per-handle solves.
  * mppi_debug_launch_info tells which it was.  Either way every
  * handle's results are bit for bit those of its own mppi_compute_control, collected per handle with
  * mppi_synchronize / mppi_get_results.  The blocking form waits for all of them. */
@@ -434,6 +440,13 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     the image fits 160 KB of LDS; the same refusals) with the argument block read from device memory, so that up to 64 handles of
  *     one layer list share ONE rollout launch (mppi_compute_control_batch: the sharing rule is stated there); the bits of "lds16"
  *     and "valu_lds"; NO gated form; a handle solved alone runs the same kernel with one instance; by name only.
+ *     "fleet_multi4" mfma16x16x4_h<H>_l<N>_fleet_multi4_tree_gen: "multi4_tree_gen"'s workgroup (four dynamics waves with every
+ *     weight in registers, riders on the side, the output layer as a butterfly, eps from the stand-alone generator kernel) with the
+ *     argument block read from device memory, so that up to 64 handles of one shape share ONE rollout launch
+ *     (mppi_compute_control_batch: the sharing rule is stated there); the bits of "multi4_tree_gen"; the fleet form to ask for on
+ *     these shapes (ahead of "fleet16" at every fleet size, ahead of "auto" from 16 handles on); NO gated form; a
+ *     handle solved alone runs the same kernel with one instance; by name only; MPPI_ERR_UNSUPPORTED for the basis-function model
+ *     and for any list but 6-32x2-4, 6-32x4-4, 6-64x2-4 (K is a multiple of 64 on every handle: mppi_create).
  *     "glb16" mfma16x16x4_glb_l<hidden layers>_w<widest hidden layer>: "lds16"'s wavefront for EVERY layer list of the network model
  *     (3 <= n_layers <= 8, hidden widths 1..256): the same image with up to 16 tiles per layer; its head (biases, layer 0) and the
  *     first R of its 1 KB blocks are copied into LDS, the other blocks are read from the image in global memory (it stays in L2),

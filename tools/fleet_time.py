@@ -7,6 +7,10 @@ n distinct oval instances with generator noise; the median wall time of a tick (
 `ticks` ticks after `warm` warm ones, three ways: (a) every handle forced to "fleet16"; (b) forced to "lds16" -- the same
 wavefront, handle by handle; (c) "auto" (row_tree / m44, handle by handle).  Prints one line per network and a JSON line.
 
+With "d" among --ways: (d) every handle forced to "fleet_multi4" -- the register MFMA group of "multi4_tree_gen" as a fleet form
+(6-32x2-4, 6-32x4-4 and 6-64x2-4; any other list: not available) -- and with "A": "fleet16" a second time, the A/A spread of the
+visit beside the ratios (--ways dabcA).
+
     python tools/fleet_time.py --ddp [--T 100] [--ticks 200] [--net ...]
 
 The DDP feedback gains of the fleet instead (n = 2, 4, 16, 64): mppi_compute_feedback_gains_batch -- one launch of ddp_fleet_kernel --
@@ -28,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-WAYS = (("a", "fleet16"), ("b", "lds16"), ("c", "auto"))
+WAYS = (("d", "fleet_multi4"), ("a", "fleet16"), ("b", "lds16"), ("c", "auto"), ("A", "fleet16"))
 
 
 def fleet(net, variant, n, K, T):
@@ -46,7 +50,12 @@ def fleet(net, variant, n, K, T):
                    cost=dict(base["cost"], desired_speed=6.0 + 0.25 * i), start_state=st)
         sol = capi.Solver(cfg)
         if variant != "auto":
-            sol.set_rollout_variant(variant)
+            try:
+                sol.set_rollout_variant(variant)
+            except capi.MppiError:
+                for s in sols + [sol]:
+                    s.close()
+                raise
         sol.seed(1000 + i, 0)
         sols.append(sol)
         states.append(st)
@@ -56,7 +65,12 @@ def fleet(net, variant, n, K, T):
 def tick_ms(net, variant, n=16, K=1920, T=100, ticks=200, warm=20):
     """-> (median ms per tick, instances per rollout launch, the form's name)"""
     from autorally_amd import capi
-    sols, states = fleet(net, variant, n, K, T)
+    try:
+        sols, states = fleet(net, variant, n, K, T)
+    except capi.MppiError as e:
+        if e.status != capi.ERR_UNSUPPORTED:
+            raise
+        return None, 0, "not available"  # a list the form does not take ("fleet_multi4")
     try:
         capi.control_ticks_batch(sols, states, warm, 1)
         dt = []
@@ -80,8 +94,10 @@ def table(nets, n=16, K=1920, T=100, ticks=200, warm=20, ways="abc"):
             ms, inst, name = tick_ms(net, variant, n, K, T, ticks, warm)
             row[key + "_ms"], row[key + "_instances"], row[key + "_form"] = ms, inst, name
         rows.append(row)
-        if set("abc") - set(ways):
-            print("FLEET n=%d K=%d T=%d net=%s: %s" % (n, K, T, row["net"], {k: v for k, v in row.items() if k.endswith("_ms")}), flush=True)
+        if set(ways) != set("abc"):
+            print("FLEET n=%d K=%d T=%d net=%s: %s" % (n, K, T, row["net"], "  ".join(
+                "(%s) %s %s [%d per launch]" % (key, variant, "n/a" if row[key + "_ms"] is None else "%.4f ms" % row[key + "_ms"], row[key + "_instances"])
+                for key, variant in WAYS if key + "_ms" in row)), flush=True)
             continue
         print("FLEET n=%d K=%d T=%d net=%s: (a) fleet16 %.4f ms [%d per launch]  (b) lds16 %.4f ms  (c) auto (%s) %.4f ms;  b/a %.2f  c/a %.2f" % (
             n, K, T, row["net"], row["a_ms"], row["a_instances"], row["b_ms"], row["c_form"], row["c_ms"], row["b_ms"] / row["a_ms"],
@@ -224,7 +240,7 @@ def main():
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--warm", type=int, default=20)
-    ap.add_argument("--ways", default="abc", help="which of (a) fleet16, (b) lds16, (c) auto to run")
+    ap.add_argument("--ways", default="abc", help="which of (a) fleet16, (b) lds16, (c) auto, (d) fleet_multi4, (A) fleet16 again to run")
     ap.add_argument("--net", nargs="*", default=["6-32-32-4", "6-64-64-64-64-4"])
     ap.add_argument("--ddp", action="store_true", help="the DDP feedback gains of the fleet instead: the batch entry against the host "
                     "passes, n = 2, 4, 16, 64 (mppi_compute_feedback_gains_batch)")
