@@ -1,5 +1,6 @@
 // abi_forms.hip -- which rollout kernel form serves a handle: the selection TABLE (model shape x rollout groups per CU ->
-// form, every row with the measurement that justifies it), the forms' properties, their names, mppi_set_rollout_variant.
+// form, every row with the measurement that justifies it), the descriptor table kForms (what the host knows about a form: image,
+// noise source, launch adapters, name), the table of request names kRequests behind mppi_set_rollout_variant.
 // tests/test_form_selection_gpu.py times the candidates of every bucket and fails if the table's choice is more than
 // 10 % slower than the best of them.
 #include "abi_internal.hpp"
@@ -19,20 +20,6 @@ bool use_mfma(const mppi_handle *h)
 bool use_valu_reg(const mppi_handle *h) { return !h->basis && !use_mfma(h) && h->valu_reg_ok && h->pref != Pref::ValuLds; }
 
 namespace {
-
-bool form_supported(Form f, int hidden, int n_hidden)
-{
-  switch (f) {
-    case Form::M44: case Form::M44Chain: return m44_variant_supported(hidden, n_hidden);
-    case Form::Row64R16: return row64_variant_supported(hidden, n_hidden);
-    case Form::Oct: return oct_variant_supported(hidden, n_hidden);
-    case Form::Row: case Form::RowTree: return row_variant_supported(hidden, n_hidden);
-    case Form::Multi2: case Form::Multi4: case Form::Multi4Tree:
-      return multi_variant_supported(hidden, n_hidden);
-    case Form::Quad: case Form::Fused64: case Form::Fused256: return mfma_variant_supported(hidden, n_hidden);
-    default: return false;
-  }
-}
 
 // The network model on a 6 -> hidden x n_hidden -> 4 shape: first row that matches the shape (0 = any), serves the
 // handle's 16-rollout groups per CU (0 = any number), exists for the shape and -- when "mfma" asked for the reference's
@@ -72,11 +59,69 @@ const FormRule kFormRules[] = {
 
 }  // namespace
 
-// the forms of the network model that run by name only, for every layer list they serve (the standard shapes too)
-static bool form_by_name_only(Form f)
-{
-  return f == Form::Lds44 || f == Form::Lds128 || f == Form::Lds16 || f == Form::Glb16 || f == Form::Glb44 || f == Form::Fleet16 || f == Form::FleetMulti4;
-}
+// The descriptor table: everything the host knows about a form outside the selection policy above.  First the launch adapters:
+// they pass on what a kernel's launcher takes beside the argument block (d.arg: the row's own integer).
+namespace {
+hipError_t one_mfma(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_mfma(h->hidden, h->n_hidden, a, d.arg, s); }    // arg: threads per workgroup
+hipError_t one_multi(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_multi(h->hidden, h->n_hidden, a, d.arg, s); }  // arg: ND; 44 = ND 4 with the tree output layer
+hipError_t one_oct(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_oct(h->hidden, h->n_hidden, a, s); }
+hipError_t one_row(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_row(h->hidden, h->n_hidden, a, d.arg != 0, s); }  // arg: tree
+hipError_t one_row64(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_row64(h->hidden, h->n_hidden, a, d.arg, s); }   // arg: rollouts per group
+hipError_t one_m44(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_m44(h->hidden, h->n_hidden, a, d.arg != 0, s); }  // arg: split
+hipError_t one_lds44(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_lds44(h->net, a, s); }
+hipError_t one_lds128(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_lds128(h->net, a, s); }
+hipError_t one_lds16(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_lds16(h->net, a, h->num_simds / 4, s); }
+hipError_t one_glb16(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, s); }
+hipError_t one_glb44(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_glb44(h->net, a, h->glb44_cap, s); }
+hipError_t one_fleet(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_fleet_one(h, a); }  // the fleet's kernel with one instance, on the handle's own stream
+hipError_t one_valu_reg(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_valu_reg(h->hidden, h->n_hidden, a, s); }
+hipError_t one_valu(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_valu(h->net, a, s); }
+hipError_t one_bf(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_bf(a, d.arg, s); }  // arg: waves per 64 rollouts
+hipError_t one_bf_row(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_bf_row(a, s); }
+hipError_t batch_quad(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_quad_batch(h0->hidden, h0->n_hidden, qb, s); }
+hipError_t batch_row(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_row_batch(qb, d.arg != 0, s); }
+hipError_t batch_m44(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_m44_batch(h0->n_hidden, qb, s); }
+hipError_t batch_lds44(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_lds44_batch(h0->net, qb, s); }
+hipError_t batch_lds128(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_lds128_batch(h0->net, qb, s); }
+hipError_t batch_glb44(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_glb44_batch(h0->net, qb, h0->glb44_cap, s); }
+hipError_t batch_bf(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_batch(qb, s); }
+hipError_t batch_bf_row(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_row_batch(qb, s); }
+hipError_t fleet_16(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet16(h->net, h_inst, d_inst, n, h->num_simds / 4, s); }
+hipError_t fleet_multi(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet_multi(h->hidden, h->n_hidden, h_inst, d_inst, n, s); }
+constexpr const char *kMfma16 = "mfma16x16x4", *kMfma4 = "mfma4x4x1";
+constexpr FormDesc kForms[] = {
+    // form, image, noise, flags, standard shapes, launch, arg, batch {launch, pair only, same list, waves}, fleet, cap, name {stem, tag, suffix, gen}, ask {first, second, K multiple}
+    {Form::Auto, Image::Mfma, Noise::Never, 0, nullptr, nullptr, 0, {}, nullptr, nullptr, {""}, {}},  // form_of never answers Auto
+    {Form::Fused64, Image::Mfma, Noise::Never, 0, mfma_variant_supported, one_mfma, 64, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_fused_b64"}, {}},
+    {Form::Fused256, Image::Mfma, Noise::Never, 0, mfma_variant_supported, one_mfma, 256, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_fused_b256"}, {"fused"}},
+    {Form::Quad, Image::Mfma, Noise::InKernel, 0, mfma_variant_supported, one_mfma, 512, {batch_quad, false, false, 16}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_quad4w"}, {"quad"}},
+    {Form::Oct, Image::Mfma, Noise::UnlessStandalone, 0, oct_variant_supported, one_oct, 0, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_oct8w", true}, {"oct"}},
+    {Form::Multi2, Image::Mfma, Noise::UnlessStandalone, kPublishes, multi_variant_supported, one_multi, 2, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_multi2", true}, {"multi2", nullptr, 32}},
+    {Form::Multi4, Image::Mfma, Noise::UnlessStandalone, kPublishes, multi_variant_supported, one_multi, 4, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_multi4", true}, {"multi4_gen", nullptr, 64}},
+    {Form::Multi4Tree, Image::Mfma, Noise::UnlessStandalone, kPublishes, multi_variant_supported, one_multi, 44, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_multi4_tree", true}, {"multi4_tree_gen", nullptr, 64}},
+    {Form::Row, Image::Row, Noise::InKernel, kGate, row_variant_supported, one_row, 0, {batch_row, false, false, 16}, nullptr, nullptr, {"valu_row8w", Tag::HiddenLayers}, {}},
+    {Form::RowTree, Image::Row, Noise::InKernel, kGate, row_variant_supported, one_row, 1, {batch_row, false, false, 16}, nullptr, nullptr, {"valu_row8w_tree", Tag::HiddenLayers}, {"row_tree", "row_exact"}},
+    {Form::Row64R16, Image::Row64, Noise::InKernel, 0, row64_variant_supported, one_row64, 16, {}, nullptr, nullptr, {"valu_row64_r16_tree", Tag::HiddenLayers}, {}},
+    {Form::M44, Image::M44, Noise::InKernel, kGate, m44_variant_supported, one_m44, 1, {batch_m44, true, false, 16}, nullptr, nullptr, {kMfma4, Tag::HiddenLayers, "_m44_split_tree"}, {"m44", "m44_chain"}},
+    {Form::M44Chain, Image::M44, Noise::InKernel, 0, m44_variant_supported, one_m44, 0, {}, nullptr, nullptr, {kMfma4, Tag::HiddenLayers, "_m44_tree"}, {}},
+    {Form::Lds44, Image::Lds44, Noise::InKernel, kGate | kByName, nullptr, one_lds44, 0, {batch_lds44, true, true, 16}, nullptr, nullptr, {"mfma4x4x1_lds", Tag::LayersWidth}, {}},
+    {Form::Lds128, Image::Lds128, Noise::InKernel, kGate | kByName, nullptr, one_lds128, 0, {batch_lds128, true, true, 16}, nullptr, nullptr, {"mfma4x4x1_lds2h", Tag::LayersWidth}, {}},
+    {Form::Lds16, Image::Lds16, Noise::Never, kByName, nullptr, one_lds16, 0, {}, nullptr, nullptr, {"mfma16x16x4_lds", Tag::LayersWidth}, {}},
+    {Form::Glb16, Image::Glb16, Noise::Never, kByName, nullptr, one_glb16, 0, {}, nullptr, &mppi_handle::glb16_cap, {"mfma16x16x4_glb", Tag::LayersWidth}, {}},
+    {Form::Glb44, Image::Glb44, Noise::InKernel, kGate | kByName, nullptr, one_glb44, 0, {batch_glb44, true, true, 16}, nullptr, &mppi_handle::glb44_cap, {"mfma4x4x1_glb", Tag::LayersWidth}, {}},
+    {Form::Fleet16, Image::Lds16, Noise::Never, kByName, nullptr, one_fleet, 0, {}, fleet_16, nullptr, {"mfma16x16x4_fleet", Tag::LayersWidth}, {}},
+    {Form::FleetMulti4, Image::Mfma, Noise::Never, kPublishes | kByName, multi_variant_supported, one_fleet, 0, {}, fleet_multi, nullptr, {kMfma16, Tag::HiddenLayers, "_fleet_multi4_tree", true}, {}},
+    {Form::ValuReg, Image::ThetaS, Noise::Never, 0, nullptr, one_valu_reg, 0, {}, nullptr, nullptr, {"valu_reg_lds"}, {}},
+    {Form::ValuLds, Image::Theta, Noise::Never, 0, nullptr, one_valu, 0, {}, nullptr, nullptr, {"valu_lds"}, {}},
+    {Form::Bf1, Image::Theta, Noise::Never, 0, nullptr, one_bf, 1, {}, nullptr, nullptr, {"basis_funcs25_valu"}, {}},
+    {Form::Bf2, Image::Theta, Noise::Never, 0, nullptr, one_bf, 2, {}, nullptr, nullptr, {"basis_funcs25_valu_2w"}, {}},
+    {Form::Bf3, Image::Theta, Noise::InKernel, 0, nullptr, one_bf, 3, {batch_bf, false, false, 3}, nullptr, nullptr, {"basis_funcs25_valu_3w"}, {}},
+    {Form::BfRow, Image::BfRow, Noise::InKernel, kGate | kByName | kNegateYaw, nullptr, one_bf_row, 0, {batch_bf_row, true, false, 16}, nullptr, nullptr, {"basis_funcs25_row8w"}, {}},
+};
+static_assert(rows_in_order(kForms, &FormDesc::form), "row i of kForms describes form i");
+}  // namespace
+const FormDesc &form_desc(Form f) { return kForms[(int)f]; }
+static bool form_supported(Form f, int hidden, int n_hidden) { return kForms[(int)f].shape && kForms[(int)f].shape(hidden, n_hidden); }
 
 Form form_of(const mppi_handle *h)
 {
@@ -88,7 +133,7 @@ Form form_of(const mppi_handle *h)
     if (3 * (h->K / 64) <= h->num_simds) return Form::Bf3;
     return (2 * (h->K / 64) <= 2 * h->num_simds) ? Form::Bf2 : Form::Bf1;
   }
-  if (form_by_name_only(h->forced)) return h->forced;
+  if (form_desc(h->forced).has(kByName)) return h->forced;
   if (!use_mfma(h)) return use_valu_reg(h) ? Form::ValuReg : Form::ValuLds;
   if (h->forced != Form::Auto) return h->forced;
   const int groups = h->K / kRolloutsPerWave, cus = h->num_simds / 4;
@@ -113,23 +158,9 @@ bool form_generator_noise(const mppi_handle *h)
 // does the rollout kernel draw eps itself (a control / noise wavefront with the in-kernel MRG32k3a)?
 bool has_noise_wave(const mppi_handle *h)
 {
-  switch (form_of(h)) {
-    case Form::Bf3: case Form::Quad: case Form::Row: case Form::RowTree: case Form::Row64R16: case Form::M44: case Form::M44Chain:
-    case Form::Lds44: case Form::Lds128: case Form::Glb44: case Form::BfRow:
-      return true;
-    case Form::Oct: case Form::Multi2: case Form::Multi4: case Form::Multi4Tree:
-      return !form_generator_noise(h);
-    default:
-      return false;
-  }
+  const Noise n = form_desc(form_of(h)).noise;
+  return n == Noise::InKernel || (n == Noise::UnlessStandalone && !form_generator_noise(h));
 }
-
-int form_bf_waves(Form f) { return f == Form::Bf3 ? 3 : f == Form::Bf2 ? 2 : 1; }
-int form_multi_nd(Form f)  // launch_rollout_multi's code: 44 = multi4 with the tree output layer
-{
-  return f == Form::Multi2 ? 2 : f == Form::Multi4 ? 4 : 44;
-}
-int form_fused_threads(Form f) { return f == Form::Quad ? 512 : f == Form::Fused256 ? 256 : 64; }
 
 }  // namespace mppi_abi
 
@@ -151,41 +182,120 @@ static int resident_cap_of(const char *suffix)
   return atoi(p);
 }
 
+// The request names of mppi_set_rollout_variant.  A request is refused by the first of its preconditions that does not hold, in the
+// order of the columns: model kind, shape, K multiple, LDS limit, image present, preparation step.  (Every K multiple divides 64
+// and mppi_create refuses a K that 64 does not divide: that check is a guard no caller can see, whatever its place.)
+namespace {
+using Shape = bool (*)(const mppi_handle *h, Form f);  // f: the form the request would force
+bool table_shape(const mppi_handle *h, Form) { return h->mfma_ok; }
+bool form_shape(const mppi_handle *h, Form f) { return h->mfma_ok && form_supported(f, h->hidden, h->n_hidden); }
+bool lds44_shape(const mppi_handle *h, Form) { return lds44_supported(h->net); }
+bool lds128_shape(const mppi_handle *h, Form) { return lds128_lds_bytes(h->net) != 0; }
+bool lds16_shape(const mppi_handle *h, Form) { return lds16_lds_bytes(h->net) != 0; }
+bool glb16_shape(const mppi_handle *h, Form) { return glb16_supported(h->net); }
+bool glb44_shape(const mppi_handle *h, Form) { return glb44_supported(h->net); }
+// the image of a form built on request; without parameters yet: mppi_set_nn_params builds it
+int build_image(mppi_handle *h, Form f)
+{
+  const Image id = form_desc(f).image;
+  return (!image(h, id) && h->have_nn) ? upload_image(h, id) : MPPI_OK;
+}
+int prepare_fleet(mppi_handle *h, Form) { return fleet_prepare(h); }
+
+enum class Model { Any, Network, Basis };
+enum class Gen { Keep, Off, On };  // multi_standalone_noise: eps from the stand-alone generator ("_gen")
+struct Request {
+  const char *name;         // the spelling; with_cap: "<name>" or "<name>_r<N>" (at most N blocks / quads of the stream resident)
+  bool with_cap;
+  Form net, bf;             // the form it forces on the network model / on the basis-function model
+  int pref;                 // >= 0: the request is a preference (Pref), and a form forced earlier does not stick
+  Gen gen;
+  Model model;              // refusal: "<name> is a form of the ... model"
+  Shape shape;              // nullptr: any
+  const char *shape_msg;
+  int k_multiple;           // with k_msg
+  const char *k_msg;
+  size_t (*lds_bytes)(const NetDesc &net);  // the LDS the weights of the list need per <lds_unit>, held against lds_limit()
+  size_t (*lds_limit)();
+  const char *lds_unit;
+  bool needs_image;         // the form's image was allocated with the handle; refusal: "<name> form: this handle has no image"
+  int (*prepare)(mppi_handle *h, Form f);
+};
+const char kRowMsg[] = "row form exists for 6-32x2-4", kM44Msg[] = "m44 form exists for 6-64x2-4 and 6-64x4-4",
+           kRow64Msg[] = "row64 form exists for 6-64x2-4 and 6-64x4-4", kOctMsg[] = "oct form exists for 6-64x2-4 and 6-64x4-4",
+           kMultiMsg[] = "multi form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4", kMultiK[] = "multi form needs K to be a multiple of 16 ND",
+           kLds128Msg[] = "lds128 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer",
+           kLds16Msg[] = "lds16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer",
+           kGlb16Msg[] = "glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer",
+           kGlb44Msg[] = "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer";
+constexpr int kNoPref = -1;
+const Request kRequests[] = {
+    // name, with cap, network form, basis form, pref, gen | model, shape, its refusal | K multiple | LDS bytes, limit, unit | image | preparation
+    {"auto", false, Form::Auto, Form::Auto, (int)Pref::Auto, Gen::Keep},
+    // the table again, restricted to the forms in the reference's order
+    {"mfma", false, Form::Auto, Form::Auto, (int)Pref::Mfma, Gen::Keep, Model::Any, table_shape, "MFMA variant needs 6-HxN-4 with H in {32,64}, N in {2,4}"},
+    {"valu", false, Form::Auto, Form::Auto, (int)Pref::Valu, Gen::Keep},
+    {"valu_lds", false, Form::Auto, Form::Auto, (int)Pref::ValuLds, Gen::Keep},
+    {"quad", false, Form::Quad, Form::Bf2, kNoPref, Gen::Keep},
+    {"bf3", false, Form::Bf3, Form::Bf3, kNoPref, Gen::Keep, Model::Basis},
+    // the latency form of the basis-function model; the bits of bf3
+    {"bf_row", false, Form::BfRow, Form::BfRow, kNoPref, Gen::Keep, Model::Basis, nullptr, nullptr, kRolloutsPerWave, "bf_row form needs K to be a multiple of 16", nullptr, nullptr, nullptr, true},
+    {"row", false, Form::Row, Form::Row, kNoPref, Gen::Keep, Model::Any, form_shape, kRowMsg},
+    {"row_exact", false, Form::Row, Form::Row, kNoPref, Gen::Keep, Model::Any, form_shape, kRowMsg},
+    {"row_tree", false, Form::RowTree, Form::RowTree, kNoPref, Gen::Keep, Model::Any, form_shape, kRowMsg},
+    {"m44", false, Form::M44, Form::M44, kNoPref, Gen::Keep, Model::Any, form_shape, kM44Msg},
+    {"m44_chain", false, Form::M44Chain, Form::M44Chain, kNoPref, Gen::Keep, Model::Any, form_shape, kM44Msg},
+    // any layer list up to 64 wide; the reference's order in every layer
+    {"lds44", false, Form::Lds44, Form::Lds44, kNoPref, Gen::Keep, Model::Network, lds44_shape,
+     "lds44 form needs 6 -> hidden widths 1..64 -> 4 with at least one hidden layer"},
+    // any layer list up to 128 wide whose image fits one workgroup's LDS: the latency form, the throughput form
+    {"lds128", false, Form::Lds128, Form::Lds128, kNoPref, Gen::Keep, Model::Network, lds128_shape, kLds128Msg, 1, nullptr,
+     lds128_lds_bytes, lds128_lds_limit, "group", true},
+    {"lds16", false, Form::Lds16, Form::Lds16, kNoPref, Gen::Keep, Model::Network, lds16_shape, kLds16Msg, 1, nullptr,
+     lds16_lds_bytes, lds16_lds_limit, "workgroup", true},
+    // lds16's wave, image and lists; up to 64 such handles share the launches of a batched solve
+    {"fleet16", false, Form::Fleet16, Form::Fleet16, kNoPref, Gen::Keep, Model::Network, lds16_shape,
+     "fleet16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer", 1, nullptr, lds16_lds_bytes, lds16_lds_limit,
+     "workgroup", true, prepare_fleet},
+    // "multi4_tree_gen"'s workgroup and bits (eps from the stand-alone generator: no form with the in-kernel one); up to 64 such
+    // handles share the launches of a batched solve
+    {"fleet_multi4", false, Form::FleetMulti4, Form::FleetMulti4, kNoPref, Gen::On, Model::Network, form_shape,
+     "fleet_multi4 form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4", 64, "fleet_multi4 form needs K to be a multiple of 64", nullptr, nullptr, nullptr, false, prepare_fleet},
+    // lds16's wave / lds128's group for every layer list up to 256 wide
+    {"glb16", true, Form::Glb16, Form::Glb16, kNoPref, Gen::Keep, Model::Network, glb16_shape, kGlb16Msg, 64, "glb16 form needs K to be a multiple of 64", nullptr,
+     nullptr, nullptr, false, build_image},
+    {"glb44", true, Form::Glb44, Form::Glb44, kNoPref, Gen::Keep, Model::Network, glb44_shape, kGlb44Msg, kRolloutsPerWave,
+     "glb44 form needs K to be a multiple of 16", nullptr, nullptr, nullptr, false, build_image},
+    // the vector-ALU arm of the 64-wide A/B
+    {"row64", false, Form::Row64R16, Form::Row64R16, kNoPref, Gen::Keep, Model::Any, form_shape, kRow64Msg},
+    {"row64_r16", false, Form::Row64R16, Form::Row64R16, kNoPref, Gen::Keep, Model::Any, form_shape, kRow64Msg},
+    {"oct", false, Form::Oct, Form::Oct, kNoPref, Gen::Off, Model::Any, form_shape, kOctMsg},
+    {"oct_gen", false, Form::Oct, Form::Oct, kNoPref, Gen::On, Model::Any, form_shape, kOctMsg},
+    {"multi2", false, Form::Multi2, Form::Multi2, kNoPref, Gen::Off, Model::Any, form_shape, kMultiMsg, 32, kMultiK},
+    {"multi2_gen", false, Form::Multi2, Form::Multi2, kNoPref, Gen::On, Model::Any, form_shape, kMultiMsg, 32, kMultiK},
+    {"multi4", false, Form::Multi4, Form::Multi4, kNoPref, Gen::Off, Model::Any, form_shape, kMultiMsg, 64, kMultiK},
+    {"multi4_gen", false, Form::Multi4, Form::Multi4, kNoPref, Gen::On, Model::Any, form_shape, kMultiMsg, 64, kMultiK},
+    // ND = 4, butterfly output layer
+    {"multi4_tree", false, Form::Multi4Tree, Form::Multi4Tree, kNoPref, Gen::Off, Model::Any, form_shape, kMultiMsg, 64, kMultiK},
+    {"multi4_tree_gen", false, Form::Multi4Tree, Form::Multi4Tree, kNoPref, Gen::On, Model::Any, form_shape, kMultiMsg, 64, kMultiK},
+    {"fused", false, Form::Fused256, Form::Bf1, kNoPref, Gen::Keep},
+    {"block256", false, Form::Fused256, Form::Bf1, kNoPref, Gen::Keep},
+    {"block64", false, Form::Fused64, Form::Bf1, kNoPref, Gen::Keep},
+};
+}  // namespace
+
 extern "C" {
 
 const char *mppi_rollout_variant(const mppi_handle *h)
 {
   if (!h) return "";
   static thread_local char buf[64];
-  const Form f = form_of(h);
-  const char *gen = form_generator_noise(h) ? "_gen" : "";
-  switch (f) {
-    case Form::Bf3: return "basis_funcs25_valu_3w";
-    case Form::Bf2: return "basis_funcs25_valu_2w";
-    case Form::Bf1: return "basis_funcs25_valu";
-    case Form::BfRow: return "basis_funcs25_row8w";
-    case Form::ValuReg: return "valu_reg_lds";
-    case Form::ValuLds: return "valu_lds";
-    case Form::Multi4Tree: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_multi4_tree%s", h->hidden, h->n_hidden, gen); break;
-    case Form::FleetMulti4: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_fleet_multi4_tree%s", h->hidden, h->n_hidden, gen); break;
-    case Form::Multi2: case Form::Multi4:
-      snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_multi%d%s", h->hidden, h->n_hidden, form_multi_nd(f), gen);
-      break;
-    case Form::Row: snprintf(buf, sizeof(buf), "valu_row8w_h%d_l%d", h->hidden, h->n_hidden); break;
-    case Form::RowTree: snprintf(buf, sizeof(buf), "valu_row8w_tree_h%d_l%d", h->hidden, h->n_hidden); break;
-    case Form::Row64R16: snprintf(buf, sizeof(buf), "valu_row64_r16_tree_h%d_l%d", h->hidden, h->n_hidden); break;
-    case Form::M44: snprintf(buf, sizeof(buf), "mfma4x4x1_h%d_l%d_m44_split_tree", h->hidden, h->n_hidden); break;
-    case Form::M44Chain: snprintf(buf, sizeof(buf), "mfma4x4x1_h%d_l%d_m44_tree", h->hidden, h->n_hidden); break;
-    case Form::Lds44: case Form::Lds128: case Form::Lds16: case Form::Glb16: case Form::Glb44: case Form::Fleet16: {  // the forms of a layer list
-      const char *stem = f == Form::Lds44 ? "mfma4x4x1_lds" : f == Form::Lds128 ? "mfma4x4x1_lds2h" : f == Form::Lds16 ? "mfma16x16x4_lds"
-                         : f == Form::Glb16 ? "mfma16x16x4_glb" : f == Form::Fleet16 ? "mfma16x16x4_fleet" : "mfma4x4x1_glb";
-      snprintf(buf, sizeof(buf), "%s_l%d_w%d", stem, h->net.n_layers - 2, widest_hidden(h->net));
-      break;
-    }
-    case Form::Oct: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_oct8w%s", h->hidden, h->n_hidden, gen); break;
-    case Form::Quad: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_quad4w", h->hidden, h->n_hidden); break;
-    case Form::Fused256: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_fused_b256", h->hidden, h->n_hidden); break;
-    default: snprintf(buf, sizeof(buf), "mfma16x16x4_h%d_l%d_fused_b64", h->hidden, h->n_hidden); break;
+  const FormDesc::Name &nm = form_desc(form_of(h)).name;
+  const char *gen = (nm.gen && form_generator_noise(h)) ? "_gen" : "";
+  switch (nm.tag) {
+    case Tag::Fixed: return nm.stem;
+    case Tag::HiddenLayers: snprintf(buf, sizeof(buf), "%s_h%d_l%d%s%s", nm.stem, h->hidden, h->n_hidden, nm.suffix, gen); break;
+    case Tag::LayersWidth: snprintf(buf, sizeof(buf), "%s_l%d_w%d", nm.stem, h->net.n_layers - 2, widest_hidden(h->net)); break;  // the forms of a layer list
   }
   return buf;
 }
@@ -194,137 +304,39 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
 {
   if (!h || !name) return MPPI_ERR_INVALID;
   DISARM(h);
-  auto need = [&](bool ok, const char *what) { return ok ? MPPI_OK : fail(h, MPPI_ERR_UNSUPPORTED, what); };
-  int rc = MPPI_OK;
-  if (strcmp(name, "auto") == 0) {
-    h->pref = Pref::Auto;
-    h->forced = Form::Auto;
+  const Request *r = nullptr;
+  int cap = -1;
+  for (const Request &q : kRequests) {
+    const size_t len = strlen(q.name);
+    if (q.with_cap ? strncmp(name, q.name, len) != 0 : strcmp(name, q.name) != 0) continue;
+    if (!q.with_cap || (cap = resident_cap_of(name + len)) >= -1) r = &q;
+    break;
   }
-  else if (strcmp(name, "mfma") == 0) {
-    if ((rc = need(h->mfma_ok, "MFMA variant needs 6-HxN-4 with H in {32,64}, N in {2,4}"))) return rc;
-    h->pref = Pref::Mfma;
-    h->forced = Form::Auto;  // the table again, restricted to the forms in the reference's order: a form forced earlier does not stick
-  } else if (strcmp(name, "valu") == 0) { h->pref = Pref::Valu; h->forced = Form::Auto; }
-  else if (strcmp(name, "valu_lds") == 0) { h->pref = Pref::ValuLds; h->forced = Form::Auto; }
-  else if (strcmp(name, "quad") == 0) h->forced = h->basis ? Form::Bf2 : Form::Quad;
-  else if (strcmp(name, "bf3") == 0) {
-    if ((rc = need(h->basis, "bf3 is a form of the basis-function model"))) return rc;
-    h->forced = Form::Bf3;
+  if (!r) return fail(h, MPPI_ERR_INVALID, "unknown variant");
+  char msg[160];
+  auto refuse = [&](const char *what) { return fail(h, MPPI_ERR_UNSUPPORTED, what); };
+  if (r->model != Model::Any && h->basis != (r->model == Model::Basis)) {
+    snprintf(msg, sizeof(msg), "%s is a form of the %s model", r->name, r->model == Model::Basis ? "basis-function" : "network");
+    return refuse(msg);
   }
-  else if (strcmp(name, "bf_row") == 0) {  // the latency form of the basis-function model; the bits of bf3
-    if ((rc = need(h->basis, "bf_row is a form of the basis-function model"))) return rc;
-    if ((rc = need(h->K % kRolloutsPerWave == 0, "bf_row form needs K to be a multiple of 16"))) return rc;
-    if ((rc = need(h->d_bfrowpack != nullptr, "bf_row form: this handle has no image"))) return rc;
-    h->forced = Form::BfRow;
+  const Form f = h->basis ? r->bf : r->net;
+  if (r->shape && !r->shape(h, f)) return refuse(r->shape_msg);
+  if (r->k_msg && h->K % r->k_multiple != 0) return refuse(r->k_msg);
+  if (r->lds_bytes && r->lds_bytes(h->net) > r->lds_limit()) {
+    snprintf(msg, sizeof(msg), "%s form: the weights of this layer list need %zu bytes of LDS per %s, %zu are available", r->name,
+             r->lds_bytes(h->net), r->lds_unit, r->lds_limit());
+    return refuse(msg);
   }
-  else if (strcmp(name, "row") == 0 || strcmp(name, "row_exact") == 0 || strcmp(name, "row_tree") == 0) {
-    if ((rc = need(h->mfma_ok && row_variant_supported(h->hidden, h->n_hidden), "row form exists for 6-32x2-4"))) return rc;
-    h->forced = strcmp(name, "row_tree") == 0 ? Form::RowTree : Form::Row;
+  if (r->needs_image && !image(h, form_desc(f).image)) {
+    snprintf(msg, sizeof(msg), "%s form: this handle has no image", r->name);
+    return refuse(msg);
   }
-  else if (strcmp(name, "m44") == 0 || strcmp(name, "m44_chain") == 0) {
-    if ((rc = need(h->mfma_ok && m44_variant_supported(h->hidden, h->n_hidden), "m44 form exists for 6-64x2-4 and 6-64x4-4"))) return rc;
-    h->forced = name[3] == 0 ? Form::M44 : Form::M44Chain;
-  }
-  else if (strcmp(name, "lds44") == 0) {  // any layer list up to 64 wide; the reference's order in every layer
-    if ((rc = need(!h->basis, "lds44 is a form of the network model"))) return rc;
-    if ((rc = need(lds44_supported(h->net), "lds44 form needs 6 -> hidden widths 1..64 -> 4 with at least one hidden layer"))) return rc;
-    h->forced = Form::Lds44;
-  }
-  else if (strcmp(name, "lds128") == 0) {  // any layer list up to 128 wide whose image fits one workgroup's LDS
-    if ((rc = need(!h->basis, "lds128 is a form of the network model"))) return rc;
-    const size_t bytes = lds128_lds_bytes(h->net);
-    if ((rc = need(bytes != 0, "lds128 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer"))) return rc;
-    if (bytes > lds128_lds_limit()) {
-      char msg[160];
-      snprintf(msg, sizeof(msg), "lds128 form: the weights of this layer list need %zu bytes of LDS per group, %zu are available",
-               bytes, lds128_lds_limit());
-      return fail(h, MPPI_ERR_UNSUPPORTED, msg);
-    }
-    if ((rc = need(h->d_lds128pack != nullptr, "lds128 form: this handle has no image"))) return rc;
-    h->forced = Form::Lds128;
-  }
-  else if (strcmp(name, "lds16") == 0) {  // the throughput form of any layer list up to 128 wide whose image fits one workgroup's LDS
-    if ((rc = need(!h->basis, "lds16 is a form of the network model"))) return rc;
-    const size_t bytes = lds16_lds_bytes(h->net);
-    if ((rc = need(bytes != 0, "lds16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer"))) return rc;
-    if (bytes > lds16_lds_limit()) {
-      char msg[160];
-      snprintf(msg, sizeof(msg), "lds16 form: the weights of this layer list need %zu bytes of LDS per workgroup, %zu are available",
-               bytes, lds16_lds_limit());
-      return fail(h, MPPI_ERR_UNSUPPORTED, msg);
-    }
-    if ((rc = need(h->d_lds16pack != nullptr, "lds16 form: this handle has no image"))) return rc;
-    h->forced = Form::Lds16;
-  }
-  else if (strcmp(name, "fleet16") == 0) {  // lds16's wave, image and lists; up to 64 such handles share the launches of a batched solve
-    if ((rc = need(!h->basis, "fleet16 is a form of the network model"))) return rc;
-    const size_t bytes = lds16_lds_bytes(h->net);
-    if ((rc = need(bytes != 0, "fleet16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer"))) return rc;
-    if (bytes > lds16_lds_limit()) {
-      char msg[160];
-      snprintf(msg, sizeof(msg), "fleet16 form: the weights of this layer list need %zu bytes of LDS per workgroup, %zu are available",
-               bytes, lds16_lds_limit());
-      return fail(h, MPPI_ERR_UNSUPPORTED, msg);
-    }
-    if ((rc = need(h->d_lds16pack != nullptr, "fleet16 form: this handle has no image"))) return rc;
-    if ((rc = fleet_prepare(h))) return rc;
-    h->forced = Form::Fleet16;
-  }
-  else if (strcmp(name, "fleet_multi4") == 0) {  // "multi4_tree_gen"'s workgroup and bits; up to 64 such handles share the launches of a batched solve
-    if ((rc = need(!h->basis, "fleet_multi4 is a form of the network model"))) return rc;
-    if ((rc = need(h->mfma_ok && multi_variant_supported(h->hidden, h->n_hidden), "fleet_multi4 form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4"))) return rc;
-    if ((rc = need(h->K % 64 == 0, "fleet_multi4 form needs K to be a multiple of 64"))) return rc;  // a guard: mppi_create refuses such a K
-    if ((rc = fleet_prepare(h))) return rc;
-    h->forced = Form::FleetMulti4;
-    h->multi_standalone_noise = true;  // eps from the stand-alone generator: no form with the in-kernel one
-  }
-  else if (strncmp(name, "glb16", 5) == 0) {  // lds16's wave for every layer list up to 256 wide; "glb16_r<N>": at most N stream blocks resident
-    const int cap = resident_cap_of(name + 5);
-    if (cap < -1) return fail(h, MPPI_ERR_INVALID, "unknown variant");
-    if ((rc = need(!h->basis, "glb16 is a form of the network model"))) return rc;
-    if ((rc = need(glb16_supported(h->net), "glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer"))) return rc;
-    if ((rc = need(h->K % 64 == 0, "glb16 form needs K to be a multiple of 64"))) return rc;
-    if (!h->d_glb16pack && h->have_nn && (rc = upload_glb16_image(h))) return rc;  // without parameters yet: mppi_set_nn_params builds it
-    h->glb16_cap = cap;
-    h->forced = Form::Glb16;
-  }
-  else if (strncmp(name, "glb44", 5) == 0) {  // lds128's group for every layer list up to 256 wide; "glb44_r<N>": at most N stream quads resident
-    const int cap = resident_cap_of(name + 5);
-    if (cap < -1) return fail(h, MPPI_ERR_INVALID, "unknown variant");
-    if ((rc = need(!h->basis, "glb44 is a form of the network model"))) return rc;
-    if ((rc = need(glb44_supported(h->net), "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer"))) return rc;
-    if ((rc = need(h->K % kRolloutsPerWave == 0, "glb44 form needs K to be a multiple of 16"))) return rc;
-    if (!h->d_glb44pack && h->have_nn && (rc = upload_glb44_image(h))) return rc;  // without parameters yet: mppi_set_nn_params builds it
-    h->glb44_cap = cap;
-    h->forced = Form::Glb44;
-  }
-  else if (strcmp(name, "row64") == 0 || strcmp(name, "row64_r16") == 0) {  // the vector-ALU arm of the 64-wide A/B
-    if ((rc = need(h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden), "row64 form exists for 6-64x2-4 and 6-64x4-4"))) return rc;
-    h->forced = Form::Row64R16;
-  }
-  else if (strcmp(name, "oct") == 0 || strcmp(name, "oct_gen") == 0) {
-    if ((rc = need(h->mfma_ok && oct_variant_supported(h->hidden, h->n_hidden), "oct form exists for 6-64x2-4 and 6-64x4-4"))) return rc;
-    h->forced = Form::Oct;
-    h->multi_standalone_noise = name[3] != 0;
-  }
-  else if (strcmp(name, "multi4_tree") == 0 || strcmp(name, "multi4_tree_gen") == 0) {  // ND = 4, butterfly output layer
-    if ((rc = need(h->K % 64 == 0, "multi form needs K to be a multiple of 16 ND"))) return rc;
-    if ((rc = need(h->mfma_ok && multi_variant_supported(h->hidden, h->n_hidden), "multi form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4"))) return rc;
-    h->forced = Form::Multi4Tree;
-    h->multi_standalone_noise = name[11] != 0;
-  }
-  else if (strncmp(name, "multi", 5) == 0) {
-    const int nd = name[5] - '0';
-    const bool gen = strcmp(name + 6, "_gen") == 0;
-    if ((nd != 2 && nd != 4) || (name[6] != 0 && !gen)) return fail(h, MPPI_ERR_INVALID, "unknown variant");
-    if ((rc = need(h->K % (16 * nd) == 0, "multi form needs K to be a multiple of 16 ND"))) return rc;
-    if ((rc = need(h->mfma_ok && multi_variant_supported(h->hidden, h->n_hidden), "multi form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4"))) return rc;
-    h->forced = nd == 2 ? Form::Multi2 : Form::Multi4;
-    h->multi_standalone_noise = gen;
-  }
-  else if (strcmp(name, "fused") == 0 || strcmp(name, "block256") == 0) h->forced = h->basis ? Form::Bf1 : Form::Fused256;
-  else if (strcmp(name, "block64") == 0) h->forced = h->basis ? Form::Bf1 : Form::Fused64;
-  else return fail(h, MPPI_ERR_INVALID, "unknown variant");
+  if (r->prepare)
+    if (int rc = r->prepare(h, f)) return rc;
+  if (r->pref >= 0) h->pref = (Pref)r->pref;
+  if (form_desc(f).cap) h->*form_desc(f).cap = cap;
+  h->forced = f;
+  if (r->gen != Gen::Keep) h->multi_standalone_noise = r->gen == Gen::On;
   return MPPI_OK;
 }
 
@@ -340,17 +352,10 @@ int mppi_debug_form_candidates(const mppi_handle *h, const char **names, int max
   for (const FormRule &r : kFormRules) {
     if ((r.hidden != 0 && r.hidden != h->hidden) || (r.n_hidden != 0 && r.n_hidden != h->n_hidden)) continue;
     if (!form_supported(r.form, h->hidden, h->n_hidden)) continue;
-    switch (r.form) {
-      case Form::M44: put("m44"); put("m44_chain"); break;
-      case Form::Oct: put("oct"); break;
-      case Form::RowTree: put("row_tree"); put("row_exact"); break;
-      case Form::Quad: put("quad"); break;
-      case Form::Multi2: if (h->K % 32 == 0) put("multi2"); break;
-      case Form::Multi4Tree: if (h->K % 64 == 0) put("multi4_tree_gen"); break;
-      case Form::Multi4: if (h->K % 64 == 0) put("multi4_gen"); break;
-      case Form::Fused256: put("fused"); break;
-      default: break;
-    }
+    const FormDesc::Ask &ask = form_desc(r.form).ask;
+    if (h->K % ask.k_multiple != 0) continue;
+    if (ask.first) put(ask.first);
+    if (ask.second) put(ask.second);
   }
   return n;
 }

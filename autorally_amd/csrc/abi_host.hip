@@ -155,7 +155,7 @@ static bool ddp_fleet_together(mppi_handle *const *hs, int n)
   if (n < 2) return false;
   for (int i = 0; i < n; i++) {
     const mppi_handle *h = hs[i];
-    if (h->basis || !h->have_nn || !h->d_theta || !h->d_tracepack || h->cfg.device != hs[0]->cfg.device) return false;
+    if (h->basis || !h->have_nn || !image(h, Image::Theta) || !image(h, Image::Trace) || h->cfg.device != hs[0]->cfg.device) return false;
   }
   return true;
 }
@@ -200,8 +200,8 @@ static int ddp_fleet_launch(mppi_handle *const *hs, const float *states, const f
     memcpy(in + 7 + (size_t)7 * T, us[i], sizeof(float) * (size_t)T * kControlDim);
     DdpFleetArgs &a = da[i];
     a = DdpFleetArgs{};
-    a.theta = h->d_theta;
-    a.wimg = h->d_tracepack;
+    a.theta = image(h, Image::Theta);
+    a.wimg = image(h, Image::Trace);
     a.in = w.d_in + in_off[i];
     a.out = w.d_out + out_off[i];
     a.work = w.d_work + work_off[i];
@@ -264,7 +264,7 @@ static bool nominal_fleet_together(mppi_handle *const *hs, int n)
   if (n < 2) return false;
   for (int i = 0; i < n; i++) {
     const mppi_handle *h = hs[i];
-    if (h->basis || !h->have_nn || !h->d_tracepack || h->cfg.device != hs[0]->cfg.device) return false;
+    if (h->basis || !h->have_nn || !image(h, Image::Trace) || h->cfg.device != hs[0]->cfg.device) return false;
   }
   return true;
 }
@@ -310,7 +310,7 @@ static int nominal_fleet_launch(mppi_handle *const *hs, const float *states, flo
       const mppi_handle *h = hs[i];
       NominalFleetArgs &a = na[i - at];
       a = NominalFleetArgs{};
-      a.wimg = h->d_tracepack;
+      a.wimg = image(h, Image::Trace);
       a.in = w.d_in + in_off[i];
       a.out = w.d_out + out_off[i];
       a.T = h->T;

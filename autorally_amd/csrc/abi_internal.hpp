@@ -70,8 +70,31 @@ enum class Form : int {
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
   BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
                                     // riders per 16 rollouts), the bits of Bf1..3; by name only ("bf_row")
+  Count
 };
 enum class Pref : int { Auto = 0, Mfma, Valu, ValuLds };
+
+// Device images of the model's weights (abi_pack.hip: kImages says which handles have one, its size and how it is packed)
+enum class Image : int {
+  Theta = 0,  // the parameters as they were set (basis-function model: W[4][25])
+  ThetaS,     // theta with hidden-layer biases * kTanhScale (register VALU kernel)
+  Mfma,       // 6-HxN-4: register image of rollout_mfma.hip / rollout_multi.hip / rollout_oct.hip
+  Row,        // 6-32-32-4: the weights in the register order of the row form (rollout_row.hip)
+  BfRow,      // basis-function model: the per-lane image of rollout_bf_row.hip
+  Row64,      // 64-wide nets: register + LDS image of rollout_row64.hip
+  M44,        // 64-wide nets: image of rollout_m44.hip
+  Lds44,      // any layer list with hidden widths <= 64: image of rollout_lds44.hip
+  Lds128,     // any layer list with hidden widths <= 128 whose image fits the LDS: image of rollout_lds128.hip
+  Lds16,      // the same lists: image of rollout_lds16.hip (and of rollout_fleet16.hip)
+  Glb16,      // image of rollout_glb16.hip: only a handle that asked for "glb16" has one (built at that call)
+  Glb44,      // image of rollout_glb44.hip: only a handle that asked for "glb44" has one (built at that call)
+  Trace,      // network model: k-major image of rollout_trace.hip (every layer's W transposed)
+  Count
+};
+struct DeviceImage {
+  float *d = nullptr;
+  size_t bytes = 0;
+};
 
 struct Events {
   // e[0..3]: markers on the handle's stream before noise / before rollout / after rollout / after tail;
@@ -174,26 +197,12 @@ struct mppi_handle {
   hipEvent_t ev_gt[2] = {nullptr, nullptr};
   bool gen_timed = false, gen_time_now = false;
   float *d_costs = nullptr, *d_w = nullptr;
-  float *d_theta = nullptr, *d_wpack = nullptr, *d_map = nullptr;
-  float *d_theta_s = nullptr;  // theta with hidden-layer biases * kTanhScale (register VALU kernel)
-  float *d_rowpack = nullptr;  // 6-32-32-4: the weights in the register order of the row form (rollout_row.hip)
-  float *d_bfrowpack = nullptr;  // basis-function model: the per-lane image of rollout_bf_row.hip
-  float *d_row64pack = nullptr;  // 64-wide nets: register + LDS image of rollout_row64.hip
-  float *d_m44pack = nullptr;    // 64-wide nets: image of rollout_m44.hip
-  float *d_lds44pack = nullptr;  // any layer list with hidden widths <= 64: image of rollout_lds44.hip
-  float *d_lds128pack = nullptr; // any layer list with hidden widths <= 128 whose image fits the LDS: image of rollout_lds128.hip
-  size_t lds128_bytes = 0;       // ... and its size
-  float *d_lds16pack = nullptr;  // the same lists: image of rollout_lds16.hip
-  size_t lds16_bytes = 0;        // ... and its size
+  float *d_map = nullptr;
+  mppi_abi::DeviceImage img[(int)mppi_abi::Image::Count];  // the weight images this handle has (d == nullptr: not this one)
   mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16", "fleet_multi4": the argument block of this handle's own launches (on its own stream); only a
                                  // handle that asked for the form has one
-  float *d_glb16pack = nullptr;  // image of rollout_glb16.hip: only a handle that asked for "glb16" has one (built at that call)
-  size_t glb16_bytes = 0;        // ... and its size
   int glb16_cap = -1;            // "glb16_r<N>": the cap on the resident stream blocks; -1: none
-  float *d_glb44pack = nullptr;  // image of rollout_glb44.hip: only a handle that asked for "glb44" has one (built at that call)
-  size_t glb44_bytes = 0;        // ... and its size
   int glb44_cap = -1;            // "glb44_r<N>": the cap on the resident stream quads; -1: none
-  float *d_tracepack = nullptr;  // network model: k-major image of rollout_trace.hip (every layer's W transposed)
   // mppi_trace_rollouts: the records of one chunk of trace_chunk rollouts -- states [c][T][7], controls [c][T][2], step costs
   // [c][T], costs [c], first_crash [c] (int) -- allocated with the handle (nothing is allocated or freed while armed); the
   // chunk's rollout indices reach the kernel through host-mapped memory (h_trace_ks / d_trace_ks: no upload on the stream)
@@ -284,19 +293,27 @@ inline hipError_t ensure_device(int dev)
   } while (0)
 
 int compute_k99(int K);
-std::vector<float> pack_mfma_weights(const std::vector<float> &theta, int H, int NHID);
-std::vector<float> pack_row_weights(const std::vector<float> &theta);
-std::vector<float> pack_bf_row_weights(const std::vector<float> &W);
-std::vector<float> pack_row64_weights(const std::vector<float> &theta, int NHID);
-std::vector<float> pack_m44_weights(const std::vector<float> &theta, int NHID);
-std::vector<float> pack_lds44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
-std::vector<float> pack_lds128_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
-std::vector<float> pack_lds16_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
-std::vector<float> pack_glb16_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
-int upload_glb16_image(mppi_handle *h);  // (re)builds d_glb16pack from h->theta (allocates it at the first call)
-std::vector<float> pack_glb44_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
-int upload_glb44_image(mppi_handle *h);  // (re)builds d_glb44pack from h->theta (allocates it at the first call)
-std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
+// a table with one row per member of an enum (whose last member is Count): row i describes member i
+template <class Row, class Id, size_t N>
+constexpr bool rows_in_order(const Row (&rows)[N], Id Row::*id)
+{
+  for (size_t i = 0; i < N; i++)
+    if ((size_t)(rows[i].*id) != i) return false;
+  return N == (size_t)Id::Count;
+}
+// abi_pack.hip: one row per weight image, indexed by Image
+struct ImageDesc {
+  Image id;                                           // the row's own index
+  bool (*has)(const mppi_handle *h);                  // which handles have it
+  size_t (*floats)(const mppi_handle *h);             // its size
+  std::vector<float> (*pack)(const mppi_handle *h);   // from h->theta
+  bool on_request;          // built when mppi_set_rollout_variant asks for its form (upload_image allocates it), not with the handle
+  const char *size_check;   // the refusal where the packed size is not the allocated one; nullptr: not checked
+};
+const ImageDesc &image_desc(Image id);  // row id of the table
+inline float *image(const mppi_handle *h, Image id) { return h->img[(int)id].d; }
+int upload_image(mppi_handle *h, Image id);  // packs the image from h->theta and copies it (an image built on request: allocated at the first call)
+int upload_images(mppi_handle *h);           // every image the handle has, and the one the form it asked for by name needs
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
 int upload_rng_tables(mppi_handle *h);
 bool use_mfma(const mppi_handle *h);
@@ -304,16 +321,51 @@ bool use_valu_reg(const mppi_handle *h);
 Form form_of(const mppi_handle *h);
 bool form_generator_noise(const mppi_handle *h);
 bool has_noise_wave(const mppi_handle *h);
-int form_bf_waves(Form f);
-int form_multi_nd(Form f);
-int form_fused_threads(Form f);
-inline bool form_is_row(Form f) { return f == Form::Row || f == Form::RowTree; }
-inline bool form_is_row64(Form f) { return f == Form::Row64R16; }
-// the latency forms with riders, which have a gated kernel: the row forms, the automatic m44 form, lds44, lds128, glb44, bf_row
-inline bool form_has_gate(Form f)
-{
-  return form_is_row(f) || f == Form::M44 || f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44 || f == Form::BfRow;
-}
+
+// abi_forms.hip: what the host knows about a rollout form, one row per form, indexed by Form
+struct FormDesc;
+using LaunchFn = hipError_t (*)(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t stream);
+using BatchFn = hipError_t (*)(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t stream);
+using FleetFn = hipError_t (*)(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t stream);
+enum class Noise { Never, InKernel, UnlessStandalone };  // does the kernel draw eps itself?  UnlessStandalone (oct, multi): unless the
+                                                          // stand-alone generator was asked for ("_gen") or is the automatic choice
+enum class Tag { Fixed, HiddenLayers, LayersWidth };      // the reported name: stem [+ "_h%d_l%d" | "_l%d_w%d"] + suffix [+ "_gen"]
+enum : unsigned {
+  kGate = 1,       // has a gated kernel (mppi_arm): the latency forms with riders
+  kPublishes = 2,  // publishes its minimum cost for the streaming tail (multi_group.hpp)
+  kByName = 4,     // runs by name only, for every model it serves
+  kNegateYaw = 8,  // forces negate_yaw_der (bf_row: its kinematics are the riders'; computeKinematics of the basis-function model
+                   // always negates the yaw rate, generalized_linear.cu:212-217 -- the model's own kernels never look at the flag)
+};
+struct FormDesc {
+  Form form;       // the row's own index
+  Image image;     // RolloutArgs::wpack
+  Noise noise;
+  unsigned flags;  // kGate | ...
+  bool (*shape)(int hidden, int n_hidden);  // the standard shapes 6 -> hidden x n_hidden -> 4 it exists for; nullptr: not a form of those
+  LaunchFn launch;
+  int arg;         // what the launch adapter passes on: waves (bf), ND code (multi), block threads (mfma), rollouts per group (row64), tree / split
+  struct Batch {   // one launch for the handles of a batch (batch_together); launch == nullptr: none
+    BatchFn launch = nullptr;
+    bool pair_only = false;   // the pair of a tick only; else up to kMaxBatch
+    bool same_list = false;   // the whole layer list must agree, not only hidden x n_hidden
+    int waves = 0;            // waves per 64 rollouts that need a SIMD of their own
+  } batch;                    // (a form with a resident cap batches only handles of one cap)
+  FleetFn fleet;              // the launch shared by a fleet (mppi_compute_control_batch); != nullptr: a fleet form
+  int mppi_handle::*cap;      // "<form>_r<N>": where the handle keeps the cap on the resident part; nullptr: the form has none
+  struct Name {
+    const char *stem;
+    Tag tag = Tag::Fixed;
+    const char *suffix = "";
+    bool gen = false;         // takes "_gen" where eps comes from the stand-alone generator
+  } name;
+  struct Ask {                // mppi_debug_form_candidates: the requests that time this form where kFormRules names it
+    const char *first = nullptr, *second = nullptr;
+    int k_multiple = 1;
+  } ask;
+  bool has(unsigned f) const { return (flags & f) != 0; }
+};
+const FormDesc &form_desc(Form f);  // row f of the table
 hipStream_t batch_stream(int device);
 // abi_solve.hip: the argument block beside a device's batch stream, shared by every fleet on the device and never destroyed.
 // mu: held while a batched solve, a batched DDP pass or a batched nominal replay stages, sends and launches (the latter two: until
@@ -329,6 +381,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
 // a rollout launch that is followed by its tail kernel: the tag its minimum cost travels under (a.min_cost, a.min_cost_tag)
 int tag_min_cost(mppi_handle *h, RolloutArgs &a, hipStream_t stream);
 int launch_rollout(mppi_handle *h, const RolloutArgs &a);
+hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a);  // a handle of a fleet form solved alone
 int fleet_prepare(mppi_handle *h);  // what a handle that asks for "fleet16" or "fleet_multi4" needs of its own (fleet_one), once
 int check_ready(mppi_handle *h);
 int launch_generator(mppi_handle *h, float *dst);

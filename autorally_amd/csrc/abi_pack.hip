@@ -390,26 +390,6 @@ std::vector<float> pack_glb16_weights(const std::vector<float> &theta, const Net
   const size_t floats = (size_t)glb16_pack_floats(net);
   return floats ? pack_mfma16_image(theta, net, glb16_net_of(net), floats) : std::vector<float>();
 }
-// the device image of a handle that asked for a partly resident form by name: allocated at the first call, rebuilt from h->theta
-// at every call.  pk: the packed image; what: "<form> image size"
-static int upload_named_image(mppi_handle *h, const std::vector<float> &pk, float *&d_img, size_t &bytes, const char *what)
-{
-  if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, what);
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (!d_img) {
-    bytes = pk.size() * sizeof(float);
-    HIPCHK(h, hipMalloc(&d_img, bytes));
-  }
-  if (pk.size() * sizeof(float) != bytes) return fail(h, MPPI_ERR_INVALID, what);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(d_img, pk.data(), bytes, hipMemcpyHostToDevice));
-  return MPPI_OK;
-}
-int upload_glb16_image(mppi_handle *h)
-{
-  return upload_named_image(h, pack_glb16_weights(h->theta, h->net), h->d_glb16pack, h->glb16_bytes, "glb16 image size");
-}
-
 // Image of rollout_glb44.hip, any layer list with hidden widths <= 256, in 1 KB quads: float4 q of lane l at float4 index q * 64 + l.
 // First kGlb44BiasQuads quads: float h of quad j of lane l = bias of neuron 64 h + l of weight layer j (hidden layers: b x
 // kTanhScale, 0 where the neuron does not exist; output layer, float 0: b_out[l >> 4]).  Then per weight layer ceil(nin / 4) x H
@@ -440,10 +420,6 @@ std::vector<float> pack_glb44_weights(const std::vector<float> &theta, const Net
     p += (size_t)nout * nin + nout;
   }
   return out;
-}
-int upload_glb44_image(mppi_handle *h)
-{
-  return upload_named_image(h, pack_glb44_weights(h->theta, h->net), h->d_glb44pack, h->glb44_bytes, "glb44 image size");
 }
 
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset)
@@ -517,6 +493,82 @@ std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mpp
     off += nin * nout + nout;
   }
   return img;
+}
+
+
+// The weight images, one row per Image: which handles have one, its size in floats, how it is packed from h->theta.
+namespace {
+using H = const mppi_handle *;
+size_t num_params(H h) { return (size_t)h->net.num_params; }
+// theta with the hidden-layer biases pre-scaled for tanh_bias
+std::vector<float> pack_scaled_theta(H h)
+{
+  std::vector<float> ts(h->theta);
+  size_t off = 0;
+  for (int l = 0; l + 1 < h->net.n_layers; l++) {
+    const size_t nin = h->net.layers[l], nout = h->net.layers[l + 1];
+    if (l + 2 < h->net.n_layers)
+      for (size_t j = 0; j < nout; j++) ts[off + nin * nout + j] = ts[off + nin * nout + j] * kTanhScale;
+    off += nin * nout + nout;
+  }
+  return ts;
+}
+constexpr ImageDesc kImages[] = {
+    // image, which handles have it, floats, packed image, built on request, size check
+    {Image::Theta, [](H) { return true; }, num_params, [](H h) { return h->theta; }, false, nullptr},
+    {Image::ThetaS, [](H h) { return !h->basis; }, num_params, pack_scaled_theta, false, nullptr},
+    {Image::Mfma, [](H h) { return h->mfma_ok; }, [](H h) { return (size_t)64 * mfma_pack_floats_per_lane(h->hidden, h->n_hidden); },
+     [](H h) { return pack_mfma_weights(h->theta, h->hidden, h->n_hidden); }, false, nullptr},
+    {Image::Row, [](H h) { return h->mfma_ok && row_variant_supported(h->hidden, h->n_hidden); }, [](H) { return (size_t)row_pack_floats(); },
+     [](H h) { return pack_row_weights(h->theta); }, false, nullptr},
+    {Image::BfRow, [](H h) { return h->basis; }, [](H) { return (size_t)bf_row_pack_floats(); }, [](H h) { return pack_bf_row_weights(h->theta); }, false, nullptr},
+    {Image::Row64, [](H h) { return h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden); }, [](H h) { return (size_t)row64_pack_floats(h->n_hidden); },
+     [](H h) { return pack_row64_weights(h->theta, h->n_hidden); }, false, nullptr},
+    {Image::M44, [](H h) { return h->mfma_ok && m44_variant_supported(h->hidden, h->n_hidden); }, [](H h) { return (size_t)m44_pack_floats(h->n_hidden); },
+     [](H h) { return pack_m44_weights(h->theta, h->n_hidden); }, false, "m44 image size"},
+    {Image::Lds44, [](H h) { return !h->basis && lds44_supported(h->net); }, [](H h) { return (size_t)lds44_pack_floats(h->net); },
+     [](H h) { return pack_lds44_weights(h->theta, h->net); }, false, nullptr},
+    {Image::Lds128, [](H h) { return !h->basis && lds128_supported(h->net); }, [](H h) { return (size_t)lds128_pack_floats(h->net); },
+     [](H h) { return pack_lds128_weights(h->theta, h->net); }, false, "lds128 image size"},
+    {Image::Lds16, [](H h) { return !h->basis && lds16_supported(h->net); }, [](H h) { return (size_t)lds16_pack_floats(h->net); },
+     [](H h) { return pack_lds16_weights(h->theta, h->net); }, false, "lds16 image size"},
+    {Image::Glb16, [](H h) { return !h->basis && glb16_supported(h->net); }, [](H h) { return (size_t)glb16_pack_floats(h->net); },
+     [](H h) { return pack_glb16_weights(h->theta, h->net); }, true, "glb16 image size"},
+    {Image::Glb44, [](H h) { return !h->basis && glb44_supported(h->net); }, [](H h) { return (size_t)glb44_pack_floats(h->net); },
+     [](H h) { return pack_glb44_weights(h->theta, h->net); }, true, "glb44 image size"},
+    {Image::Trace, [](H h) { return !h->basis; }, num_params, [](H h) { return pack_trace_weights(h->theta, h->net); }, false, nullptr},
+};
+static_assert(rows_in_order(kImages, &ImageDesc::id), "row i of kImages describes image i");
+}  // namespace
+const ImageDesc &image_desc(Image id) { return kImages[(int)id]; }
+
+int upload_image(mppi_handle *h, Image id)
+{
+  const ImageDesc &im = image_desc(id);
+  DeviceImage &di = h->img[(int)id];
+  const std::vector<float> pk = im.pack(h);
+  if (im.on_request) {  // of a handle that asked for the form by name: allocated at the first call, rebuilt from h->theta at every call
+    if (pk.empty() || h->theta.size() != (size_t)h->net.num_params) return fail(h, MPPI_ERR_INVALID, im.size_check);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!di.d) {
+      di.bytes = pk.size() * sizeof(float);
+      HIPCHK(h, hipMalloc(&di.d, di.bytes));
+    }
+  }
+  if (im.size_check && pk.size() * sizeof(float) != di.bytes) return fail(h, MPPI_ERR_INVALID, im.size_check);
+  if (im.on_request) HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(di.d, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+  return MPPI_OK;
+}
+
+int upload_images(mppi_handle *h)
+{
+  for (const ImageDesc &im : kImages) {
+    const bool wanted = im.on_request && form_desc(h->forced).image == im.id;  // asked for before the parameters were set
+    if (h->img[(int)im.id].d || wanted)
+      if (int rc = upload_image(h, im.id)) return rc;
+  }
+  return MPPI_OK;
 }
 
 }  // namespace mppi_abi

@@ -99,22 +99,15 @@ int fleet_prepare(mppi_handle *h)
   return MPPI_OK;
 }
 
-// the rollout launch of a fleet form ("fleet16", "fleet_multi4") for the n instances h_inst / d_inst (host and device copies)
-static hipError_t launch_rollout_fleet(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t stream)
-{
-  if (h->forced == Form::FleetMulti4) return launch_rollout_fleet_multi(h->hidden, h->n_hidden, h_inst, d_inst, n, stream);
-  return launch_rollout_fleet16(h->net, h_inst, d_inst, n, h->num_simds / 4, stream);
-}
-
 // a handle of a fleet form solved alone: the fleet's kernel with one instance, its argument block sent on the handle's own stream
-static hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a)
+hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a)
 {
-  if (!h->fleet_one) return hipErrorInvalidValue;
+  if (!h->fleet_one || !form_desc(h->forced).fleet) return hipErrorInvalidValue;
   unsigned char *host = nullptr;
   if (hipError_t e = arg_block_stage(*h->fleet_one, &host); e != hipSuccess) return e;
   memcpy(host, &a, sizeof(RolloutArgs));
   if (hipError_t e = arg_block_send(*h->fleet_one, sizeof(RolloutArgs), h->stream); e != hipSuccess) return e;
-  return launch_rollout_fleet(h, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), 1, h->stream);
+  return form_desc(h->forced).fleet(h, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), 1, h->stream);
 }
 
 void fill_cost_args(const mppi_handle *h, CostArgs &c)
@@ -153,9 +146,8 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
   a.U = h->d_in;
   a.noise = noise;
   a.costs = h->d_costs;
-  const Form f = form_of(h);
-  a.wpack = f == Form::BfRow ? h->d_bfrowpack : form_is_row(f) ? h->d_rowpack : form_is_row64(f) ? h->d_row64pack : (f == Form::M44 || f == Form::M44Chain) ? h->d_m44pack
-            : f == Form::Lds44 ? h->d_lds44pack : f == Form::Lds128 ? h->d_lds128pack : (f == Form::Lds16 || f == Form::Fleet16) ? h->d_lds16pack : f == Form::Glb16 ? h->d_glb16pack : f == Form::Glb44 ? h->d_glb44pack : f == Form::ValuReg ? h->d_theta_s : (f == Form::ValuLds || h->basis) ? h->d_theta : h->d_wpack;
+  const FormDesc &d = form_desc(form_of(h));
+  a.wpack = image(h, d.image);
   a.inv_t = h->d_invt;
   a.K = h->K;
   a.T = h->T;
@@ -167,9 +159,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
     a.u_hi[i] = h->u_hi[i];
   }
   a.dt = h->dt;
-  // (the bf_row form's kinematics are the riders': computeKinematics of the basis-function model always negates the yaw rate,
-  // generalized_linear.cu:212-217 -- its own kernels never look at the flag)
-  a.negate_yaw_der = (h->cfg.negate_yaw_der || f == Form::BfRow) ? 1 : 0;
+  a.negate_yaw_der = (h->cfg.negate_yaw_der || d.has(kNegateYaw)) ? 1 : 0;
   a.rng_in = nullptr;
   a.rng_out = nullptr;
   a.inline_noise = 0;
@@ -190,9 +180,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
 // cost wave costs the rollout kernel 0.6 us, and the tail's own block reduction was never on its critical path) -- not used there.
 static unsigned long long *min_cost_keys(const mppi_handle *h)
 {
-  const Form f = form_of(h);
-  const bool publishes = f == Form::Multi2 || f == Form::Multi4 || f == Form::Multi4Tree || f == Form::FleetMulti4;  // multi_group.hpp
-  return (h->use_min_cost && tail_is_stream(h->K) && publishes) ? h->d_min_cost : nullptr;
+  return (h->use_min_cost && tail_is_stream(h->K) && form_desc(form_of(h)).has(kPublishes)) ? h->d_min_cost : nullptr;
 }
 
 int tag_min_cost(mppi_handle *h, RolloutArgs &a, hipStream_t stream)
@@ -209,32 +197,8 @@ int tag_min_cost(mppi_handle *h, RolloutArgs &a, hipStream_t stream)
 
 int launch_rollout(mppi_handle *h, const RolloutArgs &a)
 {
-  // basis-function model: the two-wave form while both waves of a group get a SIMD of their own
-  const Form f = form_of(h);
-  hipError_t e = hipSuccess;
-  switch (f) {
-    case Form::Bf1: case Form::Bf2: case Form::Bf3: e = launch_rollout_bf(a, form_bf_waves(f), h->stream); break;
-    case Form::BfRow: e = launch_rollout_bf_row(a, h->stream); break;
-    case Form::Multi2: case Form::Multi4: case Form::Multi4Tree:
-      e = launch_rollout_multi(h->hidden, h->n_hidden, a, form_multi_nd(f), h->stream);
-      break;
-    case Form::Oct: e = launch_rollout_oct(h->hidden, h->n_hidden, a, h->stream); break;
-    case Form::M44: e = launch_rollout_m44(h->hidden, h->n_hidden, a, true, h->stream); break;
-    case Form::M44Chain: e = launch_rollout_m44(h->hidden, h->n_hidden, a, false, h->stream); break;
-    case Form::Lds44: e = launch_rollout_lds44(h->net, a, h->stream); break;
-    case Form::Lds128: e = launch_rollout_lds128(h->net, a, h->stream); break;
-    case Form::Lds16: e = launch_rollout_lds16(h->net, a, h->num_simds / 4, h->stream); break;
-    case Form::Fleet16: case Form::FleetMulti4: e = launch_rollout_fleet_one(h, a); break;
-    case Form::Glb16: e = launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, h->stream); break;
-    case Form::Glb44: e = launch_rollout_glb44(h->net, a, h->glb44_cap, h->stream); break;
-    case Form::Row64R16: e = launch_rollout_row64(h->hidden, h->n_hidden, a, 16, h->stream); break;
-    case Form::Row: case Form::RowTree: e = launch_rollout_row(h->hidden, h->n_hidden, a, f == Form::RowTree, h->stream); break;
-    case Form::Quad: case Form::Fused64: case Form::Fused256:
-      e = launch_rollout_mfma(h->hidden, h->n_hidden, a, form_fused_threads(f), h->stream);
-      break;
-    case Form::ValuReg: e = launch_rollout_valu_reg(h->hidden, h->n_hidden, a, h->stream); break;
-    default: e = launch_rollout_valu(h->net, a, h->stream); break;
-  }
+  const FormDesc &d = form_desc(form_of(h));
+  const hipError_t e = d.launch ? d.launch(h, d, a, h->stream) : hipErrorInvalidValue;
   if (e != hipSuccess) return fail(h, MPPI_ERR_HIP, "rollout launch", e);
   h->launch_instances = 1;
   h->launch_gated = a.gate != nullptr;
@@ -683,15 +647,15 @@ int enqueue_solve(mppi_handle *h, const float *state)
 // d_in at the one it smooths into.
 
 // The forms that have a gated rollout and gain from it (one iteration, no stage events, no capture): 1: a latency form with
-// riders (the row forms, the automatic m44 form, the lds44, lds128 and glb44 forms, the basis-function model's bf_row form) and its in-kernel generator; 2: the automatic multi4-tree form with the
-// stand-alone generator kernel prefetched on a second stream; 0: none
+// riders (kGate: the row forms, the automatic m44 form, the lds44, lds128 and glb44 forms, the basis-function model's bf_row form) and its in-kernel generator; 2: the automatic multi4-tree form with the
+// stand-alone generator kernel prefetched on a second stream; 0: none (the basis-function model's other forms among them: no kGate)
 static int arm_kind(const mppi_handle *h)
 {
   const Form f = form_of(h);
   if (!(h->d_gate != nullptr && wants_slid_copy(h) && h->cfg.num_iters == 1 && !h->timing && !h->capture &&
-        h->explicit_iters == 0 && (!h->basis || f == Form::BfRow) && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
+        h->explicit_iters == 0 && h->fault_wave == 0 && h->have_nn && h->have_map && h->have_cost && !h->timed_out))
     return 0;
-  if (form_has_gate(f) && has_noise_wave(h) && !h->prefetch_valid) return 1;
+  if (form_desc(f).has(kGate) && has_noise_wave(h) && !h->prefetch_valid) return 1;
   // (where the generator kernel runs beside the rollout.  Where it runs behind it -- 32-wide nets at K = 65 536 -- the phase
   // between two rollouts is the generator's own 41 us whatever the launches cost: chained 0.3139, unchained 0.3131 ms)
   if (f == Form::Multi4Tree && h->forced == Form::Auto && !has_noise_wave(h) && h->gen_async && gen_beside_rollout(h)) return 2;
@@ -912,16 +876,8 @@ static int open_armed(mppi_handle *h, const float *state)
 // the rollout of a batch batch_together admits, in one launch on S; gated: every argument block carries its handle's gate block
 static hipError_t launch_rollout_batch(mppi_handle *const *hs, int n, const QuadBatchArgs &qb, bool gated, hipStream_t S)
 {
-  const mppi_handle *h0 = hs[0];
-  const Form f = form_of(h0);
-  const hipError_t e = f == Form::BfRow   ? launch_rollout_bf_row_batch(qb, S)
-                       : h0->basis        ? launch_rollout_bf_batch(qb, S)
-                       : form_is_row(f)   ? launch_rollout_row_batch(qb, f == Form::RowTree, S)
-                       : f == Form::M44   ? launch_rollout_m44_batch(h0->n_hidden, qb, S)
-                       : f == Form::Lds44 ? launch_rollout_lds44_batch(h0->net, qb, S)
-                       : f == Form::Lds128 ? launch_rollout_lds128_batch(h0->net, qb, S)
-                       : f == Form::Glb44 ? launch_rollout_glb44_batch(h0->net, qb, h0->glb44_cap, S)
-                                          : launch_rollout_quad_batch(h0->hidden, h0->n_hidden, qb, S);
+  const FormDesc &d = form_desc(form_of(hs[0]));
+  const hipError_t e = d.batch.launch ? d.batch.launch(hs[0], d, qb, S) : hipErrorInvalidValue;
   if (e != hipSuccess) return e;
   for (int i = 0; i < n; i++) {
     hs[i]->launch_instances = n;
@@ -936,8 +892,7 @@ static bool batch_together(mppi_handle *const *hs, int n);
 static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
 {
   mppi_handle *h0 = hs[0];
-  const Form f0 = form_of(h0);
-  if (!form_has_gate(f0))
+  if (!form_desc(form_of(h0)).has(kGate))
     return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
   for (int i = 0; i < n; i++)
     if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");
@@ -989,21 +944,21 @@ static bool batch_together(mppi_handle *const *hs, int n)
   int waves = 0;
   for (int i = 0; i < n && together; i++) {
     const mppi_handle *h = hs[i];
-    // network model: the four-wavefront form; basis-function model: its three-wavefront form (in-kernel generator)
+    // the forms with a batched kernel (FormDesc::Batch) -- network model: the four-wavefront form, the row forms; basis-function
+    // model: its three-wavefront form (in-kernel generator)
     const Form f = form_of(h);
+    const FormDesc &d = form_desc(f);
     // the pair of a tick only (their batched kernels exist for two instances): the automatic m44 form of one network shape; the
     // lds44 / lds128 / glb44 form (by name only: forced on every handle) of one WHOLE layer list -- one layer list and one image size
     // serve the launch
     // (glb44: and one cap on the resident quads -- one dynamic-LDS size)
-    const bool by_list = f == Form::Lds44 || f == Form::Lds128 || f == Form::Glb44;
-    const bool wide = f == Form::M44 || by_list;
+    // (... or the pair of the basis-function model's bf_row form, by name only: forced on both handles)
+    const bool wide = d.batch.pair_only && !h->basis;
     bool same_list = h->net.n_layers == h0->net.n_layers;
     for (int l = 0; l < h->net.n_layers && same_list; l++) same_list = h->net.layers[l] == h0->net.layers[l];
-    // (... or the pair of its bf_row form, by name only: forced on both handles)
-    const bool form_ok = h->basis ? (h0->basis && (f == Form::Bf3 || (f == Form::BfRow && n == 2)) && f == form_of(h0))
-                                  : (!h0->basis && (f == Form::Quad || form_is_row(f) || (wide && n == 2)) && f == form_of(h0) &&
-                                     h->hidden == h0->hidden && h->n_hidden == h0->n_hidden && (!by_list || same_list) &&
-                                     (f != Form::Glb44 || h->glb44_cap == h0->glb44_cap));
+    const bool form_ok = d.batch.launch != nullptr && (!d.batch.pair_only || n == 2) && f == form_of(h0) && h->basis == h0->basis &&
+                         h->hidden == h0->hidden && h->n_hidden == h0->n_hidden && (!d.batch.same_list || same_list) &&
+                         (!d.cap || h->*d.cap == h0->*d.cap);
     // one kernel instance serves the whole batch: the instances must agree on what it is specialised for (affine / projective
     // costmap transform, control cost or none) -- a superset kernel would compute 0 * x where the single solve computes
     // nothing, which differs for a non-finite x; such a pair is solved one by one.
@@ -1020,7 +975,7 @@ static bool batch_together(mppi_handle *const *hs, int n)
                h->K <= 4096 && !h->timing && !h->capture && !h->prefetch_valid && h->have_nn && h->have_map && h->have_cost;
     // waves of a group that need a SIMD each: quad 4, row 4 dynamics waves (its riders ride), basis functions 3 per 64 rollouts
     // (bf_row: the row form's 4 per 16)
-    waves += (h->basis && f != Form::BfRow) ? 3 * (h->K / 64) : 4 * (h->K / kRolloutsPerWave);
+    waves += d.batch.waves * (h->K / 64);
   }
   return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
 }
@@ -1039,7 +994,7 @@ static bool fleet_together(mppi_handle *const *hs, int n)
   fill_cost_args(h0, c0);
   for (int i = 0; i < n; i++) {
     const mppi_handle *h = hs[i];
-    if (h->basis || (h0->forced != Form::Fleet16 && h0->forced != Form::FleetMulti4) || h->forced != h0->forced || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
+    if (h->basis || !form_desc(h0->forced).fleet || h->forced != h0->forced || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
     if (h->net.n_layers != h0->net.n_layers) return false;
     for (int l = 0; l < h->net.n_layers; l++)
       if (h->net.layers[l] != h0->net.layers[l]) return false;
@@ -1123,7 +1078,7 @@ static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
     const unsigned char *dev = fb->args.d;
     if (e == hipSuccess) e = launch_noise_fleet(nd, reinterpret_cast<const NoiseFleetDesc *>(dev + fleet_noise_offset(n)), n, S);
     if (e == hipSuccess)
-      e = launch_rollout_fleet(h0, ra, reinterpret_cast<const RolloutArgs *>(dev), n, S);
+      e = form_desc(h0->forced).fleet(h0, ra, reinterpret_cast<const RolloutArgs *>(dev), n, S);
     if (e == hipSuccess) e = launch_solve_tail_fleet(tl, n, dev + fleet_tail_offset(n), S);
     if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "fleet launch", e));
     for (int i = 0; i < n; i++) {
@@ -1227,7 +1182,7 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
   if (!together && fleet_together(hs, n)) return enqueue_fleet(hs, states, n);  // the "fleet16" / "fleet_multi4" forms: 2..64 handles, three launches
   if (!together && n >= 2) {
     // a set of "fleet16" (or of "fleet_multi4") handles with one that is not ready: its error before any of the others has moved
-    bool all_fleet = h0->forced == Form::Fleet16 || h0->forced == Form::FleetMulti4;
+    bool all_fleet = form_desc(h0->forced).fleet != nullptr;
     for (int i = 0; i < n; i++) all_fleet = all_fleet && hs[i]->forced == h0->forced;
     for (int i = 0; i < n && all_fleet; i++)
       if (const int rc = check_ready(hs[i])) return rc;

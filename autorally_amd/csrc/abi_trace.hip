@@ -71,7 +71,7 @@ int mppi_trace_rollouts(mppi_handle *h, const int *ks, int n, float *states, flo
   for (int i = 0; i < kStateDim; i++) a.state[i] = h->solve_state[i];
   a.V = h->v_buf;
   a.ks = h->d_trace_ks;
-  a.wimg = h->basis ? h->d_theta : h->d_tracepack;
+  a.wimg = image(h, h->basis ? Image::Theta : Image::Trace);
   a.inv_t = h->d_invt;
   a.states = states ? d_states : nullptr;
   a.controls = controls ? d_controls : nullptr;

@@ -43,10 +43,12 @@ int own_stream(mppi_handle *h)
 void free_all(mppi_handle *h)
 {
   if (!h) return;
-  float *fp[] = {h->d_theta_s, h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
-                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_theta, h->d_wpack, h->d_map, h->d_part, h->d_rowpack, h->d_bfrowpack, h->d_row64pack, h->d_m44pack, h->d_lds44pack, h->d_lds128pack, h->d_lds16pack, h->d_glb16pack, h->d_glb44pack, h->d_cap, h->d_tracepack, h->d_trace};
+  float *fp[] = {h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
+                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_map, h->d_part, h->d_cap, h->d_trace};
   for (float *p : fp)
     if (p) (void)hipFree(p);
+  for (const DeviceImage &im : h->img)
+    if (im.d) (void)hipFree(im.d);
   if (h->d_invt) (void)hipFree(h->d_invt);
   if (h->d_counter) (void)hipFree(h->d_counter);
   if (h->d_gx) (void)hipFree(h->d_gx);
@@ -235,26 +237,13 @@ int mppi_create(const mppi_config *cfg, mppi_handle **out)
   CR(hipMalloc(&h->d_w, sizeof(float) * h->K));
   CR(hipMalloc(&h->d_costs_alt, sizeof(float) * h->K));
   CR(hipMalloc(&h->d_w_alt, sizeof(float) * h->K));
-  CR(hipMalloc(&h->d_theta, sizeof(float) * h->net.num_params));
-  CR(hipMalloc(&h->d_theta_s, sizeof(float) * h->net.num_params));
-  if (h->mfma_ok)
-    CR(hipMalloc(&h->d_wpack, sizeof(float) * 64 * (size_t)mfma_pack_floats_per_lane(h->hidden, h->n_hidden)));
-  if (h->mfma_ok && row_variant_supported(h->hidden, h->n_hidden)) CR(hipMalloc(&h->d_rowpack, sizeof(float) * (size_t)row_pack_floats()));
-  if (basis) CR(hipMalloc(&h->d_bfrowpack, sizeof(float) * (size_t)bf_row_pack_floats()));
-  if (h->mfma_ok && row64_variant_supported(h->hidden, h->n_hidden))
-    CR(hipMalloc(&h->d_row64pack, sizeof(float) * (size_t)row64_pack_floats(h->n_hidden)));
-  if (h->mfma_ok && m44_variant_supported(h->hidden, h->n_hidden))
-    CR(hipMalloc(&h->d_m44pack, sizeof(float) * (size_t)m44_pack_floats(h->n_hidden)));
-  if (!basis && lds44_supported(h->net)) CR(hipMalloc(&h->d_lds44pack, sizeof(float) * (size_t)lds44_pack_floats(h->net)));
-  if (!basis && lds128_supported(h->net)) {
-    h->lds128_bytes = sizeof(float) * (size_t)lds128_pack_floats(h->net);
-    CR(hipMalloc(&h->d_lds128pack, h->lds128_bytes));
+  for (int i = 0; i < (int)Image::Count; i++) {  // the weight images that are built with the handle
+    const ImageDesc &im = image_desc((Image)i);
+    if (im.on_request || !im.has(h)) continue;
+    DeviceImage &di = h->img[i];
+    di.bytes = sizeof(float) * im.floats(h);
+    CR(hipMalloc(&di.d, di.bytes));
   }
-  if (!basis && lds16_supported(h->net)) {
-    h->lds16_bytes = sizeof(float) * (size_t)lds16_pack_floats(h->net);
-    CR(hipMalloc(&h->d_lds16pack, h->lds16_bytes));
-  }
-  if (!basis) CR(hipMalloc(&h->d_tracepack, sizeof(float) * h->net.num_params));
   h->trace_chunk = std::min(h->K, kTraceChunk);
   CR(hipMalloc(&h->d_trace, sizeof(float) * (size_t)h->trace_chunk * ((size_t)h->T * (kStateDim + kControlDim + 1) + 2)));
   CR(hipHostMalloc(&h->h_trace_ks, sizeof(int) * (size_t)h->trace_chunk, hipHostMallocMapped));
@@ -340,11 +329,7 @@ int mppi_set_bf_params(mppi_handle *h, const float *W, size_t n)
   OWN(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->theta.assign(W, W + n);
-  HIPCHK(h, hipMemcpy(h->d_theta, W, n * sizeof(float), hipMemcpyHostToDevice));
-  {
-    const std::vector<float> pk = pack_bf_row_weights(h->theta);
-    HIPCHK(h, hipMemcpy(h->d_bfrowpack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  if (int rc = upload_images(h)) return rc;
   h->have_nn = true;
   return MPPI_OK;
 }
@@ -359,60 +344,8 @@ int mppi_set_nn_params(mppi_handle *h, const float *theta, size_t n)
   OWN(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->theta.assign(theta, theta + n);
-  HIPCHK(h, hipMemcpy(h->d_theta, theta, n * sizeof(float), hipMemcpyHostToDevice));
-  {
-    std::vector<float> ts(h->theta);  // hidden-layer biases pre-scaled for tanh_bias
-    size_t off = 0;
-    for (int l = 0; l + 1 < h->net.n_layers; l++) {
-      const size_t nin = h->net.layers[l], nout = h->net.layers[l + 1];
-      if (l + 2 < h->net.n_layers)
-        for (size_t j = 0; j < nout; j++) ts[off + nin * nout + j] = ts[off + nin * nout + j] * kTanhScale;
-      off += nin * nout + nout;
-    }
-    HIPCHK(h, hipMemcpy(h->d_theta_s, ts.data(), n * sizeof(float), hipMemcpyHostToDevice));
-  }
   h->hnet.init(h->net.layers, h->net.n_layers, h->theta.data());
-  if (h->mfma_ok) {
-    const std::vector<float> pk = pack_mfma_weights(h->theta, h->hidden, h->n_hidden);
-    HIPCHK(h, hipMemcpy(h->d_wpack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (h->d_rowpack) {
-    const std::vector<float> pk = pack_row_weights(h->theta);
-    HIPCHK(h, hipMemcpy(h->d_rowpack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (h->d_row64pack) {
-    const std::vector<float> pk = pack_row64_weights(h->theta, h->n_hidden);
-    HIPCHK(h, hipMemcpy(h->d_row64pack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (h->d_m44pack) {
-    const std::vector<float> pk = pack_m44_weights(h->theta, h->n_hidden);
-    if ((int)pk.size() != m44_pack_floats(h->n_hidden)) return fail(h, MPPI_ERR_INVALID, "m44 image size");
-    HIPCHK(h, hipMemcpy(h->d_m44pack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (h->d_lds44pack) {
-    const std::vector<float> pk = pack_lds44_weights(h->theta, h->net);
-    HIPCHK(h, hipMemcpy(h->d_lds44pack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  if (h->d_lds128pack) {
-    const std::vector<float> pk = pack_lds128_weights(h->theta, h->net);
-    if (pk.size() * sizeof(float) != h->lds128_bytes) return fail(h, MPPI_ERR_INVALID, "lds128 image size");
-    HIPCHK(h, hipMemcpy(h->d_lds128pack, pk.data(), h->lds128_bytes, hipMemcpyHostToDevice));
-  }
-  if (h->d_lds16pack) {
-    const std::vector<float> pk = pack_lds16_weights(h->theta, h->net);
-    if (pk.size() * sizeof(float) != h->lds16_bytes) return fail(h, MPPI_ERR_INVALID, "lds16 image size");
-    HIPCHK(h, hipMemcpy(h->d_lds16pack, pk.data(), h->lds16_bytes, hipMemcpyHostToDevice));
-  }
-  if (h->d_glb16pack || h->forced == Form::Glb16) {
-    if (int rc = upload_glb16_image(h)) return rc;
-  }
-  if (h->d_glb44pack || h->forced == Form::Glb44) {
-    if (int rc = upload_glb44_image(h)) return rc;
-  }
-  {
-    const std::vector<float> pk = pack_trace_weights(h->theta, h->net);
-    HIPCHK(h, hipMemcpy(h->d_tracepack, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  if (int rc = upload_images(h)) return rc;
   h->have_nn = true;
   return MPPI_OK;
 }
@@ -807,10 +740,10 @@ int mppi_debug_dynamics(mppi_handle *h, int n, const float *states, const float 
   hipError_t e = hipMemcpy(d_s, states, sizeof(float) * 7 * n, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_u, controls, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
   if (e == hipSuccess)
-    e = h->basis ? launch_dynamics_bf(h->d_theta, d_s, d_u, d_o, n, h->stream)
-        : use_mfma(h) ? launch_dynamics_mfma(h->hidden, h->n_hidden, h->d_wpack, d_s, d_u, d_o, n,
+    e = h->basis ? launch_dynamics_bf(image(h, Image::Theta), d_s, d_u, d_o, n, h->stream)
+        : use_mfma(h) ? launch_dynamics_mfma(h->hidden, h->n_hidden, image(h, Image::Mfma), d_s, d_u, d_o, n,
                                            h->cfg.negate_yaw_der ? 1 : 0, h->stream)
-                    : launch_dynamics_valu(h->net, h->d_theta, d_s, d_u, d_o, n,
+                    : launch_dynamics_valu(h->net, image(h, Image::Theta), d_s, d_u, d_o, n,
                                            h->cfg.negate_yaw_der ? 1 : 0, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e == hipSuccess) e = hipMemcpy(ders, d_o, sizeof(float) * 7 * n, hipMemcpyDeviceToHost);
