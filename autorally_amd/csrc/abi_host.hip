@@ -117,17 +117,18 @@ HostHelper &host_helper()
 
 void host_helper_arm() { host_helper().arm(); }
 
-// The batched DDP pass (mppi_compute_feedback_gains_batch -> ddp_fleet_kernel): ONE set of buffers per device beside the device's
-// batch stream, grown on demand and never destroyed -- the instances' inputs (pinned staging -> device, one copy), their results
-// (device -> pinned, one copy) and the kernel's records.  Used under the device's FleetBlock::mu, from staging until the results
-// are unpacked; the stream is idle in them whenever the mutex is free.
-struct DdpFleetWork {
+// The buffers of a batched host pass: ONE set per purpose and device beside the device's batch stream, grown on demand and never
+// destroyed -- the instances' inputs (pinned staging -> device, one copy), their results (device -> pinned, one copy) and, where
+// the kernel keeps records, its work area.  Used under the device's FleetBlock::mu, from staging until the results are unpacked;
+// the stream is idle in them whenever the mutex is free.
+struct FleetWork {
   float *d_in = nullptr, *d_out = nullptr, *d_work = nullptr, *h_in = nullptr, *h_out = nullptr;
   size_t in_cap = 0, out_cap = 0, work_cap = 0;  // floats
 };
-static DdpFleetWork g_ddp_work[64];
+static FleetWork g_ddp_work[64];      // mppi_compute_feedback_gains_batch -> ddp_fleet_kernel
+static FleetWork g_nominal_work[64];  // mppi_nominal_traj_batch -> nominal_fleet_kernel
 
-static hipError_t ddp_grow(float **d, float **h, size_t *cap, size_t need)
+static hipError_t fleet_grow(float **d, float **h, size_t *cap, size_t need)
 {
   if (need <= *cap) return hipSuccess;
   const size_t want = need + need / 2;
@@ -147,6 +148,81 @@ static hipError_t ddp_grow(float **d, float **h, size_t *cap, size_t need)
   return hipSuccess;
 }
 
+static size_t align4(size_t floats) { return (floats + 3) & ~(size_t)3; }
+
+// One batched host pass over the handles hs[0 .. n) of one device: open() -- the device, its batch stream and fleet block, every
+// handle's offsets into the buffers, the block's lock (held until the pass goes out of scope), the buffers, the inputs staged
+// by the caller and sent in one copy; launch() -- the argument blocks of one chunk of at most kMaxFleet handles staged, sent
+// and its kernel enqueued (a chunk's blocks are ordered behind the launch before it, which reads the device block); finish() --
+// the results in one copy and the synchronise.  An error of the enqueues is kept in `e`: the calls after it do nothing and
+// finish() fails every handle with `what`.  The results are in w->h_out, at out_off, once finish() has returned MPPI_OK.
+struct FleetPass {
+  mppi_handle *const *hs;
+  int n;
+  const char *what;
+  hipStream_t S = nullptr;
+  FleetBlock *fb = nullptr;
+  FleetWork *w = nullptr;
+  std::vector<size_t> in_off, out_off, work_off;  // [n + 1] floats, every handle's piece a multiple of four
+  std::unique_lock<std::mutex> lk;
+  hipError_t e = hipSuccess;
+
+  // in_floats / out_floats / work_floats (or nullptr): a handle's pieces; stage(i, in): fills handle i's inputs in pinned memory
+  template <class Stage>
+  int open(FleetWork *work, size_t (*in_floats)(int), size_t (*out_floats)(int), size_t (*work_floats)(int, const NetDesc &), Stage stage)
+  {
+    mppi_handle *h0 = hs[0];
+    const int dev = h0->cfg.device;
+    HIPCHK(h0, ensure_device(dev));
+    S = batch_stream(dev);
+    if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+    fb = fleet_block(dev);
+    if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
+    in_off = out_off = work_off = std::vector<size_t>((size_t)n + 1, 0);
+    for (int i = 0; i < n; i++) {
+      in_off[i + 1] = in_off[i] + align4(in_floats(hs[i]->T));
+      out_off[i + 1] = out_off[i] + align4(out_floats(hs[i]->T));
+      work_off[i + 1] = work_off[i] + (work_floats ? align4(work_floats(hs[i]->T, hs[i]->net)) : 0);
+    }
+    lk = std::unique_lock<std::mutex>(fb->mu);
+    w = &work[dev];
+    if (in_off[n] > w->in_cap || out_off[n] > w->out_cap || work_off[n] > w->work_cap) {
+      HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier pass is behind the buffers; nothing else on the stream reads them
+      HIPCHK(h0, fleet_grow(&w->d_in, &w->h_in, &w->in_cap, in_off[n]));
+      HIPCHK(h0, fleet_grow(&w->d_out, &w->h_out, &w->out_cap, out_off[n]));
+      HIPCHK(h0, fleet_grow(&w->d_work, nullptr, &w->work_cap, work_off[n]));
+    }
+    for (int i = 0; i < n; i++) stage(i, w->h_in + in_off[i]);
+    e = hipMemcpyAsync(w->d_in, w->h_in, sizeof(float) * in_off[n], hipMemcpyHostToDevice, S);
+    return MPPI_OK;
+  }
+
+  // handles [at, at + m): fill(i, a) writes handle i's (zeroed) argument block
+  template <class Args, class Fill>
+  void launch(int at, int m, hipError_t (*kernel)(const Args *, const Args *, int, hipStream_t), Fill fill)
+  {
+    unsigned char *host = nullptr;
+    if (e != hipSuccess || (e = arg_block_stage(fb->args, &host)) != hipSuccess) return;
+    Args *args = reinterpret_cast<Args *>(host);
+    for (int i = at; i < at + m; i++) {
+      args[i - at] = Args{};
+      fill(i, args[i - at]);
+    }
+    e = arg_block_send(fb->args, sizeof(Args) * (size_t)m, S);
+    if (e == hipSuccess) e = kernel(args, reinterpret_cast<const Args *>(fb->args.d), m, S);
+  }
+
+  int finish()
+  {
+    if (e == hipSuccess) e = hipMemcpyAsync(w->h_out, w->d_out, sizeof(float) * out_off[n], hipMemcpyDeviceToHost, S);
+    if (e == hipSuccess) e = hipStreamSynchronize(S);
+    if (e == hipSuccess) return MPPI_OK;
+    (void)hipStreamSynchronize(S);  // nothing enqueued so far is left behind the buffers
+    for (int i = 0; i < n; i++) fail(hs[i], MPPI_ERR_HIP, what, e);
+    return MPPI_ERR_HIP;
+  }
+};
+
 // The sharing rule of the batched DDP pass, next to fleet_together: two or more handles of the network model with parameters set,
 // all on one device.  Layer lists, T, hz, limits and weights may differ: they are data.  (The basis-function model stays on the
 // host: its Jacobian is fp32 central differences through powf, which is ulp-sensitive.)
@@ -160,75 +236,40 @@ static bool ddp_fleet_together(mppi_handle *const *hs, int n)
   return true;
 }
 
-static size_t align4(size_t floats) { return (floats + 3) & ~(size_t)3; }
-
 // n <= kMaxFleet handles of a ddp_fleet_together set: one launch.  xs / us: every handle's target sequences.  Returns MPPI_OK,
 // MPPI_ERR_STATE when a handle's factorisation failed (that handle alone has no result), or the error that stopped the launch.
 static int ddp_fleet_launch(mppi_handle *const *hs, const float *states, const float *const *xs, const float *const *us, int n)
 {
-  mppi_handle *h0 = hs[0];
-  const int dev = h0->cfg.device;
-  HIPCHK(h0, ensure_device(dev));
-  const hipStream_t S = batch_stream(dev);
-  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
-  FleetBlock *fb = fleet_block(dev);
-  if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
-  size_t in_off[kMaxFleet + 1], out_off[kMaxFleet + 1], work_off[kMaxFleet + 1];
-  in_off[0] = out_off[0] = work_off[0] = 0;
-  for (int i = 0; i < n; i++) {
-    in_off[i + 1] = in_off[i] + align4(ddp_fleet_in_floats(hs[i]->T));
-    out_off[i + 1] = out_off[i] + align4(ddp_fleet_out_floats(hs[i]->T));
-    work_off[i + 1] = work_off[i] + align4(ddp_fleet_work_floats(hs[i]->T, hs[i]->net));
-  }
-  std::lock_guard<std::mutex> lk(fb->mu);
-  DdpFleetWork &w = g_ddp_work[dev];
-  if (in_off[n] > w.in_cap || out_off[n] > w.out_cap || work_off[n] > w.work_cap) {
-    HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier pass is behind the buffers; a solve on the stream never reads them
-    HIPCHK(h0, ddp_grow(&w.d_in, &w.h_in, &w.in_cap, in_off[n]));
-    HIPCHK(h0, ddp_grow(&w.d_out, &w.h_out, &w.out_cap, out_off[n]));
-    HIPCHK(h0, ddp_grow(&w.d_work, nullptr, &w.work_cap, work_off[n]));
-  }
-  unsigned char *host = nullptr;
-  HIPCHK(h0, arg_block_stage(fb->args, &host));
-  DdpFleetArgs *da = reinterpret_cast<DdpFleetArgs *>(host);
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    const int T = h->T;
-    float *in = w.h_in + in_off[i];
+  FleetPass p{hs, n, "batched DDP pass"};
+  int rc = p.open(g_ddp_work, ddp_fleet_in_floats, ddp_fleet_out_floats, ddp_fleet_work_floats, [&](int i, float *in) {
+    const int T = hs[i]->T;
     memcpy(in, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
     memcpy(in + 7, xs[i], sizeof(float) * (size_t)T * kStateDim);
     memcpy(in + 7 + (size_t)7 * T, us[i], sizeof(float) * (size_t)T * kControlDim);
-    DdpFleetArgs &a = da[i];
-    a = DdpFleetArgs{};
+  });
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) { hs[i]->have_ddp = false; hs[i]->ddp_on_device = 1; }
+  p.launch(0, n, launch_ddp_fleet, [&](int i, DdpFleetArgs &a) {
+    const mppi_handle *h = hs[i];
     a.theta = image(h, Image::Theta);
     a.wimg = image(h, Image::Trace);
-    a.in = w.d_in + in_off[i];
-    a.out = w.d_out + out_off[i];
-    a.work = w.d_work + work_off[i];
-    a.T = T;
+    a.in = p.w->d_in + p.in_off[i];
+    a.out = p.w->d_out + p.out_off[i];
+    a.work = p.w->d_work + p.work_off[i];
+    a.T = h->T;
     a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
     a.img_lds = ddp_fleet_image_in_lds(h->net) ? 1 : 0;
     a.dt = (float)(1.0 / h->cfg.hz);  // mppi_controller.cu:408
     for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; a.R[j] = h->ddp_R[j]; }
     for (int q = 0; q < kStateDim; q++) { a.Q[q] = h->ddp_Q[q]; a.Qf[q] = h->ddp_Qf[q]; }
     a.net = h->net;
-    h->have_ddp = false;
-    h->ddp_on_device = 1;
-  }
-  hipError_t e = hipMemcpyAsync(w.d_in, w.h_in, sizeof(float) * in_off[n], hipMemcpyHostToDevice, S);
-  if (e == hipSuccess) e = arg_block_send(fb->args, sizeof(DdpFleetArgs) * (size_t)n, S);
-  if (e == hipSuccess) e = launch_ddp_fleet(da, reinterpret_cast<const DdpFleetArgs *>(fb->args.d), n, S);
-  if (e == hipSuccess) e = hipMemcpyAsync(w.h_out, w.d_out, sizeof(float) * out_off[n], hipMemcpyDeviceToHost, S);
-  if (e == hipSuccess) e = hipStreamSynchronize(S);
-  if (e != hipSuccess) {
-    for (int i = 0; i < n; i++) fail(hs[i], MPPI_ERR_HIP, "batched DDP pass", e);
-    return MPPI_ERR_HIP;
-  }
-  int rc = MPPI_OK;
+  });
+  rc = p.finish();
+  if (rc) return rc;
   for (int i = 0; i < n; i++) {
     mppi_handle *h = hs[i];
     const size_t T = (size_t)h->T;
-    const float *o = w.h_out + out_off[i];
+    const float *o = p.w->h_out + p.out_off[i];
     int status = 0;
     memcpy(&status, o + 26 * T + 1, sizeof(int));
     if (status != 0) {
@@ -248,14 +289,6 @@ static int ddp_fleet_launch(mppi_handle *const *hs, const float *states, const f
   return rc;
 }
 
-// The batched nominal replay (mppi_nominal_traj_batch -> nominal_fleet_kernel): its own set of buffers per device, used exactly as
-// the DDP pass uses DdpFleetWork -- under the device's FleetBlock::mu, on the batch stream, grown on demand, never destroyed.
-struct NominalFleetWork {
-  float *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-  size_t in_cap = 0, out_cap = 0;  // floats
-};
-static NominalFleetWork g_nominal_work[64];
-
 // The sharing rule of the batched nominal replay, beside ddp_fleet_together: two or more handles of the network model with
 // parameters set and a trace image, all on one device.  Everything else about a controller is data.  (The basis-function model
 // stays on the host: its functions go through powf, which is ulp-sensitive -- the reason ddp_fleet_together gives.)
@@ -274,65 +307,30 @@ static bool nominal_fleet_together(mppi_handle *const *hs, int n)
 // buffers are written only after EVERY launch has succeeded: an error leaves all of them as they were.
 static int nominal_fleet_launch(mppi_handle *const *hs, const float *states, float *const *state_seqs, float *const *control_seqs, int n)
 {
-  mppi_handle *h0 = hs[0];
-  const int dev = h0->cfg.device;
-  HIPCHK(h0, ensure_device(dev));
-  const hipStream_t S = batch_stream(dev);
-  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
-  FleetBlock *fb = fleet_block(dev);
-  if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
-  std::vector<size_t> in_off((size_t)n + 1), out_off((size_t)n + 1);
-  in_off[0] = out_off[0] = 0;
-  for (int i = 0; i < n; i++) {
-    in_off[i + 1] = in_off[i] + align4(nominal_fleet_in_floats(hs[i]->T));
-    out_off[i + 1] = out_off[i] + align4(nominal_fleet_out_floats(hs[i]->T));
-  }
-  std::lock_guard<std::mutex> lk(fb->mu);
-  NominalFleetWork &w = g_nominal_work[dev];
-  if (in_off[n] > w.in_cap || out_off[n] > w.out_cap) {
-    HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier replay is behind the buffers; nothing else on the stream reads them
-    HIPCHK(h0, ddp_grow(&w.d_in, &w.h_in, &w.in_cap, in_off[n]));
-    HIPCHK(h0, ddp_grow(&w.d_out, &w.h_out, &w.out_cap, out_off[n]));
-  }
-  for (int i = 0; i < n; i++) {
-    float *in = w.h_in + in_off[i];
+  FleetPass p{hs, n, "batched nominal replay"};
+  int rc = p.open(g_nominal_work, nominal_fleet_in_floats, nominal_fleet_out_floats, nullptr, [&](int i, float *in) {
     memcpy(in, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
     memcpy(in + 7, hs[i]->U.data(), sizeof(float) * (size_t)hs[i]->T * kControlDim);
-  }
-  hipError_t e = hipMemcpyAsync(w.d_in, w.h_in, sizeof(float) * in_off[n], hipMemcpyHostToDevice, S);
-  for (int at = 0; at < n && e == hipSuccess; at += kMaxFleet) {
-    const int m = std::min(kMaxFleet, n - at);
-    unsigned char *host = nullptr;
-    e = arg_block_stage(fb->args, &host);
-    if (e != hipSuccess) break;
-    NominalFleetArgs *na = reinterpret_cast<NominalFleetArgs *>(host);
-    for (int i = at; i < at + m; i++) {
+  });
+  if (rc) return rc;
+  for (int at = 0; at < n; at += kMaxFleet)
+    p.launch(at, std::min(kMaxFleet, n - at), launch_nominal_fleet, [&](int i, NominalFleetArgs &a) {
       const mppi_handle *h = hs[i];
-      NominalFleetArgs &a = na[i - at];
-      a = NominalFleetArgs{};
       a.wimg = image(h, Image::Trace);
-      a.in = w.d_in + in_off[i];
-      a.out = w.d_out + out_off[i];
+      a.in = p.w->d_in + p.in_off[i];
+      a.out = p.w->d_out + p.out_off[i];
       a.T = h->T;
       a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
       a.img_lds = nominal_fleet_image_in_lds(h->net) ? 1 : 0;
       a.dt = h->dt;
       for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; }
       a.net = h->net;
-    }
-    e = arg_block_send(fb->args, sizeof(NominalFleetArgs) * (size_t)m, S);  // ordered behind the launch before it, which reads the block
-    if (e == hipSuccess) e = launch_nominal_fleet(na, reinterpret_cast<const NominalFleetArgs *>(fb->args.d), m, S);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(w.h_out, w.d_out, sizeof(float) * out_off[n], hipMemcpyDeviceToHost, S);
-  if (e == hipSuccess) e = hipStreamSynchronize(S);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(S);  // nothing enqueued so far is left behind the buffers
-    for (int i = 0; i < n; i++) fail(hs[i], MPPI_ERR_HIP, "batched nominal replay", e);
-    return MPPI_ERR_HIP;
-  }
+    });
+  rc = p.finish();
+  if (rc) return rc;
   for (int i = 0; i < n; i++) {
     const size_t T = (size_t)hs[i]->T;
-    const float *o = w.h_out + out_off[i];
+    const float *o = p.w->h_out + p.out_off[i];
     memcpy(state_seqs[i], o, sizeof(float) * 7 * T);
     memcpy(control_seqs[i], o + 7 * T, sizeof(float) * 2 * T);
     hs[i]->nominal_on_device = 1;

@@ -4,7 +4,7 @@
 // handle's gains are those of its host pass up to sinf / cosf of the heading, which are the rounded double results here.
 //
 // A pass is three sequential recurrences of T steps and T independent Jacobians -- the latency shape:
-//   A  initial rollout, wave 0: rollout_trace.hip's wave (lane j owns neurons j, j + 64, j + 128, j + 192; activations through an
+//   A  initial rollout, wave 0: wave_net.hpp's per-wave forward (lane j owns neurons j, j + 64, j + 128, j + 192; activations through an
 //      LDS tile as broadcast reads; weights from the k-major image, in LDS where it fits, else from global memory); x[t], the
 //      clamped u[t], sin / cos of the heading and every hidden layer's tanh values are kept per step
 //   B  the T - 1 Jacobians the backward pass reads, step t on wave t mod kDdpFleetWaves: lane = input neuron, four output chains per
@@ -14,8 +14,6 @@
 //      beside Lk), so that a vector's sum is its matrix's sum in the spare lanes
 //   D  forward pass with the gains, wave 0: the wave of A; the per-step costs and their k-ascending total
 // Any layer list mppi_create accepts (widths up to 256) is data.  A factorisation that is not `ok` ends the pass with status 1.
-#include <atomic>
-
 #include "../../include/mppi_hip.h"
 #include "ddp_fleet_device.hpp"
 
@@ -25,8 +23,8 @@ namespace mppi {
 #define MPPI_DDP_FLEET_WAVES 4  // waves per workgroup; only phase B (the Jacobians) uses more than one (a build knob for A/B)
 #endif
 constexpr int kDdpFleetWaves = MPPI_DDP_FLEET_WAVES;
-constexpr int kDdpActFloats = 2 * kDdpMaxWidth;                   // wave 0's two activation tiles
-constexpr int kDdpDeltaFloats = 2 * 4 * kDdpMaxWidth;             // a wave's two delta tiles (float4 per neuron)
+constexpr int kDdpActFloats = 2 * kWaveNetMaxWidth;                   // wave 0's two activation tiles
+constexpr int kDdpDeltaFloats = 2 * 4 * kWaveNetMaxWidth;             // a wave's two delta tiles (float4 per neuron)
 constexpr int kDdpFixedFloats = kDdpActFloats + kDdpFleetWaves * kDdpDeltaFloats;
 constexpr size_t kDdpLdsLimit = 96 * 1024;                        // tiles + image
 // phase C and D reuse wave 0's delta tiles: eleven 8 x 8 tiles, the step's record, the forward pass's row
@@ -55,12 +53,12 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
   float *o_tail = o_cost + H;  // total_cost, status
   float *w_x = work, *w_u = w_x + (size_t)7 * H, *w_sc = w_u + (size_t)2 * H, *w_rec = w_sc + (size_t)2 * H, *w_th = w_rec + (size_t)72 * H;
 
-  float *tile0 = ddp_lds, *tile1 = ddp_lds + kDdpMaxWidth;
+  float *tile0 = ddp_lds, *tile1 = ddp_lds + kWaveNetMaxWidth;
   float *delta = ddp_lds + kDdpActFloats + wave * kDdpDeltaFloats;
   const float *img = wimg;
   if (A.img_lds) {
     float *img_s = ddp_lds + kDdpFixedFloats;
-    for (int i = threadIdx.x; i < net.num_params; i += 64 * kDdpFleetWaves) img_s[i] = wimg[i];
+    wave_net_stage_image(img_s, wimg, net.num_params, 64 * kDdpFleetWaves);
     img = img_s;
   }
   __syncthreads();
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
   for (int t = wave; t < H - 1; t += kDdpFleetWaves) {
     const float sn = w_sc[2 * t], cs = w_sc[2 * t + 1];
     ddp_jacobian(net, theta, w_th + (size_t)t * hidden, reinterpret_cast<f32x4 *>(delta),
-                 reinterpret_cast<f32x4 *>(delta) + kDdpMaxWidth, w_x + (size_t)7 * t, w_u + 2 * t, tx + (size_t)7 * t, tu + 2 * t, sn,
+                 reinterpret_cast<f32x4 *>(delta) + kWaveNetMaxWidth, w_x + (size_t)7 * t, w_u + 2 * t, tx + (size_t)7 * t, tu + 2 * t, sn,
                  cs, dt, A.Q, A.R, w_rec + (size_t)72 * t, lane);
   }
   __syncthreads();
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
   const int ri = lane >> 3, rj = lane & 7;
   const bool valid = ri < 7 && rj < 7;
   for (int q = lane; q < kRicEnd; q += 64) R_[q] = 0.0f;
-  ddp_wave_sync();
+  wave_tile_sync();
   float Vlast = 0.0f;
   {
     // boundary condition (target of the terminal cost = target_x[H-1])
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
     if (lane < 8) R_[kRicDl + 1 + lane] = r1;
   };
   put_record(rec0, rec1);
-  ddp_wave_sync();
+  wave_tile_sync();
   int status = 0;
   for (int k = H - 2; k >= 0; k--) {
     if (k > 0) {  // the next step's record, requested now
@@ -181,7 +179,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
         else R_[kRicQux + 8 * ri + 7] = R_[kRicDl + 7 + ri] * dt + sb;  // qu
       }
     }
-    ddp_wave_sync();
+    wave_tile_sync();
     // S2: qxx = (Phi^T Vxx) Phi, qux = (B^T Vxx) Phi (lanes of rows 0, 1), quu = (B^T Vxx) B (lanes of rows 2, 3, columns 0, 1)
     {
       const int br = ri & 1;
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
       if (ri < 2 && rj < 7) R_[kRicQux + 8 * ri + rj] = sb;
       if ((ri == 2 || ri == 3) && rj < 2) R_[kRicQuu + 2 * br + rj] = (br == rj) ? rdt + sb : sb;
     }
-    ddp_wave_sync();
+    wave_tile_sync();
     // S3: the pivoted 2 x 2 LDL^T (every lane), Lk's columns and lk (column 7) in the lanes of row 0
     {
       const DdpLdlt2 ldlt(R_[kRicQuu], R_[kRicQuu + 1], R_[kRicQuu + 2], R_[kRicQuu + 3]);
@@ -219,7 +217,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
         }
       }
     }
-    ddp_wave_sync();
+    wave_tile_sync();
     // S4: Vn = qxx + qux^T Lk; column 7: Vx = qx + (qux^T lk), whose sum has no leading zero in the host file
     {
       const float p0 = R_[kRicQux + ri] * R_[kRicLk + rj];
@@ -231,11 +229,11 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
         else R_[kRicVxx + 8 * ri + 7] = v;
       }
     }
-    ddp_wave_sync();
+    wave_tile_sync();
     // S5: Vxx = 0.5 (Vn + Vn^T); the next step's record
     if (valid) R_[kRicVxx + 8 * ri + rj] = 0.5f * (R_[kRicVn + 8 * ri + rj] + R_[kRicVn + 8 * rj + ri]);
     if (k > 0) put_record(rec0, rec1);
-    ddp_wave_sync();
+    wave_tile_sync();
   }
   if (status != 0) {
     if (lane == 0) {
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
     return;
   }
   __threadfence_block();  // the gains (global memory, written by lanes of row 0) are read by every lane below
-  ddp_wave_sync();
+  wave_tile_sync();
 
   // ---- D: forward pass with alpha = 1 (ddp.h:125-152) ----
   float *row = R_ + kRicRow;  // [x 7 | u 2 | feedback 14 | feedforward 2 | target_x 7 | target_u 2] of the step
@@ -265,7 +263,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
   float rv = (H >= 2) ? *row_addr(0) : 0.0f;
   for (int k = 0; k + 1 < H; k++) {
     if (lane < 34) row[lane] = rv;
-    ddp_wave_sync();
+    wave_tile_sync();
     if (k + 2 < H) rv = *row_addr(k + 1);  // the next step's row, requested now
     float r[36];
 #pragma unroll
@@ -273,7 +271,7 @@ __global__ __launch_bounds__(64 * kDdpFleetWaves) void ddp_fleet_kernel(const Dd
       const f32x4 v = *reinterpret_cast<const f32x4 *>(row + 4 * q);
       r[4 * q] = v[0]; r[4 * q + 1] = v[1]; r[4 * q + 2] = v[2]; r[4 * q + 3] = v[3];
     }
-    ddp_wave_sync();  // the row is the next step's from here
+    wave_tile_sync();  // the row is the next step's from here
     float dxs[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) dxs[i] = ox[i] - r[i];
@@ -336,7 +334,7 @@ __global__ __launch_bounds__(256) void device_tanhf_kernel(const float *__restri
 
 bool ddp_fleet_image_in_lds(const NetDesc &net)
 {
-  return sizeof(float) * ((size_t)kDdpFixedFloats + (size_t)net.num_params) <= kDdpLdsLimit;
+  return wave_net_image_in_lds(net, kDdpFixedFloats, kDdpLdsLimit);
 }
 
 hipError_t launch_ddp_fleet(const DdpFleetArgs *h_inst, const DdpFleetArgs *d_inst, int n, hipStream_t stream)
@@ -346,22 +344,13 @@ hipError_t launch_ddp_fleet(const DdpFleetArgs *h_inst, const DdpFleetArgs *d_in
   size_t lds = sizeof(float) * (size_t)kDdpFixedFloats;
   for (int i = 0; i < n; i++) {
     const NetDesc &net = h_inst[i].net;
-    if (net.n_layers < 2 || net.n_layers > MPPI_MAX_LAYERS || net.max_width > kDdpMaxWidth || h_inst[i].T < 2) return hipErrorInvalidValue;
+    if (!wave_net_valid(net) || h_inst[i].T < 2) return hipErrorInvalidValue;
     if (h_inst[i].img_lds) {
       if (!ddp_fleet_image_in_lds(net)) return hipErrorInvalidValue;
       lds = std::max(lds, sizeof(float) * ((size_t)kDdpFixedFloats + (size_t)net.num_params));
     }
   }
-  // the kernel's dynamic-LDS ceiling, once per device
-  static std::atomic<bool> raised[64];
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(ddp_fleet_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDdpLdsLimit);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-  }
+  if (hipError_t e = raise_lds_limit_once<ddp_fleet_kernel>(kDdpLdsLimit); e != hipSuccess) return e;
   hipLaunchKernelGGL(ddp_fleet_kernel, dim3(n), dim3(64 * kDdpFleetWaves), lds, stream, d_inst);
   return hipGetLastError();
 }

@@ -1,17 +1,14 @@
 // ddp_fleet_device.hpp -- device functions of ddp_fleet.hip: ddp_feedback.cpp's pass for the network model on one workgroup,
 // operation for operation.  Every sum is the host file's: k ascending from 0.0f with a SEPARATE multiply and add (the library is
 // compiled -ffp-contract=off: write no fmaf here), the host's association, IEEE division, tanhf_scalar for tanhf.
-// nominal_fleet.hip shares the forward layer (ddp_layer) with FMA = true: mppi_nominal_traj's arithmetic, where every multiply-add
-// of a neuron's sum is one fmaf (host_net.hpp).  FMA = false is the DDP pass's text, unchanged.
+// The network's forward pass is wave_net.hpp's per-wave forward with the DDP pass's neuron (WaveArithHostMulAdd);
+// nominal_fleet.hip takes ddp_sincos from here and runs the same forward with the host replay's neuron (WaveArithHostFma).
 #pragma once
 #include "mppi_kernels.hpp"
 #include "mppi_device.hpp"
-#include "tanhf_scalar.hpp"
+#include "wave_net.hpp"
 
 namespace mppi {
-
-constexpr int kDdpAhead = 8;       // k steps of weights in flight (the forward layer)
-constexpr int kDdpMaxWidth = 256;  // mppi_create's limit
 
 // cwiseMin(u_max).cwiseMax(u_min): ddp_feedback.cpp's clamp_minmax, the same operand order
 __device__ __forceinline__ float ddp_clamp_minmax(float v, float lo, float hi)
@@ -21,14 +18,6 @@ __device__ __forceinline__ float ddp_clamp_minmax(float v, float lo, float hi)
   return v;
 }
 
-// what one lane stored to the wave's tile is what every lane of the wave reads next
-__device__ __forceinline__ void ddp_wave_sync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // sinf / cosf of the heading: computed in double and rounded (glibc's sinf is not ported: DESIGN 4.20)
 __device__ __forceinline__ void ddp_sincos(float psi, float &sn, float &cs)
 {
@@ -36,75 +25,6 @@ __device__ __forceinline__ void ddp_sincos(float psi, float &sn, float &cs)
   sincos((double)psi, &s, &c);
   sn = (float)s;
   cs = (float)c;
-}
-
-// One layer of HostNet::forward for the wave: C chains per lane (neurons lane + 64 c), Wt the layer's k-major weights [nin][nout],
-// b its biases: s = 0, k ascending s = s + W[j][k] * a[k], then s + b[j], then tanhf on a hidden layer.  th: where a hidden layer's
-// tanh values are kept for the Jacobian (nullptr: not kept).  A lane past the layer's width walks the last neuron's weights and
-// stores nothing.  The skeleton (weights requested kDdpAhead k steps ahead, activations as broadcast reads) is rollout_trace.hip's.
-template <int C, bool FMA = false>
-__device__ __forceinline__ void ddp_layer(const float *Wt, const float *b, int nin, int nout, bool hidden, const float *cur,
-                                          float *nxt, float *th, int lane)
-{
-  int jj[C];
-  float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    jj[c] = min(lane + 64 * c, nout - 1);
-    acc[c] = 0.0f;
-  }
-  const int full = nin & ~(kDdpAhead - 1);
-  float w[kDdpAhead][C];
-  if (full > 0) {
-#pragma unroll
-    for (int u = 0; u < kDdpAhead; u++)
-#pragma unroll
-      for (int c = 0; c < C; c++) w[u][c] = Wt[u * nout + jj[c]];
-  }
-  for (int k0 = 0; k0 < full; k0 += kDdpAhead) {
-    float wc[kDdpAhead][C];
-#pragma unroll
-    for (int u = 0; u < kDdpAhead; u++)
-#pragma unroll
-      for (int c = 0; c < C; c++) wc[u][c] = w[u][c];
-    if (k0 + kDdpAhead < full) {  // the next chunk, requested before this one is multiplied
-      const float *Wn = Wt + (size_t)(k0 + kDdpAhead) * nout;
-#pragma unroll
-      for (int u = 0; u < kDdpAhead; u++)
-#pragma unroll
-        for (int c = 0; c < C; c++) w[u][c] = Wn[u * nout + jj[c]];
-    }
-    float x[kDdpAhead];
-#pragma unroll
-    for (int q = 0; q < kDdpAhead / 4; q++) {
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(cur + k0 + 4 * q);  // broadcast: every lane the same address
-      x[4 * q] = v[0]; x[4 * q + 1] = v[1]; x[4 * q + 2] = v[2]; x[4 * q + 3] = v[3];
-    }
-#pragma unroll
-    for (int u = 0; u < kDdpAhead; u++)
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        if constexpr (FMA) acc[c] = fmaf(wc[u][c], x[u], acc[c]);
-        else acc[c] = acc[c] + wc[u][c] * x[u];
-      }
-  }
-  for (int k = full; k < nin; k++) {  // the ragged end, one k at a time
-    const float x = cur[k];
-#pragma unroll
-    for (int c = 0; c < C; c++) {
-      if constexpr (FMA) acc[c] = fmaf(Wt[k * nout + jj[c]], x, acc[c]);
-      else acc[c] = acc[c] + Wt[k * nout + jj[c]] * x;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    float y = acc[c] + b[jj[c]];
-    if (hidden) y = tanhf_scalar(y);
-    if (lane + 64 * c < nout) {
-      nxt[lane + 64 * c] = y;
-      if (hidden && th) th[lane + 64 * c] = y;
-    }
-  }
 }
 
 // HostNet::f for the wave (all 64 lanes hold the same x, u, dx): computeKinematics + the network.  tile0 / tile1: the wave's two
@@ -121,31 +41,12 @@ __device__ __forceinline__ void ddp_f(const NetDesc &net, const float *img, floa
     const float hi = (lane == 3) ? x[6] : (lane == 4) ? u0 : u1;
     if (lane < kNetIn) tile0[lane] = (lane < 3) ? lo : hi;
   }
-  ddp_wave_sync();
-  float *cur = tile0, *nxt = tile1;
-  int off = 0, hoff = 0;
-  for (int l = 0; l + 1 < net.n_layers; l++) {
-    const int nin = net.layers[l], nout = net.layers[l + 1];
-    const float *Wt = img + off, *b = Wt + nin * nout;
-    const bool hidden = l + 2 < net.n_layers;
-    float *thl = (th && hidden) ? th + hoff : nullptr;
-    const int chains = (nout + 63) >> 6;
-    if (chains == 1) ddp_layer<1>(Wt, b, nin, nout, hidden, cur, nxt, thl, lane);
-    else if (chains == 2) ddp_layer<2>(Wt, b, nin, nout, hidden, cur, nxt, thl, lane);
-    else if (chains == 3) ddp_layer<3>(Wt, b, nin, nout, hidden, cur, nxt, thl, lane);
-    else ddp_layer<4>(Wt, b, nin, nout, hidden, cur, nxt, thl, lane);
-    ddp_wave_sync();
-    off += nin * nout + nout;
-    hoff += nout;
-    float *sw = cur; cur = nxt; nxt = sw;
-  }
-  const f32x4 d = *reinterpret_cast<const f32x4 *>(cur);
+  const f32x4 d = wave_net_forward<WaveArithHostMulAdd>(net, img, tile0, tile1, th, lane);
   dx[3] = d[0]; dx[4] = d[1]; dx[5] = d[2]; dx[6] = d[3];
-  ddp_wave_sync();  // the next step's inputs go to tile0, which may be the tile just read
 }
 
 // HostNet::jacobian_after_f of one step for the wave, scaled by dt and + I (ddp.h:71-80), and the step's cost derivatives:
-// rec[0..63) = df (7 x 9, row-major), rec[63..72) = dL.  d0 / d1: the wave's two delta tiles, [kDdpMaxWidth] float4 (the four
+// rec[0..63) = df (7 x 9, row-major), rec[63..72) = dL.  d0 / d1: the wave's two delta tiles, [kWaveNetMaxWidth] float4 (the four
 // outputs' chains of a neuron side by side); theta: the weights row-major (the reference's layout); th: the step's tanh values.
 __device__ __forceinline__ void ddp_jacobian(const NetDesc &net, const float *theta, const float *th, f32x4 *d0, f32x4 *d1,
                                              const float *x, const float *u, const float *tx, const float *tu, float sn, float cs,
@@ -157,7 +58,7 @@ __device__ __forceinline__ void ddp_jacobian(const NetDesc &net, const float *th
     e[lane] = 1.0f;
     d0[lane] = e;
   }
-  ddp_wave_sync();
+  wave_tile_sync();
   f32x4 *d = d0, *dn = d1;
   int off = net.num_params, hoff = 0;
   for (int l = 1; l + 2 < net.n_layers; l++) hoff += net.layers[l];  // hidden layers below the last one
@@ -187,7 +88,7 @@ __device__ __forceinline__ void ddp_jacobian(const NetDesc &net, const float *th
         dn[i0 + lane] = o;
       }
     }
-    ddp_wave_sync();
+    wave_tile_sync();
     f32x4 *sw = d; d = dn; dn = sw;
   }
   if (lane < 63) {
@@ -202,7 +103,7 @@ __device__ __forceinline__ void ddp_jacobian(const NetDesc &net, const float *th
     rec[lane] = v;
   }
   if (lane < 9) rec[63 + lane] = (lane < 7) ? Q[lane] * (x[lane] - tx[lane]) : R[lane - 7] * (u[lane - 7] - tu[lane - 7]);
-  ddp_wave_sync();  // the tiles are the next step's
+  wave_tile_sync();  // the tiles are the next step's
 }
 
 // x = A^{-1} b for the symmetric 2 x 2 A: ddp_feedback.cpp's Ldlt2 (Eigen::LDLT semantics: largest |diagonal| first)

@@ -3,6 +3,7 @@
 #include "mppi_device.hpp"
 
 #include <hip/hip_ext.h>
+#include <atomic>
 #include <type_traits>
 
 namespace mppi {
@@ -39,17 +40,18 @@ inline hipError_t dispatch_rollout_flags(bool affine, bool ctrl, bool gated, F &
   return dispatch_cost_flags(affine, ctrl, [&](auto af, auto ct) { return f(af, ct, std::false_type{}); });
 }
 
-// More dynamic LDS than the default limit for kernel instance KERN: set once per instance and device.
+// More dynamic LDS than the default limit for kernel instance KERN: set once per instance and device.  The flag is atomic: some
+// launchers are called from the host helper thread as well (abi_host.hip).
 template <auto KERN>
 inline hipError_t raise_lds_limit_once(size_t bytes)
 {
-  static bool attr_set[64] = {};
+  static std::atomic<bool> attr_set[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  if (!attr_set[dev]) {
+  if (!attr_set[dev].load(std::memory_order_acquire)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
-    attr_set[dev] = true;
+    attr_set[dev].store(true, std::memory_order_release);
   }
   return hipSuccess;
 }

@@ -3,7 +3,8 @@
 // theirs).  The kernel restates mppi_nominal_traj for the network model statement for statement (abi_host.hip, host_net.hpp):
 // record s, clamp u with the host's two branches, the kinematics as two fmaf, per neuron the k-ascending fmaf chain from 0 with
 // the bias added afterwards, tanhf_scalar on hidden layers, s = fmaf(sd, dt, s).  Only sinf / cosf of the heading differ: they
-// are the rounded double results (ddp_sincos), not glibc's floats.  The forward layer is ddp_fleet_device.hpp's with FMA = true.
+// are the rounded double results (ddp_sincos), not glibc's floats.  The network is wave_net.hpp's per-wave forward with the host
+// replay's neuron (WaveArithHostFma).
 //
 // The replay is one recurrence of T dependent steps: latency is the whole cost.  What is NOT on it:
 //   * the heading of step t + 1 is fmaf(-+s6[t], dt, psi[t]), known before step t's network runs, so its sin / cos are computed
@@ -16,8 +17,6 @@
 // s[t] from an LDS slot, records it (stores only: it never waits for memory), computes sin / cos of psi[t + 1] in double and
 // hands them over in an LDS slot -- one s_barrier per step, both slots double-buffered.  = 1: one wave does everything, the
 // sin / cos issued ahead of the network.  DESIGN 4.21 has the measurement and which one is kept.
-#include <atomic>
-
 #include "../../include/mppi_hip.h"
 #include "ddp_fleet_device.hpp"
 
@@ -28,7 +27,7 @@ namespace mppi {
 #endif
 constexpr int kNomWaves = MPPI_NOMINAL_FLEET_WAVES;
 static_assert(kNomWaves == 1 || kNomWaves == 2, "one wave, or the network wave and its rider");
-constexpr int kNomActFloats = 2 * kDdpMaxWidth;  // the network wave's two activation tiles
+constexpr int kNomActFloats = 2 * kWaveNetMaxWidth;  // the network wave's two activation tiles
 constexpr int kNomX = kNomActFloats;             // [2][8]: s[t] on its way to the rider (slot t & 1; float 7 is padding)
 constexpr int kNomSC = kNomX + 16;               // [2][4]: {sn, cs} of step t on its way to the network wave (slot t & 1; two floats of padding)
 constexpr int kNomFixedFloats = kNomSC + 8;
@@ -53,25 +52,8 @@ __device__ __forceinline__ void nom_net(const NetDesc &net, const float *img, fl
     tile0[4] = u0;
     tile0[5] = u1;
   }
-  ddp_wave_sync();
-  float *cur = tile0, *nxt = tile1;
-  int off = 0;
-  for (int l = 0; l + 1 < net.n_layers; l++) {
-    const int nin = net.layers[l], nout = net.layers[l + 1];
-    const float *Wt = img + off, *b = Wt + nin * nout;
-    const bool hidden = l + 2 < net.n_layers;
-    const int chains = (nout + 63) >> 6;
-    if (chains == 1) ddp_layer<1, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
-    else if (chains == 2) ddp_layer<2, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
-    else if (chains == 3) ddp_layer<3, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
-    else ddp_layer<4, true>(Wt, b, nin, nout, hidden, cur, nxt, nullptr, lane);
-    ddp_wave_sync();
-    off += nin * nout + nout;
-    float *sw = cur; cur = nxt; nxt = sw;
-  }
-  const f32x4 d = *reinterpret_cast<const f32x4 *>(cur);
+  const f32x4 d = wave_net_forward<WaveArithHostFma>(net, img, tile0, tile1, nullptr, lane);
   o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
-  ddp_wave_sync();  // the next step's inputs go to tile0, which may be the tile just read
 }
 
 // mppi_nominal_traj's update of one step: the kinematics, the network, the Euler step
@@ -100,7 +82,7 @@ __device__ __forceinline__ void nom_single_wave(const NominalFleetArgs &A, const
   const float ulo0 = A.u_lo[0], ulo1 = A.u_lo[1], uhi0 = A.u_hi[0], uhi1 = A.u_hi[1];
   const float *U = in + 7;
   float *o_x = out;
-  float *tile0 = lds, *tile1 = lds + kDdpMaxWidth;
+  float *tile0 = lds, *tile1 = lds + kWaveNetMaxWidth;
   float s[7];
 #pragma unroll
   for (int i = 0; i < 7; i++) s[i] = in[i];
@@ -136,7 +118,7 @@ __device__ __forceinline__ void nom_network_wave(const NominalFleetArgs &A, cons
   const float dt = A.dt;
   const float ulo0 = A.u_lo[0], ulo1 = A.u_lo[1], uhi0 = A.u_hi[0], uhi1 = A.u_hi[1];
   const float *U = in + 7;
-  float *tile0 = lds, *tile1 = lds + kDdpMaxWidth, *hx = lds + kNomX;
+  float *tile0 = lds, *tile1 = lds + kWaveNetMaxWidth, *hx = lds + kNomX;
   const float *hsc = lds + kNomSC;
   float s[7];
 #pragma unroll
@@ -194,7 +176,7 @@ __global__ __launch_bounds__(64 * kNomWaves) void nominal_fleet_kernel(const Nom
   const bool img_lds = A.img_lds != 0;
   if (img_lds) {
     const int np = A.net.num_params;
-    for (int i = threadIdx.x; i < np; i += 64 * kNomWaves) nom_lds[kNomFixedFloats + i] = wimg[i];
+    wave_net_stage_image(nom_lds + kNomFixedFloats, wimg, np, 64 * kNomWaves);
   }
   {  // control_seq: every control clamped, by the whole workgroup
     const int T = A.T;
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(64 * kNomWaves) void nominal_fleet_kernel(const Nom
 
 bool nominal_fleet_image_in_lds(const NetDesc &net)
 {
-  return sizeof(float) * ((size_t)kNomFixedFloats + (size_t)net.num_params) <= kNomLdsLimit;
+  return wave_net_image_in_lds(net, kNomFixedFloats, kNomLdsLimit);
 }
 
 hipError_t launch_nominal_fleet(const NominalFleetArgs *h_inst, const NominalFleetArgs *d_inst, int n, hipStream_t stream)
@@ -238,22 +220,13 @@ hipError_t launch_nominal_fleet(const NominalFleetArgs *h_inst, const NominalFle
   size_t lds = sizeof(float) * (size_t)kNomFixedFloats;
   for (int i = 0; i < n; i++) {
     const NetDesc &net = h_inst[i].net;
-    if (net.n_layers < 2 || net.n_layers > MPPI_MAX_LAYERS || net.max_width > kDdpMaxWidth || h_inst[i].T < 2) return hipErrorInvalidValue;
+    if (!wave_net_valid(net) || h_inst[i].T < 2) return hipErrorInvalidValue;
     if (h_inst[i].img_lds) {
       if (!nominal_fleet_image_in_lds(net)) return hipErrorInvalidValue;
       lds = std::max(lds, sizeof(float) * ((size_t)kNomFixedFloats + (size_t)net.num_params));
     }
   }
-  // the kernel's dynamic-LDS ceiling, once per device
-  static std::atomic<bool> raised[64];
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(nominal_fleet_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNomLdsLimit);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-  }
+  if (hipError_t e = raise_lds_limit_once<nominal_fleet_kernel>(kNomLdsLimit); e != hipSuccess) return e;
   hipLaunchKernelGGL(nominal_fleet_kernel, dim3(n), dim3(64 * kNomWaves), lds, stream, d_inst);
   return hipGetLastError();
 }

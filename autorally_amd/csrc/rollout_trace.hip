@@ -2,15 +2,13 @@
 // before every update, the clamped controls, every step's cost, the running mean and the step whose cost first saw the crash
 // flag (mppi_trace_rollouts).  A handful of rollouts, so a latency kernel, not a throughput one:
 //
-//   network model: ONE WAVEFRONT PER ROLLOUT, one lane per neuron.  Lane j owns neurons j, j + 64, j + 128 and j + 192 of a layer
-//   (one accumulation chain up to width 64, four at width 256); every neuron keeps the chain of nn_forward_valu
-//   (rollout_valu.hip): tmp = 0, k ascending tmp = fmaf(W[j][k], act[k], tmp), then tanh_bias(tmp, b[j] * kTanhScale) on a
-//   hidden layer and tmp + b[j] on the output layer -- the reference's order, so the costs are those of every order-exact
-//   rollout form bit for bit.  Activations go from layer to layer through the wave's own LDS tile and come back as broadcast
-//   reads, four k per ds_read_b128.  Weights come from a k-major image (pack_trace_weights: every W transposed, so that the 64
-//   lanes read 256 contiguous bytes per k): from LDS where image and tiles fit kTraceLdsLimit, else from global memory; either
-//   way kTraceAhead k steps are requested while the chunk before them is multiplied.  Any layer list mppi_create accepts
-//   (widths up to 256, MPPI_MAX_LAYERS entries, 6-4 without a hidden layer) is a kernel argument, not a template.
+//   network model: ONE WAVEFRONT PER ROLLOUT, one lane per neuron: the per-wave forward of wave_net.hpp with the rollout
+//   kernels' neuron (WaveArithRollout), which keeps the chain of nn_forward_valu (rollout_valu.hip): tmp = 0, k ascending
+//   tmp = fmaf(W[j][k], act[k], tmp), then tanh_bias(tmp, b[j] * kTanhScale) on a hidden layer and tmp + b[j] on the output
+//   layer -- the reference's order, so the costs are those of every order-exact rollout form bit for bit.  The k-major image
+//   (pack_trace_weights) is read from LDS where image and tiles fit kTraceLdsLimit, else from global memory.  Any layer list
+//   mppi_create accepts (widths up to 256, MPPI_MAX_LAYERS entries, 6-4 without a hidden layer) is a kernel argument, not a
+//   template.
 //   The rest of the step is computed by all 64 lanes alike, with the device functions and in the order of rollout_valu_kernel.
 //   kTraceWaves rollouts share a workgroup and its image.
 //
@@ -19,18 +17,14 @@
 // The controls are the solve's applied controls [T][K] (what the rollout kernels leave in place of the noise); the control
 // cost is NOT computed (du = eps nu cannot be had back from them bit for bit): the ABI refuses the cost outputs where a control
 // cost is on, and cost_finish<false> is the term's exact +0 everywhere else.
-#include <atomic>
-
 #include "../../include/mppi_hip.h"
 #include "bf_device.hpp"
-#include "mppi_kernels.hpp"
+#include "wave_net.hpp"
 
 namespace mppi {
 
 constexpr int kTraceWaves = 4;          // rollouts (wavefronts) per workgroup of the network kernel
-constexpr int kTraceMaxWidth = 256;     // mppi_create's limit
-constexpr int kTraceAhead = 8;          // k steps of weights in flight
-constexpr int kTraceTileFloats = 2 * kTraceMaxWidth;                   // a wave's two activation tiles
+constexpr int kTraceTileFloats = 2 * kWaveNetMaxWidth;                 // a wave's two activation tiles
 constexpr size_t kTraceLdsLimit = 64 * 1024;                           // tiles + image: beside a gated latency launch on the same CU
 constexpr size_t kTraceTilesBytes = sizeof(float) * kTraceWaves * kTraceTileFloats;
 
@@ -99,87 +93,20 @@ __device__ __forceinline__ void trace_end(const TraceArgs &a, const TraceRun &r,
   if (a.first_crash) a.first_crash[slot] = r.first;
 }
 
-// One layer for the wave: C chains per lane (neurons lane + 64 c), Wt the layer's k-major weights [nin][nout], b its biases.
-// A lane past the layer's width walks the last neuron's weights and stores nothing.
-template <int C>
-__device__ __forceinline__ void trace_layer(const float *Wt, const float *b, int nin, int nout, bool hidden, const float *cur,
-                                            float *nxt, int lane)
-{
-  int jj[C];
-  float acc[C];
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    jj[c] = min(lane + 64 * c, nout - 1);
-    acc[c] = 0.0f;
-  }
-  const int full = nin & ~(kTraceAhead - 1);
-  float w[kTraceAhead][C];
-  if (full > 0) {
-#pragma unroll
-    for (int u = 0; u < kTraceAhead; u++)
-#pragma unroll
-      for (int c = 0; c < C; c++) w[u][c] = Wt[u * nout + jj[c]];
-  }
-  for (int k0 = 0; k0 < full; k0 += kTraceAhead) {
-    float wc[kTraceAhead][C];
-#pragma unroll
-    for (int u = 0; u < kTraceAhead; u++)
-#pragma unroll
-      for (int c = 0; c < C; c++) wc[u][c] = w[u][c];
-    if (k0 + kTraceAhead < full) {  // the next chunk, requested before this one is multiplied
-      const float *Wn = Wt + (size_t)(k0 + kTraceAhead) * nout;
-#pragma unroll
-      for (int u = 0; u < kTraceAhead; u++)
-#pragma unroll
-        for (int c = 0; c < C; c++) w[u][c] = Wn[u * nout + jj[c]];
-    }
-    float x[kTraceAhead];
-#pragma unroll
-    for (int q = 0; q < kTraceAhead / 4; q++) {
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(cur + k0 + 4 * q);  // broadcast: every lane the same address
-      x[4 * q] = v[0]; x[4 * q + 1] = v[1]; x[4 * q + 2] = v[2]; x[4 * q + 3] = v[3];
-    }
-#pragma unroll
-    for (int u = 0; u < kTraceAhead; u++)
-#pragma unroll
-      for (int c = 0; c < C; c++) acc[c] = fmaf(wc[u][c], x[u], acc[c]);
-  }
-  for (int k = full; k < nin; k++) {  // the ragged end, one k at a time (no padded multiply-add: the chain is the reference's)
-    const float x = cur[k];
-#pragma unroll
-    for (int c = 0; c < C; c++) acc[c] = fmaf(Wt[k * nout + jj[c]], x, acc[c]);
-  }
-#pragma unroll
-  for (int c = 0; c < C; c++) {
-    const float bj = b[jj[c]];
-    const float y = hidden ? tanh_bias(acc[c], bj * kTanhScale) : acc[c] + bj;
-    if (lane + 64 * c < nout) nxt[lane + 64 * c] = y;
-  }
-}
-
-// what one lane stored to the wave's tile is what every lane of the wave reads next
-__device__ __forceinline__ void trace_tile_sync()
-{
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <bool LDS_IMG>
 __global__ __launch_bounds__(64 * kTraceWaves) void rollout_trace_kernel(const TraceArgs a, const NetDesc net)
 {
   extern __shared__ __attribute__((aligned(16))) float trace_lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (LDS_IMG) {
-    float *img_s = trace_lds + kTraceWaves * kTraceTileFloats;
-    for (int i = threadIdx.x; i < net.num_params; i += 64 * kTraceWaves) img_s[i] = a.wimg[i];
+    wave_net_stage_image(trace_lds + kTraceWaves * kTraceTileFloats, a.wimg, net.num_params, 64 * kTraceWaves);
     __syncthreads();
   }
   const int slot = blockIdx.x * kTraceWaves + wave;
   if (slot >= a.n) return;  // whole waves, behind the group's only barrier
   const float *img = LDS_IMG ? trace_lds + kTraceWaves * kTraceTileFloats : a.wimg;
   float *tile0 = trace_lds + wave * kTraceTileFloats;
-  float *tile1 = tile0 + kTraceMaxWidth;
+  float *tile1 = tile0 + kWaveNetMaxWidth;
   const int k = a.ks[slot];
 
   TraceRun r;
@@ -196,25 +123,8 @@ __global__ __launch_bounds__(64 * kTraceWaves) void rollout_trace_kernel(const T
       const float hi = (lane == 3) ? r.s[6] : (lane == 4) ? u0 : u1;
       if (lane < kNetIn) tile0[lane] = (lane < 3) ? lo : hi;
     }
-    trace_tile_sync();
-    float *cur = tile0, *nxt = tile1;
-    int off = 0;
-    for (int l = 0; l + 1 < net.n_layers; l++) {
-      const int nin = net.layers[l], nout = net.layers[l + 1];
-      const float *Wt = img + off, *b = Wt + nin * nout;
-      const bool hidden = l + 2 < net.n_layers;
-      const int chains = (nout + 63) >> 6;
-      if (chains == 1) trace_layer<1>(Wt, b, nin, nout, hidden, cur, nxt, lane);
-      else if (chains == 2) trace_layer<2>(Wt, b, nin, nout, hidden, cur, nxt, lane);
-      else if (chains == 3) trace_layer<3>(Wt, b, nin, nout, hidden, cur, nxt, lane);
-      else trace_layer<4>(Wt, b, nin, nout, hidden, cur, nxt, lane);
-      trace_tile_sync();
-      off += nin * nout + nout;
-      float *sw = cur; cur = nxt; nxt = sw;
-    }
-    const f32x4 d = *reinterpret_cast<const f32x4 *>(cur);
+    const f32x4 d = wave_net_forward<WaveArithRollout>(net, img, tile0, tile1, nullptr, lane);
     sd[3] = d[0]; sd[4] = d[1]; sd[5] = d[2]; sd[6] = d[3];
-    trace_tile_sync();  // the next step's inputs go to tile0, which may be the tile just read
     trace_tail(a, r, slot, t, u0, u1, tf, tb, sd, lane == 0);
   }
   if (lane == 0) trace_end(a, r, slot);
@@ -245,26 +155,16 @@ __global__ __launch_bounds__(kBfLanes) void rollout_trace_bf_kernel(const TraceA
 
 bool trace_image_in_lds(const NetDesc &net)
 {
-  return kTraceTilesBytes + sizeof(float) * (size_t)net.num_params <= kTraceLdsLimit;
+  return wave_net_image_in_lds(net, (size_t)kTraceWaves * kTraceTileFloats, kTraceLdsLimit);
 }
 
 hipError_t launch_rollout_trace(const NetDesc &net, const TraceArgs &a, hipStream_t stream)
 {
   if (a.n <= 0) return hipSuccess;
-  if (net.n_layers < 2 || net.n_layers > MPPI_MAX_LAYERS || net.max_width > kTraceMaxWidth) return hipErrorInvalidValue;
+  if (!wave_net_valid(net)) return hipErrorInvalidValue;
   const dim3 grid((a.n + kTraceWaves - 1) / kTraceWaves), block(64 * kTraceWaves);
   if (trace_image_in_lds(net)) {
-    // the kernel's dynamic-LDS ceiling, once per device
-    static std::atomic<bool> raised[64];
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_acquire)) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(rollout_trace_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTraceLdsLimit);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_release);
-    }
+    if (hipError_t e = raise_lds_limit_once<rollout_trace_kernel<true>>(kTraceLdsLimit); e != hipSuccess) return e;
     const size_t lds = kTraceTilesBytes + sizeof(float) * (size_t)net.num_params;
     hipLaunchKernelGGL(rollout_trace_kernel<true>, grid, block, lds, stream, a, net);
   } else {
