@@ -219,7 +219,10 @@ struct mppi_handle {
   int rng_cur = 0;
   int noise_L = 1, noise_C = 1;
   float *h_in = nullptr, *h_res = nullptr;
-  int explicit_iters = 0;  // >0: d_noise holds that many explicit iterations for the next solve
+  // >0: d_noise holds that many explicit iterations for the next solve.  Only ever 0 or cfg.num_iters: mppi_set_noise accepts
+  // exactly num_iters iterations and is its one writer of a non-zero value, every solve resets it, and cfg.num_iters is fixed at
+  // mppi_create (a batch shares one num_iters besides) -- so no solve checks that the count fits its iterations.
+  int explicit_iters = 0;
   bool pending = false;       // a solve is enqueued, results not yet collected
   bool pending_timed = false;
   bool pending_armed = false;  // the pending solve is one that was armed (mppi_arm): wait_pending checks its rows too

@@ -1,5 +1,8 @@
-// abi_solve.hip -- one MPPI solve (PI/mppi_controller.cu:600-671) as launches on the handle's stream: noise source, rollout
-// kernel, tail kernel, polling of the host-mapped result block; batched solves of several handles; result getters.
+// abi_solve.hip -- one MPPI solve (PI/mppi_controller.cu:600-671) as launches on a stream: noise source, rollout kernel, tail
+// kernel, polling of the host-mapped result block; result getters.  "Enqueue a solve for n >= 1 handles" is written once, as
+// phases (collect, begin_solves, distrust, solve_step, finish_solves: "the phases of a solve" below); three short drivers say
+// how the argument blocks the phases fill reach the device -- enqueue_solve (one handle, its own stream), enqueue_pair (2-4
+// handles, one rollout launch), enqueue_fleet (2-64 handles of a fleet form, three launches).
 #include "abi_internal.hpp"
 
 using namespace mppi;
@@ -344,10 +347,32 @@ int upload_controls_if_dirty(mppi_handle *h, hipStream_t stream)
   return MPPI_OK;
 }
 
+// -DMPPI_HOSTPROF (a diagnostic build: tools/build_variant.sh): where the host's microseconds of a solve go, averaged per call
+// and printed to stderr every 1000 calls of a driver.  HP_CLOCK(t) starts a clock, HP(stage, t) adds the time since t (or since
+// the last HP on t) to a stage, HP_CALL(first) counts a call of the driver whose stages begin at `first` and prints them.  The
+// default build contains none of it.
 #ifdef MPPI_HOSTPROF
-static double hp_acc[8] = {0}, hp_n = 0;
-static std::chrono::steady_clock::time_point hp_seen;
-#define HP(i, t0) hp_acc[i] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - (t0)).count()
+enum HpStage { kHpEntry, kHpRollout, kHpTail, kHpSmoothed,                           // enqueue_solve per iteration; wait_pending
+               kHpDecide, kHpStream, kHpWait, kHpArgs, kHpPairRollout, kHpPairTail,  // a batch that shares one rollout launch
+               kHpStages };
+static const char *const hp_name[kHpStages] = {"entry->launch", "rollout launch", "tail launch", "poll->smoothed", "decide",
+                                               "device + stream", "wait_pending", "upload+args", "rollout launch", "tail launch"};
+static double hp_acc[kHpStages] = {0};
+static long hp_calls[kHpStages] = {0};  // [first stage of a driver]
+#define HP_CLOCK(t) auto t = std::chrono::steady_clock::now()
+#define HP(stage, t) do { const auto n__ = std::chrono::steady_clock::now(); hp_acc[stage] += std::chrono::duration<double, std::micro>(n__ - (t)).count(); (t) = n__; } while (0)
+#define HP_CALL(first) do { if (++hp_calls[first] % 1000 == 0) hp_print(first); } while (0)
+static void hp_print(int first)
+{
+  // (the first batched call creates the device's batch stream, ~3 ms: read the averages over many calls with that in mind)
+  fprintf(stderr, "hostprof %s (us per call, %ld calls):", first == kHpDecide ? "batch" : "solve", hp_calls[first]);
+  for (int i = first; i < (first == kHpDecide ? kHpStages : kHpDecide); i++) fprintf(stderr, " %s %.2f |", hp_name[i], hp_acc[i] / hp_calls[first]);
+  fprintf(stderr, "\n");
+}
+#else
+#define HP_CLOCK(t) do { } while (0)
+#define HP(stage, t) do { } while (0)
+#define HP_CALL(first) do { } while (0)
 #endif
 
 // savitskyGolay (mppi_controller.cu:468-499) on the host, the same operations in the same order as the tail
@@ -438,9 +463,7 @@ int wait_pending(mppi_handle *h)
       }
     }
   }
-#ifdef MPPI_HOSTPROF
-  hp_seen = std::chrono::steady_clock::now();
-#endif
+  HP_CLOCK(hp_t);
   h->pending = false;
   h->no_result = false;
   h->baseline = h->h_res[4 * h->T + 0];
@@ -467,9 +490,7 @@ int wait_pending(mppi_handle *h)
                                          : "solve produced non-finite controls (device hand-over failed)");
   }
   savgol_host(h, h->h_res, 4, 2);  // rows [u0, seq, u1, seq] of the result block
-#ifdef MPPI_HOSTPROF
-  HP(4, hp_seen);
-#endif
+  HP(kHpSmoothed, hp_t);
   if (h->pending_timed) {
     h->pending_timed = false;
     for (size_t it = 0; it < h->ev.size(); it++) {
@@ -524,21 +545,137 @@ TailLaunch tail_launch(const mppi_handle *h, const float *V, bool last)
   return l;
 }
 
+// ---- the phases of a solve -------------------------------------------------------------------------------------------------
+// "Enqueue a solve for the handles hs[0 .. n) on stream S" in the order every driver below runs it: collect; begin_solves; per
+// iteration solve_step for every handle, then the driver's own launches; finish_solves.  A batched driver answers every failure
+// after begin_solves with distrust.  n = 1 drivers pass one stack RolloutArgs / TailLaunch; only the fleet driver owns arrays.
+
+// Whatever can fail without moving a handle fails here: every handle's timed-out solve has drained, its pending solve is
+// collected.  (Nothing is checked about explicit noise: see explicit_iters, abi_internal.hpp.)
+static int collect(mppi_handle *const *hs, int n)
+{
+  for (int i = 0; i < n; i++) {
+    int rc = recover_timed_out(hs[i]);
+    if (rc == MPPI_OK) rc = wait_pending(hs[i]);  // finish a previous asynchronous solve first
+    if (rc) return rc;
+  }
+  return MPPI_OK;
+}
+
+// From here on handles change (sequence numbers, generator buffers, the slid copy's validity).  batched: S is the device's batch
+// stream, and a handle's work on its own streams finishes first.
+static int begin_solves(mppi_handle *const *hs, int n, hipStream_t S, bool batched)
+{
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    int rc = batched ? hand_over(h, S) : MPPI_OK;
+    if (rc == MPPI_OK) rc = upload_controls_if_dirty(h, S);
+    if (rc) return rc;
+    h->seq = next_seq(h);
+    forget_solve_state(h);
+  }
+  return MPPI_OK;
+}
+
+// A failure between begin_solves and finish_solves of a batched solve leaves every handle of the batch in the state "nothing on
+// the device can be trusted": the host copies of U / hist are uploaded again by the next solve, no slid copy is offered to
+// mppi_slide_control_seq, nothing is pending.
+static int distrust(mppi_handle *const *hs, int n, int rc)
+{
+  for (int i = 0; i < n; i++) {
+    hs[i]->slid_valid = false;
+    hs[i]->u_dirty = true;
+    hs[i]->pending = false;
+  }
+  return rc;
+}
+
+// Where the eps of an iteration come from.  The explicit buffer (mppi_set_noise) goes first on every path; without one
+//   Single: draws already prefetched > the rollout kernel's own noise wavefront > the generator kernel, now (acquire_noise);
+//   Pair:   the rollout kernel's own noise wavefront (every batched kernel has one; batch_together admits no prefetched draws);
+//   Fleet:  the fleet's one generator launch, from the descriptor filled here -- the handle's generator stream and buffers move
+//           exactly as acquire_noise moves them for its own solve.
+enum class Eps { Single, Pair, Fleet };
+
+// *buf: iteration it's eps, which the rollout overwrites with the applied controls (v_buf).  *in_kernel: the caller's rollout
+// arguments take use_inline_noise once they are filled.  nd (Fleet only): the handle's generator descriptor; draws nothing
+// where the noise is explicit.
+static int eps_source(mppi_handle *h, Eps src, int it, float **buf, bool *in_kernel, NoiseFleetDesc *nd)
+{
+  *in_kernel = false;
+  if (src == Eps::Fleet) *nd = NoiseFleetDesc{};
+  if (h->explicit_iters > 0) {
+    *buf = h->d_noise + (size_t)it * ((size_t)h->K * h->T * 2);
+  } else if (src == Eps::Fleet) {
+    h->gen_cur = 1 - h->gen_cur;
+    *buf = h->d_gen[h->gen_cur];
+    *nd = NoiseFleetDesc{h->d_rng[h->rng_cur], h->d_rng[1 - h->rng_cur], h->d_jump, *buf, h->K, h->T, h->noise_L, h->noise_C};
+    h->rng_cur = 1 - h->rng_cur;
+  } else if (src == Eps::Pair || (!h->prefetch_valid && has_noise_wave(h))) {
+    *in_kernel = true;
+    *buf = h->d_gen[h->gen_cur];
+  } else if (int rc = acquire_noise(h, buf)) {
+    return rc;
+  }
+  h->v_buf = *buf;
+  return MPPI_OK;
+}
+
+// One handle's share of iteration `it`: its eps, and the rollout and tail arguments of the launches the driver makes on S.
+// (The tail's epoch advances on every path; only the streaming tail, K > 4096, reads it, and a batch never runs that tail.)
+static int solve_step(mppi_handle *h, const float *state, int it, bool last, hipStream_t S, Eps src, RolloutArgs &a, TailLaunch &l,
+                      NoiseFleetDesc *nd)
+{
+  float *noise = nullptr;
+  bool in_kernel = false;
+  int rc = eps_source(h, src, it, &noise, &in_kernel, nd);
+  if (rc) return rc;
+  fill_rollout_args(h, state, noise, a);
+  rc = tag_min_cost(h, a, S);
+  if (rc) return rc;
+  if (in_kernel) use_inline_noise(h, a);
+  next_tail_epoch(h);
+  l = tail_launch(h, noise, last);
+  return MPPI_OK;
+}
+
+// Every launch of the solve is on its stream.  (The slid copy the last tail leaves becomes valid here, not in solve_step: a
+// solve whose launches failed offers none.)
+static void finish_solves(mppi_handle *const *hs, const float *states, int n, bool timed)
+{
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    h->explicit_iters = 0;
+    h->slid_valid = wants_slid_copy(h);
+    h->pending = true;
+    note_solve_state(h, states + (size_t)MPPI_STATE_DIM * i, true);
+    h->pending_timed = timed;
+  }
+}
+
+// current device, then the batch stream of h0's device (looked up once per handle)
+static int use_batch_stream(mppi_handle *h0, hipStream_t *S)
+{
+  HIPCHK(h0, ensure_device(h0->cfg.device));
+  if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
+  *S = h0->batch_s;
+  return *S ? MPPI_OK : fail(h0, MPPI_ERR_HIP, "no batch stream");
+}
+
 static bool arm_usable(const mppi_handle *h);
 static int open_armed(mppi_handle *h, const float *state);
 
+// One handle on its own stream: launch_rollout + launch_solve_tail per iteration, with the stage events, the capture copies and
+// the prefetch of the next solve's draws behind the rollout.
 int enqueue_solve(mppi_handle *h, const float *state)
 {
-#ifdef MPPI_HOSTPROF
-  const auto hp_t0 = std::chrono::steady_clock::now();
-  if (hp_n > 0) hp_acc[0] += std::chrono::duration<double, std::micro>(hp_t0 - hp_seen).count();  // seen -> next enqueue entered
-#endif
+  HP_CLOCK(hp_t);
   int rc = check_ready(h);
   if (rc) return rc;
   if (!state) return fail(h, MPPI_ERR_INVALID, "state is NULL");
-  rc = recover_timed_out(h);
+  rc = recover_timed_out(h);  // (an armed solve of a handle that has not drained is left alone)
   if (rc) return rc;
-  rc = wait_pending(h);  // finish a previous asynchronous solve first
+  rc = collect(&h, 1);
   if (h->armed) {
     // armed (mppi_arm): this call opens the gate of the solve already enqueued -- unless the previous solve failed, the armed
     // solve belongs to a batch, or its deadline has passed: then it is called off and this solve runs as if it never was
@@ -548,56 +685,30 @@ int enqueue_solve(mppi_handle *h, const float *state)
   }
   if (rc) return rc;
   const int K = h->K, T = h->T, iters = h->cfg.num_iters;
-  if (h->explicit_iters > 0 && h->explicit_iters != iters)
-    return fail(h, MPPI_ERR_STATE, "explicit noise holds a different number of iterations");
   OWN(h);
-  rc = upload_controls_if_dirty(h, h->stream);
+  rc = begin_solves(&h, 1, h->stream, false);
   if (rc) return rc;
   const bool timed = h->timing && (h->timing_count++ % (unsigned)h->timing_every) == 0;
   const bool explicit_noise = h->explicit_iters > 0;
-  const size_t slot_sz = (size_t)K * T * 2;
-  h->seq = next_seq(h);
-  forget_solve_state(h);
   for (int it = 0; it < iters; it++) {
     Events *ev = timed ? &h->ev[it] : nullptr;
     if (ev) HIPCHK(h, hipEventRecord(ev->e[0], h->stream));
-    // source of eps: the explicit buffer (mppi_set_noise) > draws already prefetched > the rollout kernel's own
-    // noise wavefront > the generator kernel, now
-    const bool inline_noise = !explicit_noise && !h->prefetch_valid && has_noise_wave(h);
-    float *noise = h->d_noise + (size_t)(explicit_noise ? it : 0) * slot_sz;
-    if (!explicit_noise && !inline_noise) {
-      rc = acquire_noise(h, &noise);
-      if (rc) return rc;
-    } else if (inline_noise) {
-      noise = h->d_gen[h->gen_cur];  // receives the applied controls
-    }
-    h->v_buf = noise;
-    if (ev) HIPCHK(h, hipEventRecord(ev->e[1], h->stream));
+    const bool last = (it == iters - 1);
     RolloutArgs a;
-    fill_rollout_args(h, state, noise, a);
-    rc = tag_min_cost(h, a, h->stream);
+    TailLaunch l;
+    rc = solve_step(h, state, it, last, h->stream, Eps::Single, a, l, nullptr);
     if (rc) return rc;
-    if (inline_noise) use_inline_noise(h, a);
-#ifdef MPPI_HOSTPROF
-    HP(1, hp_t0);  // entry -> before the rollout launch
-    const auto hp_t1 = std::chrono::steady_clock::now();
-#endif
+    if (ev) HIPCHK(h, hipEventRecord(ev->e[1], h->stream));  // behind the generator, where this iteration waited for one
+    HP(kHpEntry, hp_t);  // entry -> before the rollout launch
     if (ev) { tl_kernel_start = ev->e[4]; tl_kernel_stop = ev->e[5]; }
     rc = launch_rollout(h, a);
     tl_kernel_start = tl_kernel_stop = nullptr;
     if (rc) return rc;
-#ifdef MPPI_HOSTPROF
-    HP(2, hp_t1);  // the rollout launch call
-    const auto hp_t2 = std::chrono::steady_clock::now();
-#endif
+    HP(kHpRollout, hp_t);  // the rollout launch call
     const bool prefetch = h->gen_async && iters == 1 && !explicit_noise && !has_noise_wave(h) && !h->prefetch_valid;
     if (prefetch) HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));  // the generator starts when this rollout ends
     if (ev) HIPCHK(h, hipEventRecord(ev->e[2], h->stream));
-    const bool last = (it == iters - 1);
-    const bool want_slid = last && wants_slid_copy(h);
-    next_tail_epoch(h);
-    HIPCHK(h, launch_solve_tail(tail_launch(h, noise, last), h->stream));
-    if (last) h->slid_valid = want_slid;
+    HIPCHK(h, launch_solve_tail(l, h->stream));
     if (h->capture) {  // test hook: what this iteration left (the last iteration's raw U is in the result block)
       float *c = h->d_cap + (size_t)it * (2 * (size_t)T + K);
       if (!last) HIPCHK(h, hipMemcpyAsync(c, h->d_in, sizeof(float) * 2 * (size_t)T, hipMemcpyDeviceToDevice, h->stream));
@@ -609,19 +720,11 @@ int enqueue_solve(mppi_handle *h, const float *state)
       h->gen_time_now = false;
       if (rc) return rc;
     }
-#ifdef MPPI_HOSTPROF
-    HP(3, hp_t2);  // the tail launch call
-    hp_n += 1;
-    if ((long)hp_n % 2000 == 0)
-      fprintf(stderr, "hostprof n=%.0f: seen->enqueue %.2f us, entry->launch %.2f, rollout launch %.2f, tail launch %.2f, poll->smoothed %.2f\n",
-              hp_n, hp_acc[0] / hp_n, hp_acc[1] / hp_n, hp_acc[2] / hp_n, hp_acc[3] / hp_n, hp_acc[4] / hp_n);
-#endif
+    HP(kHpTail, hp_t);  // the tail launch call
+    HP_CALL(kHpEntry);
     if (ev) HIPCHK(h, hipEventRecord(ev->e[3], h->stream));
   }
-  h->explicit_iters = 0;
-  h->pending = true;
-  note_solve_state(h, state, true);
-  h->pending_timed = timed;
+  finish_solves(&h, state, 1, timed);
   h->cap_valid = h->capture;
   h->cap_explicit = explicit_noise;
   return MPPI_OK;
@@ -896,10 +999,8 @@ static int arm_together(mppi_handle *const *hs, int n, double max_wait_s)
     return fail(h0, MPPI_ERR_UNSUPPORTED, "the batched launch of this form has no gated form");
   for (int i = 0; i < n; i++)
     if (arm_kind(hs[i]) != 1) return fail(hs[i], MPPI_ERR_UNSUPPORTED, "this handle's configuration has no gated form (mppi_arm_batch)");
-  HIPCHK(h0, ensure_device(h0->cfg.device));
-  if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
-  const hipStream_t S = h0->batch_s;
-  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+  hipStream_t S = nullptr;
+  if (int rc = use_batch_stream(h0, &S)) return rc;
   for (int i = 0; i < n; i++)
     if (int rc = hand_over(hs[i], S)) return rc;
   QuadBatchArgs qb;
@@ -1006,73 +1107,62 @@ static bool fleet_together(mppi_handle *const *hs, int n)
   return true;
 }
 
+// A batch batch_together admits: the instances' argument blocks travel by value (QuadBatchArgs), one rollout and one tail launch
+// per iteration on the device's batch stream.
+static int enqueue_pair(mppi_handle *const *hs, const float *states, int n)
+{
+  HP_CLOCK(hp_t);
+  mppi_handle *h0 = hs[0];
+  hipStream_t S = nullptr;
+  if (int rc = use_batch_stream(h0, &S)) return rc;
+  HP(kHpStream, hp_t);  // current device + the batch stream
+  if (int rc = collect(hs, n)) return rc;
+  HP(kHpWait, hp_t);  // wait_pending of every handle
+  if (int rc = begin_solves(hs, n, S, true)) return distrust(hs, n, rc);
+  const int iters = h0->cfg.num_iters;
+  for (int it = 0; it < iters; it++) {
+    QuadBatchArgs qb;
+    TailLaunch tl[kMaxBatch];
+    qb.n = n;
+    for (int i = 0; i < n; i++)
+      if (int rc = solve_step(hs[i], states + (size_t)MPPI_STATE_DIM * i, it, it == iters - 1, S, Eps::Pair, qb.inst[i], tl[i], nullptr))
+        return distrust(hs, n, rc);
+    for (int i = n; i < kMaxBatch; i++) qb.inst[i] = qb.inst[0];
+    HP(kHpArgs, hp_t);  // uploads + argument blocks
+    hipError_t e = launch_rollout_batch(hs, n, qb, false, S);
+    HP(kHpPairRollout, hp_t);
+    if (e == hipSuccess) e = launch_solve_tail_batch(tl, n, S);
+    HP(kHpPairTail, hp_t);
+    if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "batched launch", e));
+  }
+  finish_solves(hs, states, n, false);
+  HP_CALL(kHpDecide);
+  return MPPI_OK;
+}
+
 // The batched solve of a fleet (fleet_together).  The argument blocks of an iteration -- rollout, tail, generator -- are staged in
-// the device's block and sent with one copy in front of the iteration's three launches.
+// the device's block and sent with one copy in front of the iteration's three launches, under the block's lock.
 static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
 {
   mppi_handle *h0 = hs[0];
-  HIPCHK(h0, ensure_device(h0->cfg.device));
-  if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
-  const hipStream_t S = h0->batch_s;
-  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+  hipStream_t S = nullptr;
+  if (int rc = use_batch_stream(h0, &S)) return rc;
   FleetBlock *fb = fleet_block(h0->cfg.device);
   if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
-  const int iters = h0->cfg.num_iters;
-  // First pass, as in the batch call: whatever can fail is checked before any handle is changed.
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    int rc = recover_timed_out(h);
-    if (rc == MPPI_OK) rc = wait_pending(h);
-    if (rc) return rc;
-    if (h->explicit_iters > 0 && h->explicit_iters != iters)
-      return fail(h, MPPI_ERR_STATE, "explicit noise holds a different number of iterations");
-  }
-  auto poison = [&](int rc_) {
-    for (int i = 0; i < n; i++) {
-      hs[i]->slid_valid = false;
-      hs[i]->u_dirty = true;
-      hs[i]->pending = false;
-    }
-    return rc_;
-  };
+  if (int rc = collect(hs, n)) return rc;
   std::lock_guard<std::mutex> lk(fb->mu);
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    int rc = hand_over(h, S);
-    if (rc == MPPI_OK) rc = upload_controls_if_dirty(h, S);
-    if (rc) return poison(rc);
-    h->seq = next_seq(h);
-    forget_solve_state(h);
-  }
+  if (int rc = begin_solves(hs, n, S, true)) return distrust(hs, n, rc);
+  const int iters = h0->cfg.num_iters;
   TailLaunch tl[kMaxFleet];
   for (int it = 0; it < iters; it++) {
-    const bool last = (it == iters - 1);
     unsigned char *host = nullptr;
     hipError_t e = arg_block_stage(fb->args, &host);
-    if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "fleet argument block", e));
+    if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "fleet argument block", e));
     RolloutArgs *ra = reinterpret_cast<RolloutArgs *>(host);
     NoiseFleetDesc *nd = reinterpret_cast<NoiseFleetDesc *>(host + fleet_noise_offset(n));
-    for (int i = 0; i < n; i++) {
-      mppi_handle *h = hs[i];
-      const bool explicit_noise = h->explicit_iters > 0;
-      float *noise;
-      nd[i] = NoiseFleetDesc{};  // explicit noise: draws nothing
-      if (explicit_noise) {
-        noise = h->d_noise + (size_t)it * ((size_t)h->K * h->T * 2);
-      } else {
-        // the handle's generator stream and buffers move exactly as acquire_noise moves them for its own solve
-        h->gen_cur = 1 - h->gen_cur;
-        noise = h->d_gen[h->gen_cur];
-        nd[i] = NoiseFleetDesc{h->d_rng[h->rng_cur], h->d_rng[1 - h->rng_cur], h->d_jump, noise, h->K, h->T, h->noise_L, h->noise_C};
-        h->rng_cur = 1 - h->rng_cur;
-      }
-      h->v_buf = noise;
-      fill_rollout_args(h, states + (size_t)MPPI_STATE_DIM * i, noise, ra[i]);
-      if (int trc = tag_min_cost(h, ra[i], S)) return poison(trc);
-      next_tail_epoch(h);
-      tl[i] = tail_launch(h, noise, last);
-      if (last) h->slid_valid = wants_slid_copy(h);
-    }
+    for (int i = 0; i < n; i++)
+      if (int rc = solve_step(hs[i], states + (size_t)MPPI_STATE_DIM * i, it, it == iters - 1, S, Eps::Fleet, ra[i], tl[i], &nd[i]))
+        return distrust(hs, n, rc);
     fill_solve_tail_fleet(host + fleet_tail_offset(n), tl, n);
     e = arg_block_send(fb->args, fleet_bytes(n), S);
     const unsigned char *dev = fb->args.d;
@@ -1080,18 +1170,13 @@ static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
     if (e == hipSuccess)
       e = form_desc(h0->forced).fleet(h0, ra, reinterpret_cast<const RolloutArgs *>(dev), n, S);
     if (e == hipSuccess) e = launch_solve_tail_fleet(tl, n, dev + fleet_tail_offset(n), S);
-    if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "fleet launch", e));
+    if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "fleet launch", e));
     for (int i = 0; i < n; i++) {
       hs[i]->launch_instances = n;
       hs[i]->launch_gated = false;
     }
   }
-  for (int i = 0; i < n; i++) {
-    hs[i]->explicit_iters = 0;
-    hs[i]->pending = true;
-    note_solve_state(hs[i], states + (size_t)MPPI_STATE_DIM * i, true);
-    hs[i]->pending_timed = false;
-  }
+  finish_solves(hs, states, n, false);
   return MPPI_OK;
 }
 
@@ -1132,15 +1217,7 @@ int mppi_compute_control(mppi_handle *h, const float state[MPPI_STATE_DIM])
 int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states, int n)
 {
   if (!hs || !states || n < 1) return MPPI_ERR_INVALID;
-#ifdef MPPI_HOSTPROF
-  static double hb[8] = {0}; static double hbn = 0; static std::chrono::steady_clock::time_point hb_prev_end;
-  auto hb_t = std::chrono::steady_clock::now();
-  if (hbn > 0) hb[0] += std::chrono::duration<double, std::micro>(hb_t - hb_prev_end).count();  // previous batch_async returned -> this one entered (synchronize + slides of the caller)
-  // (the first call creates the device's batch stream, ~3 ms: read these averages over many calls with that in mind)
-#define HB(i) do { auto n__ = std::chrono::steady_clock::now(); hb[i] += std::chrono::duration<double, std::micro>(n__ - hb_t).count(); hb_t = n__; } while (0)
-#else
-#define HB(i) do { } while (0)
-#endif
+  HP_CLOCK(hp_t);
   for (int i = 0; i < n; i++) {
     if (!hs[i]) return MPPI_ERR_INVALID;
     for (int q = 0; q < i; q++)
@@ -1194,84 +1271,8 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     }
     return MPPI_OK;
   }
-  HB(1);  // the decision: one launch for all?
-  // (the device's batch stream is looked up once per handle)
-  HIPCHK(h0, ensure_device(h0->cfg.device));
-  if (!h0->batch_s) h0->batch_s = batch_stream(h0->cfg.device);
-  const hipStream_t S = h0->batch_s;
-  if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
-  const int iters = h0->cfg.num_iters;
-  HB(2);  // current device + the batch stream
-  // First pass: everything that can fail without having touched a handle -- every handle's previous solve collected,
-  // every handle's explicit noise checked -- so that one handle's error does not leave its partners half-advanced.
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    int rc = recover_timed_out(h);
-    if (rc == MPPI_OK) rc = wait_pending(h);  // finish a previous asynchronous solve first
-    if (rc) return rc;
-    if (h->explicit_iters > 0 && h->explicit_iters != iters)
-      return fail(h, MPPI_ERR_STATE, "explicit noise holds a different number of iterations");
-  }
-  // From here on handles change (sequence numbers, generator buffers, the slid copy's validity).  A HIP error below
-  // leaves every handle of the batch in the state "nothing on the device can be trusted": the host copies of U / hist
-  // are uploaded again by the next solve, no slid copy is offered to mppi_slide_control_seq.
-  auto poison = [&](int rc_) {
-    for (int i = 0; i < n; i++) {
-      hs[i]->slid_valid = false;
-      hs[i]->u_dirty = true;
-      hs[i]->pending = false;
-    }
-    return rc_;
-  };
-  HB(3);  // wait_pending of every handle
-  for (int i = 0; i < n; i++) {
-    mppi_handle *h = hs[i];
-    int rc = hand_over(h, S);
-    if (rc == MPPI_OK) rc = upload_controls_if_dirty(h, S);
-    if (rc) return poison(rc);
-    h->seq = next_seq(h);
-    forget_solve_state(h);
-  }
-  for (int it = 0; it < iters; it++) {
-    QuadBatchArgs qb;
-    TailLaunch tl[kMaxBatch];
-    qb.n = n;
-    const bool last = (it == iters - 1);
-    for (int i = 0; i < n; i++) {
-      mppi_handle *h = hs[i];
-      const bool explicit_noise = h->explicit_iters > 0;
-      // eps: the explicit buffer, else the control wavefront's own generator; the buffer receives the applied controls
-      float *noise = explicit_noise ? h->d_noise + (size_t)it * ((size_t)h->K * h->T * 2) : h->d_gen[h->gen_cur];
-      h->v_buf = noise;
-      RolloutArgs &a = qb.inst[i];
-      fill_rollout_args(h, states + (size_t)MPPI_STATE_DIM * i, noise, a);
-      if (int trc = tag_min_cost(h, a, S)) return trc;
-      if (!explicit_noise) use_inline_noise(h, a);
-      tl[i] = tail_launch(h, noise, last);
-      if (last) h->slid_valid = wants_slid_copy(h);
-    }
-    for (int i = n; i < kMaxBatch; i++) qb.inst[i] = qb.inst[0];
-    HB(4);  // uploads + argument blocks
-    hipError_t e = launch_rollout_batch(hs, n, qb, false, S);
-    HB(5);  // rollout launch
-    if (e == hipSuccess) e = launch_solve_tail_batch(tl, n, S);
-    HB(6);  // tail launch
-    if (e != hipSuccess) return poison(fail(h0, MPPI_ERR_HIP, "batched launch", e));
-  }
-  for (int i = 0; i < n; i++) {
-    hs[i]->explicit_iters = 0;
-    hs[i]->pending = true;
-    note_solve_state(hs[i], states + (size_t)MPPI_STATE_DIM * i, true);
-    hs[i]->pending_timed = false;
-  }
-#ifdef MPPI_HOSTPROF
-  hbn += 1;
-  hb_prev_end = std::chrono::steady_clock::now();
-  if (((long)hbn % 1000) == 0)
-    fprintf(stderr, "hostprof batch (us per call, %.0f calls): between calls %.2f | decide %.2f | device + stream %.2f | wait_pending %.2f | upload+args %.2f | rollout launch %.2f | tail launch %.2f\n",
-            hbn, hb[0] / hbn, hb[1] / hbn, hb[2] / hbn, hb[3] / hbn, hb[4] / hbn, hb[5] / hbn, hb[6] / hbn);
-#endif
-  return MPPI_OK;
+  HP(kHpDecide, hp_t);  // the decision: one launch for all?
+  return enqueue_pair(hs, states, n);
 }
 
 int mppi_compute_control_batch(mppi_handle *const *hs, const float *states, int n)
@@ -1386,21 +1387,15 @@ int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *
   OWN(h);
   rc = upload_controls_if_dirty(h, h->stream);
   if (rc) return rc;
-  const bool explicit_noise = h->explicit_iters > 0;
-  const bool inline_noise = !explicit_noise && !h->prefetch_valid && has_noise_wave(h);
-  float *noise = h->d_noise;  // explicit: its first iteration
-  if (!explicit_noise && !inline_noise) {
-    rc = acquire_noise(h, &noise);
-    if (rc) return rc;
-  } else if (inline_noise) {
-    noise = h->d_gen[h->gen_cur];
-  }
+  float *noise = nullptr;  // (explicit noise: its first iteration)
+  bool in_kernel = false;
+  rc = eps_source(h, Eps::Single, 0, &noise, &in_kernel, nullptr);
+  if (rc) return rc;
   h->explicit_iters = 0;
   forget_solve_state(h);
-  h->v_buf = noise;
   RolloutArgs a;
   fill_rollout_args(h, state, noise, a);
-  if (inline_noise) use_inline_noise(h, a);
+  if (in_kernel) use_inline_noise(h, a);
   rc = launch_rollout(h, a);
   if (rc) return rc;
   note_solve_state(h, state, false);

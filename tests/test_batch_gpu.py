@@ -249,6 +249,50 @@ def test_batch_then_single_then_batch_and_two_iterations():
         s.close()
 
 
+@pytest.mark.parametrize("form, n", [(None, 2), ("fleet16", 3)], ids=["pair", "fleet16"])
+def test_batch_single_rollout_only_batch_cross_the_drivers_on_the_same_handles(form, n):
+    """batch -> each handle alone -> mppi_rollout_only on one handle -> batch, generator noise, num_iters = 2, a slide between
+    the steps: the handles of the batch (the pair's one rollout launch; a fleet's three launches) follow twin handles that
+    make the same calls one by one, bit for bit after every step -- U, costs, weights, trajectory cost, applied controls.
+    Every driver draws its eps from the handle's generator stream in its own way; a step that left gen_cur / rng_cur
+    elsewhere than the handle's own solve does shows in the step after it.  K = 64, T = 8: the smallest K both batched
+    paths accept."""
+    cfg = S.make_config(64, 8, track="oval", num_iters=2)
+    ref, bat = [capi.Solver(cfg) for _ in range(n)], [capi.Solver(cfg) for _ in range(n)]
+    st = []
+    for i in range(n):
+        for s in (ref[i], bat[i]):
+            if form:
+                s.set_rollout_variant(form)
+            s.seed(500 + i, 0)
+        st.append(cfg["start_state"].copy())
+        st[i][1] += np.float32(0.3 * i)
+    try:
+        for step, op in enumerate(["batch", "single", "rollout_only", "batch"]):
+            if op == "rollout_only":
+                got, want = bat[0].rollout_only(st[0]), ref[0].rollout_only(st[0])
+                np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32), err_msg="rollout_only costs")
+            else:
+                for i in range(n):
+                    ref[i].compute_control(st[i])
+                if op == "batch":
+                    capi.compute_control_batch(bat, st)
+                else:
+                    for i in range(n):
+                        bat[i].compute_control(st[i])
+                infos = [s.debug_launch_info() for s in bat]
+                assert infos == [(n if op == "batch" else 1, 0)] * n, (step, op, infos)
+            for i in range(n):
+                _same(bat[i].get_results(), ref[i].get_results())
+                np.testing.assert_array_equal(bat[i].get_applied_controls().view(np.uint32),
+                                              ref[i].get_applied_controls().view(np.uint32), err_msg="step %d (%s) V[%d]" % (step, op, i))
+                ref[i].slide_control_seq(1)
+                bat[i].slide_control_seq(1)
+    finally:
+        for s in ref + bat:
+            s.close()
+
+
 def test_batches_the_library_cannot_share_a_launch_for_fall_back_to_per_handle_solves(golden_dir):
     """More groups than CUs, different layer lists, the basis-function model, a single handle: the call still
     solves every handle (on its own stream), with its own results."""
