@@ -88,6 +88,7 @@ hipError_t batch_bf(const mppi_handle *h0, const FormDesc &d, const QuadBatchArg
 hipError_t batch_bf_row(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_row_batch(qb, s); }
 hipError_t fleet_16(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet16(h->net, h_inst, d_inst, n, h->num_simds / 4, s); }
 hipError_t fleet_multi(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet_multi(h->hidden, h->n_hidden, h_inst, d_inst, n, s); }
+hipError_t fleet_bf(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet_bf(h_inst, d_inst, n, h->num_simds, h->fleet_bf_waves, s); }
 constexpr const char *kMfma16 = "mfma16x16x4", *kMfma4 = "mfma4x4x1";
 constexpr FormDesc kForms[] = {
     // form, image, noise, flags, standard shapes, launch, arg, batch {launch, pair only, same list, waves}, fleet, cap, name {stem, tag, suffix, gen}, ask {first, second, K multiple}
@@ -117,6 +118,7 @@ constexpr FormDesc kForms[] = {
     {Form::Bf2, Image::Theta, Noise::Never, 0, nullptr, one_bf, 2, {}, nullptr, nullptr, {"basis_funcs25_valu_2w"}, {}},
     {Form::Bf3, Image::Theta, Noise::InKernel, 0, nullptr, one_bf, 3, {batch_bf, false, false, 3}, nullptr, nullptr, {"basis_funcs25_valu_3w"}, {}},
     {Form::BfRow, Image::BfRow, Noise::InKernel, kGate | kByName | kNegateYaw, nullptr, one_bf_row, 0, {batch_bf_row, true, false, 16}, nullptr, nullptr, {"basis_funcs25_row8w"}, {}},
+    {Form::FleetBf, Image::Theta, Noise::Never, kByName, nullptr, one_fleet, 0, {}, fleet_bf, nullptr, {"basis_funcs25_fleet", Tag::ForcedWaves}, {}},
 };
 static_assert(rows_in_order(kForms, &FormDesc::form), "row i of kForms describes form i");
 }  // namespace
@@ -129,7 +131,7 @@ Form form_of(const mppi_handle *h)
     // basis-function model, wavefronts per 64 rollouts: dynamics + cost + control wave (in-kernel generator) while each gets
     // a SIMD of its own; dynamics + cost wave up to twice that; else one wave
     if (h->forced == Form::Bf1 || h->forced == Form::Bf2 || h->forced == Form::Bf3) return h->forced;
-    if (h->forced == Form::BfRow) return Form::BfRow;  // by name only
+    if (h->forced == Form::BfRow || h->forced == Form::FleetBf) return h->forced;  // by name only
     if (3 * (h->K / 64) <= h->num_simds) return Form::Bf3;
     return (2 * (h->K / 64) <= 2 * h->num_simds) ? Form::Bf2 : Form::Bf1;
   }
@@ -220,6 +222,8 @@ struct Request {
   const char *lds_unit;
   bool needs_image;         // the form's image was allocated with the handle; refusal: "<name> form: this handle has no image"
   int (*prepare)(mppi_handle *h, Form f);
+  int waves;                // "fleet_bf_w<N>": the wave count the request forces on the fleet's launch; 0: none
+  const char *say;          // the name its refusals speak of; nullptr: its own
 };
 const char kRowMsg[] = "row form exists for 6-32x2-4", kM44Msg[] = "m44 form exists for 6-64x2-4 and 6-64x4-4",
            kRow64Msg[] = "row64 form exists for 6-64x2-4 and 6-64x4-4", kOctMsg[] = "oct form exists for 6-64x2-4 and 6-64x4-4",
@@ -227,7 +231,8 @@ const char kRowMsg[] = "row form exists for 6-32x2-4", kM44Msg[] = "m44 form exi
            kLds128Msg[] = "lds128 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer",
            kLds16Msg[] = "lds16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer",
            kGlb16Msg[] = "glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer",
-           kGlb44Msg[] = "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer";
+           kGlb44Msg[] = "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer",
+           kFleetBfK[] = "fleet_bf form needs K to be a multiple of 64";
 constexpr int kNoPref = -1;
 const Request kRequests[] = {
     // name, with cap, network form, basis form, pref, gen | model, shape, its refusal | K multiple | LDS bytes, limit, unit | image | preparation
@@ -261,6 +266,13 @@ const Request kRequests[] = {
     // handles share the launches of a batched solve
     {"fleet_multi4", false, Form::FleetMulti4, Form::FleetMulti4, kNoPref, Gen::On, Model::Network, form_shape,
      "fleet_multi4 form exists for 6-32x2-4, 6-32x4-4 and 6-64x2-4", 64, "fleet_multi4 form needs K to be a multiple of 64", nullptr, nullptr, nullptr, false, prepare_fleet},
+    // the workgroups of the basis-function model's own kernels and the bits of "bf3" (eps from the stand-alone generator); up to 64
+    // such handles share the launches of a batched solve.  "fleet_bf": the wave count per 64 rollouts is fleet_bf_plan's choice;
+    // "_w1" / "_w2" / "_w3": that count forced (tests and A/Bs: every kernel at any shape on any device)
+    {"fleet_bf", false, Form::FleetBf, Form::FleetBf, kNoPref, Gen::On, Model::Basis, nullptr, nullptr, 64, kFleetBfK, nullptr, nullptr, nullptr, false, prepare_fleet},
+    {"fleet_bf_w1", false, Form::FleetBf, Form::FleetBf, kNoPref, Gen::On, Model::Basis, nullptr, nullptr, 64, kFleetBfK, nullptr, nullptr, nullptr, false, prepare_fleet, 1, "fleet_bf"},
+    {"fleet_bf_w2", false, Form::FleetBf, Form::FleetBf, kNoPref, Gen::On, Model::Basis, nullptr, nullptr, 64, kFleetBfK, nullptr, nullptr, nullptr, false, prepare_fleet, 2, "fleet_bf"},
+    {"fleet_bf_w3", false, Form::FleetBf, Form::FleetBf, kNoPref, Gen::On, Model::Basis, nullptr, nullptr, 64, kFleetBfK, nullptr, nullptr, nullptr, false, prepare_fleet, 3, "fleet_bf"},
     // lds16's wave / lds128's group for every layer list up to 256 wide
     {"glb16", true, Form::Glb16, Form::Glb16, kNoPref, Gen::Keep, Model::Network, glb16_shape, kGlb16Msg, 64, "glb16 form needs K to be a multiple of 64", nullptr,
      nullptr, nullptr, false, build_image},
@@ -295,6 +307,10 @@ const char *mppi_rollout_variant(const mppi_handle *h)
   switch (nm.tag) {
     case Tag::Fixed: return nm.stem;
     case Tag::HiddenLayers: snprintf(buf, sizeof(buf), "%s_h%d_l%d%s%s", nm.stem, h->hidden, h->n_hidden, nm.suffix, gen); break;
+    case Tag::ForcedWaves:
+      if (h->fleet_bf_waves == 0) return nm.stem;
+      snprintf(buf, sizeof(buf), "%s_w%d", nm.stem, h->fleet_bf_waves);
+      break;
     case Tag::LayersWidth: snprintf(buf, sizeof(buf), "%s_l%d_w%d", nm.stem, h->net.n_layers - 2, widest_hidden(h->net)); break;  // the forms of a layer list
   }
   return buf;
@@ -316,7 +332,7 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
   char msg[160];
   auto refuse = [&](const char *what) { return fail(h, MPPI_ERR_UNSUPPORTED, what); };
   if (r->model != Model::Any && h->basis != (r->model == Model::Basis)) {
-    snprintf(msg, sizeof(msg), "%s is a form of the %s model", r->name, r->model == Model::Basis ? "basis-function" : "network");
+    snprintf(msg, sizeof(msg), "%s is a form of the %s model", r->say ? r->say : r->name, r->model == Model::Basis ? "basis-function" : "network");
     return refuse(msg);
   }
   const Form f = h->basis ? r->bf : r->net;
@@ -336,6 +352,7 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
   if (r->pref >= 0) h->pref = (Pref)r->pref;
   if (form_desc(f).cap) h->*form_desc(f).cap = cap;
   h->forced = f;
+  h->fleet_bf_waves = r->waves;
   if (r->gen != Gen::Keep) h->multi_standalone_noise = r->gen == Gen::On;
   return MPPI_OK;
 }

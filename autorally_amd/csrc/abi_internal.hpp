@@ -70,6 +70,9 @@ enum class Form : int {
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
   BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
                                     // riders per 16 rollouts), the bits of Bf1..3; by name only ("bf_row")
+  FleetBf,                          // rollout_fleet_bf.hip: the workgroups of Bf1..3 with the argument block read from device memory and eps from
+                                    // the stand-alone generator: up to 64 handles of the basis-function model share a launch; by name only
+                                    // ("fleet_bf", "fleet_bf_w1..3"), no gated form
   Count
 };
 enum class Pref : int { Auto = 0, Mfma, Valu, ValuLds };
@@ -199,10 +202,11 @@ struct mppi_handle {
   float *d_costs = nullptr, *d_w = nullptr;
   float *d_map = nullptr;
   mppi_abi::DeviceImage img[(int)mppi_abi::Image::Count];  // the weight images this handle has (d == nullptr: not this one)
-  mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16", "fleet_multi4": the argument block of this handle's own launches (on its own stream); only a
+  mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16", "fleet_multi4", "fleet_bf": the argument block of this handle's own launches (on its own stream); only a
                                  // handle that asked for the form has one
   int glb16_cap = -1;            // "glb16_r<N>": the cap on the resident stream blocks; -1: none
   int glb44_cap = -1;            // "glb44_r<N>": the cap on the resident stream quads; -1: none
+  int fleet_bf_waves = 0;        // "fleet_bf_w<N>": the wave count of the fleet's launch forced; 0 ("fleet_bf"): fleet_bf_plan chooses
   // mppi_trace_rollouts: the records of one chunk of trace_chunk rollouts -- states [c][T][7], controls [c][T][2], step costs
   // [c][T], costs [c], first_crash [c] (int) -- allocated with the handle (nothing is allocated or freed while armed); the
   // chunk's rollout indices reach the kernel through host-mapped memory (h_trace_ks / d_trace_ks: no upload on the stream)
@@ -332,7 +336,8 @@ using BatchFn = hipError_t (*)(const mppi_handle *h0, const FormDesc &d, const Q
 using FleetFn = hipError_t (*)(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t stream);
 enum class Noise { Never, InKernel, UnlessStandalone };  // does the kernel draw eps itself?  UnlessStandalone (oct, multi): unless the
                                                           // stand-alone generator was asked for ("_gen") or is the automatic choice
-enum class Tag { Fixed, HiddenLayers, LayersWidth };      // the reported name: stem [+ "_h%d_l%d" | "_l%d_w%d"] + suffix [+ "_gen"]
+enum class Tag { Fixed, HiddenLayers, LayersWidth, ForcedWaves };  // the reported name: stem [+ "_h%d_l%d" | "_l%d_w%d"] + suffix [+ "_gen"];
+                                                                   // ForcedWaves: stem [+ "_w%d" where the handle forces a wave count]
 enum : unsigned {
   kGate = 1,       // has a gated kernel (mppi_arm): the latency forms with riders
   kPublishes = 2,  // publishes its minimum cost for the streaming tail (multi_group.hpp)
@@ -385,7 +390,7 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
 int tag_min_cost(mppi_handle *h, RolloutArgs &a, hipStream_t stream);
 int launch_rollout(mppi_handle *h, const RolloutArgs &a);
 hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a);  // a handle of a fleet form solved alone
-int fleet_prepare(mppi_handle *h);  // what a handle that asks for "fleet16" or "fleet_multi4" needs of its own (fleet_one), once
+int fleet_prepare(mppi_handle *h);  // what a handle that asks for "fleet16", "fleet_multi4" or "fleet_bf" needs of its own (fleet_one), once
 int check_ready(mppi_handle *h);
 int launch_generator(mppi_handle *h, float *dst);
 int acquire_noise(mppi_handle *h, float **buf_out);

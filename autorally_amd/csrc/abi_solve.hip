@@ -1081,8 +1081,8 @@ static bool batch_together(mppi_handle *const *hs, int n)
   return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
 }
 
-// The fleet: 2..kMaxFleet handles ALL forced to "fleet16" or ALL to "fleet_multi4" (a mixed set is solved handle by handle) on one
-// device with one whole layer list, one num_iters and one pair (affine
+// The fleet: 2..kMaxFleet handles ALL forced to "fleet16", ALL to "fleet_multi4" or ALL to "fleet_bf" (a mixed set is solved handle by
+// handle) on one device with one whole layer list (the basis-function model: one forced wave count instead), one num_iters and one pair (affine
 // costmap transform, control cost needed) -- one kernel instance serves the launch, and a superset kernel would not keep every
 // instance's bits (batch_together) -- K <= 4096 each (the one-workgroup-per-row tail), no stage timing, capture or prefetched
 // draws, every handle ready.  Such a set shares its launches: per iteration one generator, one rollout and one tail launch on
@@ -1095,10 +1095,14 @@ static bool fleet_together(mppi_handle *const *hs, int n)
   fill_cost_args(h0, c0);
   for (int i = 0; i < n; i++) {
     const mppi_handle *h = hs[i];
-    if (h->basis || !form_desc(h0->forced).fleet || h->forced != h0->forced || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
-    if (h->net.n_layers != h0->net.n_layers) return false;
-    for (int l = 0; l < h->net.n_layers; l++)
-      if (h->net.layers[l] != h0->net.layers[l]) return false;
+    if (h->basis != h0->basis || !form_desc(h0->forced).fleet || h->forced != h0->forced || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
+    if (h->basis) {  // "fleet_bf": one wave count for the launch, forced on all or on none
+      if (h->fleet_bf_waves != h0->fleet_bf_waves) return false;
+    } else {
+      if (h->net.n_layers != h0->net.n_layers) return false;
+      for (int l = 0; l < h->net.n_layers; l++)
+        if (h->net.layers[l] != h0->net.layers[l]) return false;
+    }
     CostArgs ci;
     fill_cost_args(h, ci);
     if (ci.affine != c0.affine || ci.need_control_cost != c0.need_control_cost) return false;

@@ -269,6 +269,18 @@ hipError_t launch_rollout_bf_batch(const QuadBatchArgs &b, hipStream_t stream);
 hipError_t launch_dynamics_bf(const float *W, const float *states, const float *controls, float *ders, int n,
                               hipStream_t stream);
 
+// rollout_fleet_bf.hip: the workgroups of rollout_bf.hip (bf_group.hpp) for up to kMaxFleet independent controllers of the
+// basis-function model in one launch -- grid (64-rollout groups of the largest instance, instances), one wave count for the
+// launch, the instances' argument blocks an array in device memory, eps from every instance's noise buffer
+struct FleetBfPlan {
+  int waves, threads, grid_x, grid_y;  // all zero: no launch (n outside 1..kMaxFleet, a K that is no multiple of 64, forced_waves outside 0..3)
+};
+// Ks: the instances' rollouts; simds: the device's SIMDs; forced_waves: 1..3, or 0 for form_of's rule on the groups of the whole
+// fleet G = sum K / 64 (3 waves while 3 G <= simds, 2 while G <= simds, else 1; n = 1: form_of's choice for that handle)
+FleetBfPlan fleet_bf_plan(const int *Ks, int n, int simds, int forced_waves);
+// h_inst: the n argument blocks on the host (K is read there); d_inst: the same blocks in device memory
+hipError_t launch_rollout_fleet_bf(const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, int simds, int forced_waves, hipStream_t stream);
+
 // rollout_bf_row.hip: latency form of the basis-function model -- four dynamics waves (four rollouts each, a rollout's sixteen
 // (output, y-thread) cells on one DPP row) + pose, cost, control and noise wave per 16 rollouts; a.wpack = the per-lane image
 // (pack_bf_row_weights, abi_pack.hip): 16-B entry e of lane p = 4 j + y at float4 index e * 16 + p; slot m of a lane is basis

@@ -65,6 +65,10 @@ extern "C" {
  *    "multi4_tree_gen" (6-32x2-4, 6-32x4-4, 6-64x2-4) with the argument block read from device memory; 2..64 handles forced to it
  *    share the launches of mppi_compute_control_batch as "fleet16" handles do; no new export, no gated form, the automatic choice
  *    does not change. */
+/*    (still 5) + rollout variants "fleet_bf", "fleet_bf_w1", "fleet_bf_w2", "fleet_bf_w3", name "basis_funcs25_fleet[_w<N>]": the
+ *    workgroups and the bits of the basis-function model's own kernels with the argument block read from device memory; 2..64
+ *    handles forced to it share the launches of mppi_compute_control_batch as "fleet16" handles do; no new export, no gated
+ *    form, the automatic choice does not change. */
 /*    (still 5) + mppi_compute_feedback_gains_batch, mppi_debug_ddp_info, mppi_debug_device_tanhf (the DDP feedback gains of a fleet
  *    in one launch; compatible additions, the single and the pair call are unchanged). */
 /*    (still 5) + mppi_nominal_traj_batch, mppi_debug_nominal_info (the nominal trajectories of a fleet in one launch; compatible
@@ -227,6 +231,8 @@ int mppi_synchronize(mppi_handle *h);
  * per-handle solves; a set of "fleet16" handles with one that is not ready returns that handle's error before any has moved.
  * The "fleet_multi4" variant: the same rule and the same three launches for 2 <= n <= 64 handles that are ALL forced to
  * "fleet_multi4" (one of 6-32x2-4, 6-32x4-4, 6-64x2-4); a set that mixes "fleet16" and "fleet_multi4" handles is n per-handle solves.
+ * The "fleet_bf" variant (the basis-function model): the same rule and the same three launches for 2 <= n <= 64 handles that are
+ * ALL forced to "fleet_bf", or all to the same "fleet_bf_w<N>"; the layer list plays no part, the forced wave count must agree.
  * mppi_debug_launch_info tells which it was.  Either way every
  * handle's results are bit for bit those of its own mppi_compute_control, collected per handle with
  * mppi_synchronize / mppi_get_results.  The blocking form waits for all of them. */
@@ -447,6 +453,13 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     these shapes (ahead of "fleet16" at every fleet size, ahead of "auto" from 16 handles on); NO gated form; a
  *     handle solved alone runs the same kernel with one instance; by name only; MPPI_ERR_UNSUPPORTED for the basis-function model
  *     and for any list but 6-32x2-4, 6-32x4-4, 6-64x2-4 (K is a multiple of 64 on every handle: mppi_create).
+ *     "fleet_bf" basis_funcs25_fleet (the basis-function model only): the model's own workgroups -- one, two or three waves per
+ *     64 rollouts, the bodies of basis_funcs25_valu / _2w / _3w -- with the argument block read from device memory and eps from
+ *     the stand-alone generator kernel, so that up to 64 handles share ONE rollout launch (mppi_compute_control_batch: the
+ *     sharing rule is stated there); the bits of "bf3".  One wave count per launch, chosen by the rule of a single handle with the
+ *     64-rollout groups counted over the fleet (three waves while 3 x groups <= SIMDs, two while groups <= SIMDs, else one);
+ *     "fleet_bf_w1" / "fleet_bf_w2" / "fleet_bf_w3" (basis_funcs25_fleet_w<N>) force the count.  NO gated form; a handle solved
+ *     alone runs the same kernel with one instance; by name only; MPPI_ERR_UNSUPPORTED for the network model.
  *     "glb16" mfma16x16x4_glb_l<hidden layers>_w<widest hidden layer>: "lds16"'s wavefront for EVERY layer list of the network model
  *     (3 <= n_layers <= 8, hidden widths 1..256): the same image with up to 16 tiles per layer; its head (biases, layer 0) and the
  *     first R of its 1 KB blocks are copied into LDS, the other blocks are read from the image in global memory (it stays in L2),

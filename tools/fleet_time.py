@@ -11,6 +11,14 @@ With "d" among --ways: (d) every handle forced to "fleet_multi4" -- the register
 (6-32x2-4, 6-32x4-4 and 6-64x2-4; any other list: not available) -- and with "A": "fleet16" a second time, the A/A spread of the
 visit beside the ratios (--ways dabcA).
 
+    python tools/fleet_time.py --model bf [--n 16] [--K 2560] [--T 100] [--ticks 200] [--warm 20] [--ways f123cF]
+
+The basis-function model (the golden W of tests/golden/models) instead of a network: (f) every handle forced to "fleet_bf" -- the
+model's own workgroups as a fleet form, the wave count per 64 rollouts chosen by fleet_bf_plan --, (1) (2) (3) "fleet_bf_w1" /
+"_w2" / "_w3", that count forced, (c) "auto" (up to 4 handles in one launch of the three-wave kernel, beyond that handle by
+handle), (F) "fleet_bf" a second time: the A/A spread of the visit; and, handle by handle, the single-handle forms the wave
+counts match: (p) "fused" (one wave), (q) "quad" (two), (r) "bf3" (three).
+
     python tools/fleet_time.py --ddp [--T 100] [--ticks 200] [--net ...]
 
 The DDP feedback gains of the fleet instead (n = 2, 4, 16, 64): mppi_compute_feedback_gains_batch -- one launch of ddp_fleet_kernel --
@@ -33,6 +41,14 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 WAYS = (("d", "fleet_multi4"), ("a", "fleet16"), ("b", "lds16"), ("c", "auto"), ("A", "fleet16"))
+BF_WAYS = (("f", "fleet_bf"), ("1", "fleet_bf_w1"), ("2", "fleet_bf_w2"), ("3", "fleet_bf_w3"), ("c", "auto"), ("F", "fleet_bf"),
+           ("p", "fused"), ("q", "quad"), ("r", "bf3"))
+BF = "bf"  # in place of a layer list: the basis-function model
+
+
+def bf_W():
+    from autorally_amd import params as P
+    return P.load_bf_npz(os.path.join(ROOT, "tests", "golden", "models", "basis_function_09_12_2018.npz"))
 
 
 def fleet(net, variant, n, K, T):
@@ -40,14 +56,20 @@ def fleet(net, variant, n, K, T):
     parameters and the seed), forced to `variant`, and their states."""
     from autorally_amd import capi
     from autorally_amd import synthetic as S
-    base = S.make_config(K, T, layers=list(net), track="oval", opt_stride=1)
+    if net == BF:
+        base = S.make_config(K, T, track="oval", opt_stride=1, bf_W=bf_W())
+    else:
+        base = S.make_config(K, T, layers=list(net), track="oval", opt_stride=1)
     sols, states = [], []
     for i in range(n):
         st = np.array(base["start_state"], np.float32)
         st[0] += np.float32(0.4 * i)
         st[4] += np.float32(0.1 * (i % 5))
-        cfg = dict(base, theta=(np.asarray(base["theta"], np.float32) * np.float32(1.0 + 0.005 * i)),
-                   cost=dict(base["cost"], desired_speed=6.0 + 0.25 * i), start_state=st)
+        cfg = dict(base, cost=dict(base["cost"], desired_speed=6.0 + 0.25 * i), start_state=st)
+        if net == BF:
+            cfg["bf_W"] = np.asarray(base["bf_W"], np.float32) * np.float32(1.0 + 0.005 * i)
+        else:
+            cfg["theta"] = np.asarray(base["theta"], np.float32) * np.float32(1.0 + 0.005 * i)
         sol = capi.Solver(cfg)
         if variant != "auto":
             try:
@@ -103,6 +125,20 @@ def table(nets, n=16, K=1920, T=100, ticks=200, warm=20, ways="abc"):
             n, K, T, row["net"], row["a_ms"], row["a_instances"], row["b_ms"], row["c_form"], row["c_ms"], row["b_ms"] / row["a_ms"],
             row["c_ms"] / row["a_ms"]), flush=True)
     return rows
+
+
+def table_bf(n=16, K=2560, T=100, ticks=200, warm=20, ways="f123cF"):
+    """One row for the basis-function model: every way of BF_WAYS named in `ways`, in BF_WAYS' order, in one process."""
+    row = {"net": BF, "n": n, "K": K, "T": T}
+    for key, variant in BF_WAYS:
+        if key not in ways:
+            continue
+        ms, inst, name = tick_ms(BF, variant, n, K, T, ticks, warm)
+        row[key + "_ms"], row[key + "_instances"], row[key + "_form"] = ms, inst, name
+    print("FLEET n=%d K=%d T=%d model=bf: %s" % (n, K, T, "  ".join(
+        "(%s) %s %.4f ms [%s, %d per launch]" % (key, variant, row[key + "_ms"], row[key + "_form"], row[key + "_instances"])
+        for key, variant in BF_WAYS if key + "_ms" in row)), flush=True)
+    return [row]
 
 
 def ddp_ms(net, n, K=64, T=100, calls=200, warm=10):
@@ -236,11 +272,12 @@ def nominal_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=16)
-    ap.add_argument("--K", type=int, default=1920)
+    ap.add_argument("--K", type=int, default=None, help="rollouts per handle (default 1920; --model bf: 2560)")
+    ap.add_argument("--model", default="nn", choices=["nn", "bf"], help="bf: the basis-function model, ways f123cF (and p, q, r)")
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--warm", type=int, default=20)
-    ap.add_argument("--ways", default="abc", help="which of (a) fleet16, (b) lds16, (c) auto, (d) fleet_multi4, (A) fleet16 again to run")
+    ap.add_argument("--ways", default=None, help="(default abc; --model bf: f123cF) which of (a) fleet16, (b) lds16, (c) auto, (d) fleet_multi4, (A) fleet16 again to run")
     ap.add_argument("--net", nargs="*", default=["6-32-32-4", "6-64-64-64-64-4"])
     ap.add_argument("--ddp", action="store_true", help="the DDP feedback gains of the fleet instead: the batch entry against the host "
                     "passes, n = 2, 4, 16, 64 (mppi_compute_feedback_gains_batch)")
@@ -255,7 +292,10 @@ def main():
     if a.ddp:
         print(json.dumps(ddp_table([[int(x) for x in s.split("-")] for s in a.net], T=a.T, calls=a.ticks)))
         return
-    rows = table([[int(x) for x in s.split("-")] for s in a.net], a.n, a.K, a.T, a.ticks, a.warm, a.ways)
+    if a.model == "bf":
+        print(json.dumps(table_bf(a.n, a.K or 2560, a.T, a.ticks, a.warm, a.ways or "f123cF")))
+        return
+    rows = table([[int(x) for x in s.split("-")] for s in a.net], a.n, a.K or 1920, a.T, a.ticks, a.warm, a.ways or "abc")
     print(json.dumps(rows))
 
 
