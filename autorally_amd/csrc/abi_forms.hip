@@ -86,12 +86,26 @@ hipError_t batch_lds128(const mppi_handle *h0, const FormDesc &d, const QuadBatc
 hipError_t batch_glb44(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_glb44_batch(h0->net, qb, h0->glb44_cap, s); }
 hipError_t batch_bf(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_batch(qb, s); }
 hipError_t batch_bf_row(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_row_batch(qb, s); }
-hipError_t fleet_16(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet16(h->net, h_inst, d_inst, n, h->num_simds / 4, s); }
-hipError_t fleet_multi(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet_multi(h->hidden, h->n_hidden, h_inst, d_inst, n, s); }
-hipError_t fleet_bf(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t s) { return launch_rollout_fleet_bf(h_inst, d_inst, n, h->num_simds, h->fleet_bf_waves, s); }
+// the fleet adapters: the forms of one list / shape / wave count read it from the first handle (fleet_together: it is every handle's)
+hipError_t fleet_16(mppi_handle *const *hs, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *, int n, hipStream_t s) { return launch_rollout_fleet16(hs[0]->net, h_inst, d_inst, n, hs[0]->num_simds / 4, s); }
+hipError_t fleet_multi(mppi_handle *const *hs, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *, int n, hipStream_t s) { return launch_rollout_fleet_multi(hs[0]->hidden, hs[0]->n_hidden, h_inst, d_inst, n, s); }
+hipError_t fleet_bf(mppi_handle *const *hs, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *, int n, hipStream_t s) { return launch_rollout_fleet_bf(h_inst, d_inst, n, hs[0]->num_simds, hs[0]->fleet_bf_waves, s); }
+// every handle's own list and cap
+hipError_t fleet_glb16(mppi_handle *const *hs, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *d_nets, int n, hipStream_t s)
+{
+  if (n < 1 || n > kMaxFleet) return hipErrorInvalidValue;
+  NetDesc nets[kMaxFleet];
+  int caps[kMaxFleet];
+  for (int i = 0; i < n; i++) {
+    nets[i] = hs[i]->net;
+    caps[i] = hs[i]->glb16_cap;
+  }
+  return launch_rollout_fleet_glb16(nets, caps, h_inst, d_inst, d_nets, n, hs[0]->num_simds / 4, s);
+}
+FleetGlbNet fleet_glb16_net(const mppi_handle *h) { return fleet_glb16_net_of(h->net, h->glb16_cap); }
 constexpr const char *kMfma16 = "mfma16x16x4", *kMfma4 = "mfma4x4x1";
 constexpr FormDesc kForms[] = {
-    // form, image, noise, flags, standard shapes, launch, arg, batch {launch, pair only, same list, waves}, fleet, cap, name {stem, tag, suffix, gen}, ask {first, second, K multiple}
+    // form, image, noise, flags, standard shapes, launch, arg, batch {launch, pair only, same list, waves}, fleet, cap, name {stem, tag, suffix, gen}, ask {first, second, K multiple}[, fleet net]
     {Form::Auto, Image::Mfma, Noise::Never, 0, nullptr, nullptr, 0, {}, nullptr, nullptr, {""}, {}},  // form_of never answers Auto
     {Form::Fused64, Image::Mfma, Noise::Never, 0, mfma_variant_supported, one_mfma, 64, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_fused_b64"}, {}},
     {Form::Fused256, Image::Mfma, Noise::Never, 0, mfma_variant_supported, one_mfma, 256, {}, nullptr, nullptr, {kMfma16, Tag::HiddenLayers, "_fused_b256"}, {"fused"}},
@@ -112,6 +126,7 @@ constexpr FormDesc kForms[] = {
     {Form::Glb44, Image::Glb44, Noise::InKernel, kGate | kByName, nullptr, one_glb44, 0, {batch_glb44, true, true, 16}, nullptr, &mppi_handle::glb44_cap, {"mfma4x4x1_glb", Tag::LayersWidth}, {}},
     {Form::Fleet16, Image::Lds16, Noise::Never, kByName, nullptr, one_fleet, 0, {}, fleet_16, nullptr, {"mfma16x16x4_fleet", Tag::LayersWidth}, {}},
     {Form::FleetMulti4, Image::Mfma, Noise::Never, kPublishes | kByName, multi_variant_supported, one_fleet, 0, {}, fleet_multi, nullptr, {kMfma16, Tag::HiddenLayers, "_fleet_multi4_tree", true}, {}},
+    {Form::FleetGlb16, Image::Glb16, Noise::Never, kByName, nullptr, one_fleet, 0, {}, fleet_glb16, &mppi_handle::glb16_cap, {"mfma16x16x4_fleet_glb", Tag::LayersWidth}, {}, fleet_glb16_net},
     {Form::ValuReg, Image::ThetaS, Noise::Never, 0, nullptr, one_valu_reg, 0, {}, nullptr, nullptr, {"valu_reg_lds"}, {}},
     {Form::ValuLds, Image::Theta, Noise::Never, 0, nullptr, one_valu, 0, {}, nullptr, nullptr, {"valu_lds"}, {}},
     {Form::Bf1, Image::Theta, Noise::Never, 0, nullptr, one_bf, 1, {}, nullptr, nullptr, {"basis_funcs25_valu"}, {}},
@@ -202,7 +217,13 @@ int build_image(mppi_handle *h, Form f)
   const Image id = form_desc(f).image;
   return (!image(h, id) && h->have_nn) ? upload_image(h, id) : MPPI_OK;
 }
-int prepare_fleet(mppi_handle *h, Form) { return fleet_prepare(h); }
+int prepare_fleet(mppi_handle *h, Form) { return fleet_prepare(h, false); }
+// glb16's image (built at this call) and the handle's own argument block with its layer-list descriptor
+int prepare_fleet_glb16(mppi_handle *h, Form f)
+{
+  if (int rc = build_image(h, f)) return rc;
+  return fleet_prepare(h, true);
+}
 
 enum class Model { Any, Network, Basis };
 enum class Gen { Keep, Off, On };  // multi_standalone_noise: eps from the stand-alone generator ("_gen")
@@ -276,6 +297,10 @@ const Request kRequests[] = {
     // lds16's wave / lds128's group for every layer list up to 256 wide
     {"glb16", true, Form::Glb16, Form::Glb16, kNoPref, Gen::Keep, Model::Network, glb16_shape, kGlb16Msg, 64, "glb16 form needs K to be a multiple of 64", nullptr,
      nullptr, nullptr, false, build_image},
+    // glb16's wave, image and lists; up to 64 such handles, every one with its own list and cap, share the launches of a batched solve
+    {"fleet_glb16", true, Form::FleetGlb16, Form::FleetGlb16, kNoPref, Gen::Keep, Model::Network, glb16_shape,
+     "fleet_glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer", 64, "fleet_glb16 form needs K to be a multiple of 64", nullptr,
+     nullptr, nullptr, false, prepare_fleet_glb16},
     {"glb44", true, Form::Glb44, Form::Glb44, kNoPref, Gen::Keep, Model::Network, glb44_shape, kGlb44Msg, kRolloutsPerWave,
      "glb44 form needs K to be a multiple of 16", nullptr, nullptr, nullptr, false, build_image},
     // the vector-ALU arm of the 64-wide A/B

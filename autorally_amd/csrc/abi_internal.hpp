@@ -66,6 +66,9 @@ enum class Form : int {
   FleetMulti4,                      // rollout_fleet_multi.hip: Multi4Tree's workgroup with the stand-alone generator ("multi4_tree_gen"), the argument
                                     // block read from device memory: up to 64 handles of one standard shape share a launch; by name only
                                     // ("fleet_multi4"), no gated form
+  FleetGlb16,                       // rollout_glb16.hip: glb16's wave and image with the argument block AND the layer list read from device memory: up to
+                                    // 64 handles of ANY layer lists and caps share a launch; by name only ("fleet_glb16", "fleet_glb16_r<N>"), no
+                                    // gated form
   ValuReg, ValuLds,                 // rollout_valu.hip: throughput-style vector kernels (any layer list: ValuLds)
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
   BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
@@ -202,9 +205,9 @@ struct mppi_handle {
   float *d_costs = nullptr, *d_w = nullptr;
   float *d_map = nullptr;
   mppi_abi::DeviceImage img[(int)mppi_abi::Image::Count];  // the weight images this handle has (d == nullptr: not this one)
-  mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16", "fleet_multi4", "fleet_bf": the argument block of this handle's own launches (on its own stream); only a
+  mppi_abi::ArgBlock *fleet_one = nullptr;  // "fleet16", "fleet_multi4", "fleet_bf", "fleet_glb16": the argument block of this handle's own launches (on its own stream); only a
                                  // handle that asked for the form has one
-  int glb16_cap = -1;            // "glb16_r<N>": the cap on the resident stream blocks; -1: none
+  int glb16_cap = -1;            // "glb16_r<N>", "fleet_glb16_r<N>": the cap on the resident stream blocks; -1: none
   int glb44_cap = -1;            // "glb44_r<N>": the cap on the resident stream quads; -1: none
   int fleet_bf_waves = 0;        // "fleet_bf_w<N>": the wave count of the fleet's launch forced; 0 ("fleet_bf"): fleet_bf_plan chooses
   // mppi_trace_rollouts: the records of one chunk of trace_chunk rollouts -- states [c][T][7], controls [c][T][2], step costs
@@ -333,7 +336,8 @@ bool has_noise_wave(const mppi_handle *h);
 struct FormDesc;
 using LaunchFn = hipError_t (*)(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t stream);
 using BatchFn = hipError_t (*)(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t stream);
-using FleetFn = hipError_t (*)(const mppi_handle *h, const RolloutArgs *h_inst, const RolloutArgs *d_inst, int n, hipStream_t stream);
+// hs: the n handles of the launch (a form of one list and one shape reads hs[0]); d_nets: the instances' layer lists in device memory (fleet_net)
+using FleetFn = hipError_t (*)(mppi_handle *const *hs, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *d_nets, int n, hipStream_t stream);
 enum class Noise { Never, InKernel, UnlessStandalone };  // does the kernel draw eps itself?  UnlessStandalone (oct, multi): unless the
                                                           // stand-alone generator was asked for ("_gen") or is the automatic choice
 enum class Tag { Fixed, HiddenLayers, LayersWidth, ForcedWaves };  // the reported name: stem [+ "_h%d_l%d" | "_l%d_w%d"] + suffix [+ "_gen"];
@@ -371,6 +375,9 @@ struct FormDesc {
     const char *first = nullptr, *second = nullptr;
     int k_multiple = 1;
   } ask;
+  // a fleet form whose instances bring their own layer lists: the handle's entry of the fourth section of the fleet's argument block
+  // (behind the generator descriptors); nullptr: the form has no such section
+  FleetGlbNet (*fleet_net)(const mppi_handle *h) = nullptr;
   bool has(unsigned f) const { return (flags & f) != 0; }
 };
 const FormDesc &form_desc(Form f);  // row f of the table
@@ -390,7 +397,8 @@ void fill_rollout_args(const mppi_handle *h, const float *state, float *noise, R
 int tag_min_cost(mppi_handle *h, RolloutArgs &a, hipStream_t stream);
 int launch_rollout(mppi_handle *h, const RolloutArgs &a);
 hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a);  // a handle of a fleet form solved alone
-int fleet_prepare(mppi_handle *h);  // what a handle that asks for "fleet16", "fleet_multi4" or "fleet_bf" needs of its own (fleet_one), once
+// what a handle that asks for a fleet form needs of its own (fleet_one: its argument block and, with_net, one layer-list descriptor behind it)
+int fleet_prepare(mppi_handle *h, bool with_net);
 int check_ready(mppi_handle *h);
 int launch_generator(mppi_handle *h, float *dst);
 int acquire_noise(mppi_handle *h, float **buf_out);

@@ -66,15 +66,17 @@ hipError_t arg_block_send(ArgBlock &b, size_t bytes, hipStream_t stream)
   return hipSuccess;
 }
 
-// The argument blocks of a fleet form's batched solve ("fleet16", "fleet_multi4"): ONE block per device beside the device's batch stream, shared by every
+// The argument blocks of a fleet form's batched solve ("fleet16", "fleet_multi4", "fleet_bf", "fleet_glb16"): ONE block per device beside the device's batch stream, shared by every
 // fleet on the device and never destroyed -- per iteration the rollout, tail and generator blocks of up to kMaxFleet instances,
-// packed for the fleet's n (FleetBlock: abi_internal.hpp).  A batched DDP pass and a batched nominal replay (abi_host.hip) send their
+// packed for the fleet's n, and behind them -- for a form whose instances bring their own layer lists (FormDesc::fleet_net) -- the
+// instances' list descriptors (FleetBlock: abi_internal.hpp).  A batched DDP pass and a batched nominal replay (abi_host.hip) send their
 // instances' blocks through it too.
 static FleetBlock g_fleet[64];
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 static size_t fleet_tail_offset(int n) { return align16(sizeof(RolloutArgs) * (size_t)n); }
 static size_t fleet_noise_offset(int n) { return align16(fleet_tail_offset(n) + solve_tail_fleet_arg_bytes() * (size_t)n); }
-static size_t fleet_bytes(int n) { return align16(fleet_noise_offset(n) + sizeof(NoiseFleetDesc) * (size_t)n); }
+static size_t fleet_net_offset(int n) { return align16(fleet_noise_offset(n) + sizeof(NoiseFleetDesc) * (size_t)n); }
+static size_t fleet_bytes(int n, bool with_nets) { return with_nets ? align16(fleet_net_offset(n) + sizeof(FleetGlbNet) * (size_t)n) : fleet_net_offset(n); }
 FleetBlock *fleet_block(int device)
 {
   if (device < 0 || device >= 64) return nullptr;
@@ -82,21 +84,30 @@ FleetBlock *fleet_block(int device)
   FleetBlock &fb = g_fleet[device];
   // (the largest of the three uses: a batched solve's blocks, a batched DDP pass's, a batched nominal replay's)
   if (!fb.ready)
-    fb.ready = arg_block_create(fb.args, std::max({fleet_bytes(kMaxFleet), sizeof(DdpFleetArgs) * (size_t)kMaxFleet,
+    fb.ready = arg_block_create(fb.args, std::max({fleet_bytes(kMaxFleet, true), sizeof(DdpFleetArgs) * (size_t)kMaxFleet,
                                                    sizeof(NominalFleetArgs) * (size_t)kMaxFleet})) == hipSuccess;
   return fb.ready ? &fb : nullptr;
 }
 
-int fleet_prepare(mppi_handle *h)
+// a handle's own one-instance block: the rollout arguments and, for a form with list descriptors, one of them behind
+static size_t fleet_one_net_offset() { return align16(sizeof(RolloutArgs)); }
+static size_t fleet_one_bytes(bool with_net) { return with_net ? fleet_one_net_offset() + sizeof(FleetGlbNet) : sizeof(RolloutArgs); }
+
+int fleet_prepare(mppi_handle *h, bool with_net)
 {
-  if (h->fleet_one) return MPPI_OK;
+  if (h->fleet_one && h->fleet_one->slot >= fleet_one_bytes(with_net)) return MPPI_OK;
   HIPCHK(h, ensure_device(h->cfg.device));
   ArgBlock *b = new (std::nothrow) ArgBlock;
   if (!b) return fail(h, MPPI_ERR_HIP, "out of memory");
-  const hipError_t e = arg_block_create(*b, sizeof(RolloutArgs));
+  const hipError_t e = arg_block_create(*b, fleet_one_bytes(with_net));
   if (e != hipSuccess) {
     delete b;
     return fail(h, MPPI_ERR_HIP, "fleet form: argument block", e);
+  }
+  if (h->fleet_one) {  // the block of another fleet form, too small for the descriptor: nothing of it is in flight any more
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    arg_block_destroy(*h->fleet_one);
+    delete h->fleet_one;
   }
   h->fleet_one = b;
   return MPPI_OK;
@@ -108,9 +119,16 @@ hipError_t launch_rollout_fleet_one(mppi_handle *h, const RolloutArgs &a)
   if (!h->fleet_one || !form_desc(h->forced).fleet) return hipErrorInvalidValue;
   unsigned char *host = nullptr;
   if (hipError_t e = arg_block_stage(*h->fleet_one, &host); e != hipSuccess) return e;
+  const FormDesc &d = form_desc(h->forced);
   memcpy(host, &a, sizeof(RolloutArgs));
-  if (hipError_t e = arg_block_send(*h->fleet_one, sizeof(RolloutArgs), h->stream); e != hipSuccess) return e;
-  return form_desc(h->forced).fleet(h, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), 1, h->stream);
+  if (d.fleet_net) {
+    const FleetGlbNet net = d.fleet_net(h);
+    memcpy(host + fleet_one_net_offset(), &net, sizeof(net));
+  }
+  if (hipError_t e = arg_block_send(*h->fleet_one, fleet_one_bytes(d.fleet_net != nullptr), h->stream); e != hipSuccess) return e;
+  mppi_handle *const hs[1] = {h};
+  return d.fleet(hs, &a, reinterpret_cast<const RolloutArgs *>(h->fleet_one->d), reinterpret_cast<const FleetGlbNet *>(h->fleet_one->d + fleet_one_net_offset()), 1,
+                 h->stream);
 }
 
 void fill_cost_args(const mppi_handle *h, CostArgs &c)
@@ -1081,8 +1099,9 @@ static bool batch_together(mppi_handle *const *hs, int n)
   return together && waves <= h0->num_simds;  // every wave of every group still gets a SIMD of its own
 }
 
-// The fleet: 2..kMaxFleet handles ALL forced to "fleet16", ALL to "fleet_multi4" or ALL to "fleet_bf" (a mixed set is solved handle by
-// handle) on one device with one whole layer list (the basis-function model: one forced wave count instead), one num_iters and one pair (affine
+// The fleet: 2..kMaxFleet handles ALL forced to "fleet16", ALL to "fleet_multi4", ALL to "fleet_bf" or ALL to "fleet_glb16" (a mixed set is
+// solved handle by handle) on one device with one whole layer list (the basis-function model: one forced wave count instead; "fleet_glb16": any
+// lists and caps -- they are data of its launch, FormDesc::fleet_net), one num_iters and one pair (affine
 // costmap transform, control cost needed) -- one kernel instance serves the launch, and a superset kernel would not keep every
 // instance's bits (batch_together) -- K <= 4096 each (the one-workgroup-per-row tail), no stage timing, capture or prefetched
 // draws, every handle ready.  Such a set shares its launches: per iteration one generator, one rollout and one tail launch on
@@ -1098,7 +1117,7 @@ static bool fleet_together(mppi_handle *const *hs, int n)
     if (h->basis != h0->basis || !form_desc(h0->forced).fleet || h->forced != h0->forced || h->fleet_one == nullptr || h->cfg.device != h0->cfg.device || h->cfg.num_iters != h0->cfg.num_iters) return false;
     if (h->basis) {  // "fleet_bf": one wave count for the launch, forced on all or on none
       if (h->fleet_bf_waves != h0->fleet_bf_waves) return false;
-    } else {
+    } else if (!form_desc(h0->forced).fleet_net) {
       if (h->net.n_layers != h0->net.n_layers) return false;
       for (int l = 0; l < h->net.n_layers; l++)
         if (h->net.layers[l] != h0->net.layers[l]) return false;
@@ -1157,6 +1176,7 @@ static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
   std::lock_guard<std::mutex> lk(fb->mu);
   if (int rc = begin_solves(hs, n, S, true)) return distrust(hs, n, rc);
   const int iters = h0->cfg.num_iters;
+  const FormDesc &fd = form_desc(h0->forced);
   TailLaunch tl[kMaxFleet];
   for (int it = 0; it < iters; it++) {
     unsigned char *host = nullptr;
@@ -1164,15 +1184,19 @@ static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
     if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "fleet argument block", e));
     RolloutArgs *ra = reinterpret_cast<RolloutArgs *>(host);
     NoiseFleetDesc *nd = reinterpret_cast<NoiseFleetDesc *>(host + fleet_noise_offset(n));
+    if (fd.fleet_net) {  // every instance's layer list and resident blocks: the block's fourth section
+      FleetGlbNet *nets = reinterpret_cast<FleetGlbNet *>(host + fleet_net_offset(n));
+      for (int i = 0; i < n; i++) nets[i] = fd.fleet_net(hs[i]);
+    }
     for (int i = 0; i < n; i++)
       if (int rc = solve_step(hs[i], states + (size_t)MPPI_STATE_DIM * i, it, it == iters - 1, S, Eps::Fleet, ra[i], tl[i], &nd[i]))
         return distrust(hs, n, rc);
     fill_solve_tail_fleet(host + fleet_tail_offset(n), tl, n);
-    e = arg_block_send(fb->args, fleet_bytes(n), S);
+    e = arg_block_send(fb->args, fleet_bytes(n, fd.fleet_net != nullptr), S);
     const unsigned char *dev = fb->args.d;
     if (e == hipSuccess) e = launch_noise_fleet(nd, reinterpret_cast<const NoiseFleetDesc *>(dev + fleet_noise_offset(n)), n, S);
     if (e == hipSuccess)
-      e = form_desc(h0->forced).fleet(h0, ra, reinterpret_cast<const RolloutArgs *>(dev), n, S);
+      e = fd.fleet(hs, ra, reinterpret_cast<const RolloutArgs *>(dev), reinterpret_cast<const FleetGlbNet *>(dev + fleet_net_offset(n)), n, S);
     if (e == hipSuccess) e = launch_solve_tail_fleet(tl, n, dev + fleet_tail_offset(n), S);
     if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "fleet launch", e));
     for (int i = 0; i < n; i++) {
@@ -1260,9 +1284,9 @@ int mppi_compute_control_batch_async(mppi_handle *const *hs, const float *states
     }
   }
   mppi_handle *h0 = hs[0];
-  if (!together && fleet_together(hs, n)) return enqueue_fleet(hs, states, n);  // the "fleet16" / "fleet_multi4" forms: 2..64 handles, three launches
+  if (!together && fleet_together(hs, n)) return enqueue_fleet(hs, states, n);  // the fleet forms: 2..64 handles, three launches
   if (!together && n >= 2) {
-    // a set of "fleet16" (or of "fleet_multi4") handles with one that is not ready: its error before any of the others has moved
+    // a set of handles of one fleet form with one that is not ready: its error before any of the others has moved
     bool all_fleet = form_desc(h0->forced).fleet != nullptr;
     for (int i = 0; i < n; i++) all_fleet = all_fleet && hs[i]->forced == h0->forced;
     for (int i = 0; i < n && all_fleet; i++)

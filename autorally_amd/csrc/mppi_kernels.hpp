@@ -236,6 +236,25 @@ size_t glb16_lds_limit();
 // threads per workgroup for K rollouts on a device of `cus` CUs: the smaller of 256 / 512 with every workgroup resident at once, else 512
 int glb16_block_threads(const NetDesc &net, int K, int cus, int cap);
 hipError_t launch_rollout_glb16(const NetDesc &net, const RolloutArgs &a, int cus, int cap, hipStream_t stream);
+// ... and for up to kMaxFleet independent controllers, every one with its OWN layer list and cap, in one launch ("fleet_glb16") --
+// grid (workgroups of the largest instance, instances); the instances' argument blocks and their layer lists are two arrays in
+// device memory
+struct FleetGlbNet {
+  Lds16Net net;  // glb16_net_of the instance's list
+  int R;         // its resident stream blocks: glb16_resident_blocks(list, cap)
+};
+FleetGlbNet fleet_glb16_net_of(const NetDesc &net, int cap);
+struct FleetGlb16Plan {
+  int tiles;                    // the instance of the launch: 16 if any list is wider than 128, else 8
+  int threads, grid_x, grid_y;  // one workgroup size for the launch; all zero: no launch (a list glb16 refuses, n outside 1..kMaxFleet, a K below 16)
+  size_t lds_bytes;             // a workgroup's dynamic LDS: the largest glb16_lds_bytes of the instances
+};
+// Ks: the instances' rollouts; threads: wave16_image_block_threads' rule on all workgroups of the fleet (n = 1: glb16_block_threads)
+FleetGlb16Plan fleet_glb16_plan(const NetDesc *nets, const int *caps, const int *Ks, int n, int cus);
+// h_inst: the n argument blocks on the host (K and the cost flags are read there); d_inst: the same blocks in device memory;
+// d_nets: fleet_glb16_net_of(nets[i], caps[i]) of every instance in device memory
+hipError_t launch_rollout_fleet_glb16(const NetDesc *nets, const int *caps, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *d_nets,
+                                      int n, int cus, hipStream_t stream);
 
 // rollout_glb44.hip: lds128's group (m44_group.hpp) for EVERY layer list 6 -> hidden widths 1..256 -> 4 (3 <= n_layers <= 8): a hidden
 // layer is one to four halves of 64 neurons with an accumulator each, its inputs one to four transposed activation sets; the

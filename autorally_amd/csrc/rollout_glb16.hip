@@ -17,6 +17,7 @@
 //     neuron's activation SET to 0, the bias after the chain -- bit-identical to "valu_lds" (oracle mode 1) and, on the lists
 //     lds16 serves, to "lds16", for every R;
 //   * instances: MTM = 8 tiles (lists up to 128 wide) and MTM = 16 (up to 256 wide: 64 activation and 64 accumulator registers).
+// Below the launcher: the same kernel for a FLEET whose instances bring their own layer lists ("fleet_glb16").
 #include "wave16_image.hpp"
 #include "wave16_step.hpp"
 
@@ -141,6 +142,111 @@ hipError_t launch_rollout_glb16(const NetDesc &net, const RolloutArgs &a, int cu
     if (glb16_tiles_max(net) == 8)
       return launch_wave16_image_instance<&rollout_glb16_kernel<8, AF, CT, kGlb16MaxThreads8>>(grid, block, lds, kGlb16MaxBytes, stream, a, nd, R);
     return launch_wave16_image_instance<&rollout_glb16_kernel<16, AF, CT, kGlb16MaxThreads16>>(grid, block, lds, kGlb16MaxBytes, stream, a, nd, R);
+  });
+}
+
+// ---- "fleet_glb16": up to kMaxFleet independent controllers, EVERY ONE WITH ITS OWN LAYER LIST, in one launch ----
+// The wave reads the layer list only as wave-uniform data and MTM only bounds the tile recursion and the register arrays, so an
+// instance of the launch may bring its own list: workgroup (x, y) runs workgroup x of inst[y] on the list and the resident blocks
+// of nets[y].  Both arrays are in DEVICE MEMORY, read-only behind __restrict__ pointers at a workgroup-uniform index: the block and
+// the list arrive in scalar registers as kernel arguments do.  The list is used through a REFERENCE into the array -- a local copy
+// of the struct is indexed at run time (net.boff[n_w - 1]) and would go to private memory.  One instance of the kernel serves a
+// launch: 16 tiles if any list of the fleet is wider than 128, else 8; a narrower list leaves the upper tiles by the wave-uniform
+// exits it leaves them by in a launch of its own, with the same bits.
+
+FleetGlbNet fleet_glb16_net_of(const NetDesc &net, int cap)
+{
+  FleetGlbNet d{};
+  if (!glb16_supported(net)) return d;
+  d.net = glb16_net_of(net);
+  d.R = glb16_resident_blocks(net, cap);
+  return d;
+}
+
+// The plan of a launch: every instance keeps the R of a launch of its own (glb16_resident_blocks); the launch has ONE dynamic-LDS
+// size, the largest of the instances', and ONE workgroup size, wave16_image_block_threads' rule with that LDS on the workgroups
+// of the whole fleet (n = 1: glb16's own plan).  All zero for n outside 1..kMaxFleet, a K below one wave or a list glb16 refuses.
+FleetGlb16Plan fleet_glb16_plan(const NetDesc *nets, const int *caps, const int *Ks, int n, int cus)
+{
+  FleetGlb16Plan p{};
+  if (!nets || !caps || !Ks || n < 1 || n > kMaxFleet || cus < 1) return p;
+  int kmax = 0, tiles = 8;
+  size_t lds = 0;
+  for (int i = 0; i < n; i++) {
+    if (!glb16_supported(nets[i]) || Ks[i] < kRolloutsPerWave) return p;
+    kmax = Ks[i] > kmax ? Ks[i] : kmax;
+    tiles = glb16_tiles_max(nets[i]) > tiles ? 16 : tiles;
+    const size_t b = glb16_lds_bytes(nets[i], caps[i]);
+    lds = b > lds ? b : lds;
+  }
+  const bool wide = tiles == 16;
+  p.tiles = tiles;
+  p.lds_bytes = lds;
+  p.threads = wave16_image_block_threads(Ks, n, cus, lds, kGlb16MaxBytes, wide ? kGlb16WavesPerSimd16 : kGlb16WavesPerSimd8,
+                                         wide ? kGlb16MaxThreads16 : kGlb16MaxThreads8);
+  const int wpb = p.threads / 64;
+  p.grid_x = (kmax / kRolloutsPerWave + wpb - 1) / wpb;
+  p.grid_y = n;
+  return p;
+}
+
+template <int MTM, bool AFFINE, bool CTRL, int THREADS>
+__global__ __launch_bounds__(THREADS) void rollout_fleet_glb16_kernel(const RolloutArgs *__restrict__ inst, const FleetGlbNet *__restrict__ nets, const int n)
+{
+  if ((int)blockIdx.y >= n) return;
+  RolloutArgs a = inst[blockIdx.y];  // workgroup-uniform, read-only: scalar loads
+  // the pointers it holds are global memory, as those of a kernel argument are known to be
+  a.U = load_global_ptr(inst[blockIdx.y].U);
+  a.noise = load_global_ptr(inst[blockIdx.y].noise);
+  a.costs = load_global_ptr(inst[blockIdx.y].costs);
+  a.wpack = load_global_ptr(inst[blockIdx.y].wpack);
+  a.inv_t = load_global_ptr(inst[blockIdx.y].inv_t);
+  a.cost.map = load_global_ptr(inst[blockIdx.y].cost.map);
+  // no wave of this workgroup belongs to the instance (a smaller K than the largest): nothing staged, no barrier
+  if ((int)(blockIdx.x * (blockDim.x >> 6)) * kRolloutsPerWave >= a.K) return;
+  const Lds16Net &net = nets[blockIdx.y].net;  // a reference: see above
+  const int R = __builtin_amdgcn_readfirstlane(nets[blockIdx.y].R);
+  f32x4 *const img = reinterpret_cast<f32x4 *>(glb16_smem);
+  const f32x4 *const src = reinterpret_cast<const f32x4 *>(a.wpack);
+  {  // THIS instance's head and the first R blocks of its stream into LDS
+    const int q_end = net.off[1] + 64 * R;
+    for (int q = threadIdx.x; q < q_end; q += blockDim.x) img[q] = src[q];
+  }
+  __syncthreads();  // the only barrier
+  Wave16ImageNet<MTM, Glb16Stream> nn(img, src, net, R);
+  wave16_rollout<AFFINE, CTRL>(a, nn);  // the step: wave16_step.hpp (its absent waves of the last workgroup leave there)
+}
+
+template <auto KERN>
+static hipError_t fleet_glb16_launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const RolloutArgs *d_inst, const FleetGlbNet *d_nets, int n)
+{
+  if (hipError_t e = raise_lds_limit_once<KERN>(kGlb16MaxBytes); e != hipSuccess) return e;
+  MPPI_LAUNCH_ROLLOUT(KERN, grid, block, lds, stream, d_inst, d_nets, n);
+  return hipGetLastError();
+}
+
+// nets / caps: every instance's layer list and the cap on its resident blocks (< 0: none); h_inst: the host's copy of the n argument
+// blocks (K and the cost flags are read there); d_inst: the same blocks in device memory and d_nets: fleet_glb16_net_of(nets[i],
+// caps[i]) of every instance there, both complete once `stream` reaches the launch.  Every instance: one pair (affine, control cost).
+hipError_t launch_rollout_fleet_glb16(const NetDesc *nets, const int *caps, const RolloutArgs *h_inst, const RolloutArgs *d_inst, const FleetGlbNet *d_nets,
+                                      int n, int cus, hipStream_t stream)
+{
+  if (!nets || !caps || !h_inst || !d_inst || !d_nets || n < 1 || n > kMaxFleet) return hipErrorInvalidValue;
+  int Ks[kMaxFleet];
+  for (int i = 0; i < n; i++) {
+    const RolloutArgs &a = h_inst[i];
+    if (a.K % 64 != 0 || a.gate != nullptr || a.cost.affine != h_inst[0].cost.affine || a.cost.need_control_cost != h_inst[0].cost.need_control_cost)
+      return hipErrorInvalidValue;
+    Ks[i] = a.K;
+  }
+  const FleetGlb16Plan p = fleet_glb16_plan(nets, caps, Ks, n, cus);
+  if (p.threads == 0 || p.lds_bytes > kGlb16MaxBytes) return hipErrorInvalidValue;
+  const dim3 grid(p.grid_x, p.grid_y), block(p.threads);
+  return dispatch_cost_flags(h_inst[0].cost.affine != 0, h_inst[0].cost.need_control_cost != 0, [&](auto af, auto ct) {
+    constexpr bool AF = decltype(af)::value, CT = decltype(ct)::value;
+    if (p.tiles == 8)
+      return fleet_glb16_launch<&rollout_fleet_glb16_kernel<8, AF, CT, kGlb16MaxThreads8>>(grid, block, p.lds_bytes, stream, d_inst, d_nets, n);
+    return fleet_glb16_launch<&rollout_fleet_glb16_kernel<16, AF, CT, kGlb16MaxThreads16>>(grid, block, p.lds_bytes, stream, d_inst, d_nets, n);
   });
 }
 

@@ -69,6 +69,10 @@ extern "C" {
  *    workgroups and the bits of the basis-function model's own kernels with the argument block read from device memory; 2..64
  *    handles forced to it share the launches of mppi_compute_control_batch as "fleet16" handles do; no new export, no gated
  *    form, the automatic choice does not change. */
+/*    (still 5) + rollout variant "fleet_glb16" (and "fleet_glb16_r<N>"), name "mfma16x16x4_fleet_glb_l<N>_w<W>": "glb16"'s wavefront,
+ *    image and lists with the argument block AND the layer list read from device memory; 2..64 handles forced to it -- of ANY
+ *    layer lists and caps -- share the launches of mppi_compute_control_batch as "fleet16" handles do; no new export, no gated
+ *    form, the automatic choice does not change. */
 /*    (still 5) + mppi_compute_feedback_gains_batch, mppi_debug_ddp_info, mppi_debug_device_tanhf (the DDP feedback gains of a fleet
  *    in one launch; compatible additions, the single and the pair call are unchanged). */
 /*    (still 5) + mppi_nominal_traj_batch, mppi_debug_nominal_info (the nominal trajectories of a fleet in one launch; compatible
@@ -233,6 +237,10 @@ int mppi_synchronize(mppi_handle *h);
  * "fleet_multi4" (one of 6-32x2-4, 6-32x4-4, 6-64x2-4); a set that mixes "fleet16" and "fleet_multi4" handles is n per-handle solves.
  * The "fleet_bf" variant (the basis-function model): the same rule and the same three launches for 2 <= n <= 64 handles that are
  * ALL forced to "fleet_bf", or all to the same "fleet_bf_w<N>"; the layer list plays no part, the forced wave count must agree.
+ * The "fleet_glb16" variant: the same three launches for 2 <= n <= 64 handles that are ALL forced to "fleet_glb16" (with or without
+ * "_r<N>"); the handles' layer lists and caps need NOT agree -- every instance of the launch brings its own -- and everything else
+ * of the rule stands (one device, one num_iters, one pair of cost flags, K <= 4096 each, no timing, capture, prefetched draws or
+ * armed handle, all ready); a set that mixes it with any other form is n per-handle solves.
  * mppi_debug_launch_info tells which it was.  Either way every
  * handle's results are bit for bit those of its own mppi_compute_control, collected per handle with
  * mppi_synchronize / mppi_get_results.  The blocking form waits for all of them. */
@@ -467,6 +475,14 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     measurement knob, same bits for every N); by name only; the device image is built at this call and held only by handles
  *     that asked for the form; NO gated form and no batched launch, as "lds16"; MPPI_ERR_UNSUPPORTED for the basis-function
  *     model and a list without a hidden layer, MPPI_ERR_INVALID ("unknown variant") for a malformed suffix
+ *     "fleet_glb16" mfma16x16x4_fleet_glb_l<hidden layers>_w<widest hidden layer> (of the handle's OWN list): "glb16"'s wavefront, image,
+ *     residency rule and lists with the argument block and the layer list read from device memory, so that up to 64 handles of
+ *     ANY layer lists share ONE rollout launch (mppi_compute_control_batch: the sharing rule is stated there); the bits of
+ *     "valu_lds", "glb16" and, where it takes the list, "lds16".  One kernel instance per launch: 16 tiles per layer if any handle of
+ *     the launch has a hidden layer wider than 128, else 8 (a narrower list skips the upper tiles: same bits); every handle keeps
+ *     the R of a launch of its own, the launch's dynamic LDS is the largest of the handles'.  "fleet_glb16_r<N>" caps the handle's
+ *     R at N as "glb16_r<N>" does (same bits for every N; the caps of a launch need not agree).  NO gated form; a handle solved
+ *     alone runs the same kernel with one instance; by name only; the refusals of "glb16"
  *     "glb44" mfma4x4x1_glb_l<hidden layers>_w<widest hidden layer>: "lds128"'s group (512 threads per 16 rollouts, four dynamics
  *     waves on v_mfma_f32_4x4x1 + the riders) for EVERY layer list of the network model (3 <= n_layers <= 8, hidden widths 1..256): a
  *     layer is one to four halves of 64 neurons with an accumulator each, the reference's order (the bits of "valu_lds", "lds128" and

@@ -27,7 +27,14 @@ against n single calls on one host thread and against the pair entry with mppi_s
     python tools/fleet_time.py --nominal [--T 100] [--ticks 200] [--net ...]
 
 The nominal trajectories of the fleet (n = 2, 4, 16, 64): mppi_nominal_traj_batch -- one launch of nominal_fleet_kernel -- against
-n mppi_nominal_traj calls on one host thread and n / 2 mppi_nominal_traj_pair calls with mppi_set_host_threads(2)."""
+n mppi_nominal_traj calls on one host thread and n / 2 mppi_nominal_traj_pair calls with mppi_set_host_threads(2).
+
+    python tools/fleet_time.py --mixed 6-32-32-4 6-64-64-64-64-4 6-129-4 6-256-256-4 [--n 4 16 64] [--K 1920] [--T 100] [--ways abcdA]
+
+A fleet whose handles cycle through the given layer lists (handle i has list i mod the number of lists), one row per n, every
+column of a row in one process: (a) every handle forced to "fleet_glb16" -- one launch for the mixed fleet --, (b) the same handles
+forced to "glb16", handle by handle, (c) "auto", (d) "fleet16" (one list of hidden widths up to 128 only; else not available),
+(A) "fleet_glb16" a second time: the A/A spread of the visit."""
 import argparse
 import json
 import os
@@ -43,6 +50,7 @@ if ROOT not in sys.path:
 WAYS = (("d", "fleet_multi4"), ("a", "fleet16"), ("b", "lds16"), ("c", "auto"), ("A", "fleet16"))
 BF_WAYS = (("f", "fleet_bf"), ("1", "fleet_bf_w1"), ("2", "fleet_bf_w2"), ("3", "fleet_bf_w3"), ("c", "auto"), ("F", "fleet_bf"),
            ("p", "fused"), ("q", "quad"), ("r", "bf3"))
+MIXED_WAYS = (("a", "fleet_glb16"), ("b", "glb16"), ("c", "auto"), ("d", "fleet16"), ("A", "fleet_glb16"))
 BF = "bf"  # in place of a layer list: the basis-function model
 
 
@@ -53,15 +61,18 @@ def bf_W():
 
 def fleet(net, variant, n, K, T):
     """n solvers on n distinct oval instances (one map: the instances differ in the start state, the model's scale, the cost
-    parameters and the seed), forced to `variant`, and their states."""
+    parameters and the seed), forced to `variant`, and their states.  net: one layer list, BF, or a tuple of layer lists the
+    handles cycle through (--mixed)."""
     from autorally_amd import capi
     from autorally_amd import synthetic as S
+    mixed = net != BF and isinstance(net[0], (list, tuple))
     if net == BF:
-        base = S.make_config(K, T, track="oval", opt_stride=1, bf_W=bf_W())
+        bases = [S.make_config(K, T, track="oval", opt_stride=1, bf_W=bf_W())]
     else:
-        base = S.make_config(K, T, layers=list(net), track="oval", opt_stride=1)
+        bases = [S.make_config(K, T, layers=list(l), track="oval", opt_stride=1) for l in (net if mixed else [net])]
     sols, states = [], []
     for i in range(n):
+        base = bases[i % len(bases)]
         st = np.array(base["start_state"], np.float32)
         st[0] += np.float32(0.4 * i)
         st[4] += np.float32(0.1 * (i % 5))
@@ -124,6 +135,26 @@ def table(nets, n=16, K=1920, T=100, ticks=200, warm=20, ways="abc"):
         print("FLEET n=%d K=%d T=%d net=%s: (a) fleet16 %.4f ms [%d per launch]  (b) lds16 %.4f ms  (c) auto (%s) %.4f ms;  b/a %.2f  c/a %.2f" % (
             n, K, T, row["net"], row["a_ms"], row["a_instances"], row["b_ms"], row["c_form"], row["c_ms"], row["b_ms"] / row["a_ms"],
             row["c_ms"] / row["a_ms"]), flush=True)
+    return rows
+
+
+def mixed_table(nets, ns=(4, 16, 64), K=1920, T=100, ticks=200, warm=20, ways="abcdA"):
+    """One row per fleet size for handles that cycle through `nets`: every way of MIXED_WAYS named in `ways`, in one process."""
+    rows = []
+    for n in ns:
+        row = {"nets": ["-".join(map(str, l)) for l in nets], "n": n, "K": K, "T": T}
+        for key, variant in MIXED_WAYS:
+            if key not in ways:
+                continue
+            if variant == "fleet16" and len(nets) != 1:  # a form of one layer list
+                ms, inst, name = None, 0, "not available"
+            else:
+                ms, inst, name = tick_ms(tuple(tuple(l) for l in nets), variant, n, K, T, ticks, warm)
+            row[key + "_ms"], row[key + "_instances"], row[key + "_form"] = ms, inst, name
+        rows.append(row)
+        print("FLEET MIXED n=%d K=%d T=%d nets=%s: %s" % (n, K, T, ",".join(row["nets"]), "  ".join(
+            "(%s) %s %s [%d per launch]" % (key, variant, "n/a" if row[key + "_ms"] is None else "%.4f ms" % row[key + "_ms"], row[key + "_instances"])
+            for key, variant in MIXED_WAYS if key + "_ms" in row)), flush=True)
     return rows
 
 
@@ -271,7 +302,8 @@ def nominal_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=16)
+    ap.add_argument("--n", type=int, nargs="*", default=None, help="handles (default 16; --mixed: 4 16 64, one row each)")
+    ap.add_argument("--mixed", nargs="+", default=None, help="the layer lists the handles of a \"fleet_glb16\" fleet cycle through, ways abcdA")
     ap.add_argument("--K", type=int, default=None, help="rollouts per handle (default 1920; --model bf: 2560)")
     ap.add_argument("--model", default="nn", choices=["nn", "bf"], help="bf: the basis-function model, ways f123cF (and p, q, r)")
     ap.add_argument("--T", type=int, default=100)
@@ -286,6 +318,11 @@ def main():
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
+    parse = lambda names: [[int(x) for x in s.split("-")] for s in names]  # noqa: E731
+    if a.mixed:
+        print(json.dumps(mixed_table(parse(a.mixed), a.n or (4, 16, 64), a.K or 1920, a.T, a.ticks, a.warm, a.ways or "abcdA")))
+        return
+    a.n = a.n[0] if a.n else 16
     if a.nominal:
         print(json.dumps(nominal_table([[int(x) for x in s.split("-")] for s in a.net], T=a.T, calls=a.ticks)))
         return
