@@ -69,6 +69,7 @@ SYMBOLS = [
     "mppi_trace_rollouts", "mppi_top_rollouts",
     "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
     "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
+    "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -82,7 +83,8 @@ ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost", "mppi_arm
 # added to version 5 as compatible additions: an older version-5 library (a kernel A/B through MPPI_LIB_PATH) lacks them
 UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_top_rollouts",
                        "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
-                       "mppi_nominal_traj_batch", "mppi_debug_nominal_info")
+                       "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
+                       "mppi_trace_rollouts_batch", "mppi_debug_trace_info")
 
 _lib = None
 
@@ -190,6 +192,11 @@ def lib():
             fpp = C.POINTER(fp)
             L.mppi_nominal_traj_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
             L.mppi_debug_nominal_info.argtypes = [hp, C.POINTER(C.c_int)]
+        if hasattr(L, "mppi_trace_rollouts_batch"):  # added without a version step, like mppi_debug_launch_info
+            ip, fpp = C.POINTER(C.c_int), C.POINTER(fp)
+            ipp = C.POINTER(ip)
+            L.mppi_trace_rollouts_batch.argtypes = [C.POINTER(hp), C.c_int, ip, ipp, ipp, fpp, fpp, fpp, fpp, ipp]
+            L.mppi_debug_trace_info.argtypes = [hp, C.POINTER(C.c_int)]
         for s in SYMBOLS:  # every declared symbol of the library's ABI version must be there
             if (v2 or s not in ABI2_SYMBOLS) and (v3 or s not in ABI3_SYMBOLS) and (v4 or s not in ABI4_SYMBOLS) and \
                     (v5 or s not in ABI5_SYMBOLS) and s not in UNVERSIONED_SYMBOLS:
@@ -437,6 +444,12 @@ class Solver:
         self._ck(self.L.mppi_top_rollouts(self.h, int(n), ks.ctypes.data_as(C.POINTER(C.c_int))))
         return ks
 
+    def debug_trace_info(self):
+        """mppi_debug_trace_info: 1 if the handle's last trace ran in the fleet's kernels, 0 if in a launch of its own."""
+        on = C.c_int(-1)
+        self._ck(self.L.mppi_debug_trace_info(self.h, C.byref(on)))
+        return on.value
+
     def rollout_only(self, state):
         costs = np.zeros(self.K, dtype=np.float32)
         self._ck(self.L.mppi_rollout_only(self.h, _fp(_f32(state, (7,))), _fp(costs)))
@@ -644,6 +657,46 @@ def nominal_traj_batch(solvers, states):
     if rc != OK:
         raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
     return out
+
+
+def trace_rollouts_batch(solvers, counts, ks=None, with_costs=True, outputs=None):
+    """mppi_trace_rollouts_batch: the traces of several Solver objects in one call (one launch per 64 where the library can share
+    it).  counts[i]: rollouts of solver i; ks: None, or one entry per solver -- its indices, or None for its counts[i] largest
+    weights (mppi_top_rollouts' order).  Returns one dict per solver as Solver.trace_rollouts does, plus ks [counts[i]]: the
+    indices that were traced.  outputs: the dicts to fill (a caller that checks what a refused call wrote); raises MppiError with
+    every handle's message (an empty fleet: MPPI_ERR_INVALID, as the library answers n_handles < 1)."""
+    n = len(solvers)
+    if n < 1 or len(counts) != n or (ks is not None and len(ks) != n):
+        raise MppiError(ERR_INVALID, "trace_rollouts_batch: %d solvers, %d counts" % (n, len(counts)))
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+    cn = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if outputs is None:
+        outputs = []
+        for s, c in zip(solvers, cn):
+            c = max(int(c), 0)
+            o = dict(ks=np.zeros(c, np.int32), states=np.zeros((c, s.T, 7), np.float32), controls=np.zeros((c, s.T, 2), np.float32),
+                     first_crash=np.zeros(c, np.int32))
+            if with_costs:
+                o.update(step_costs=np.zeros((c, s.T), np.float32), costs=np.zeros(c, np.float32))
+            outputs.append(o)
+    keep, ksp = [], None
+    if ks is not None:
+        ksp = (ip * n)()
+        for i, k in enumerate(ks):
+            if k is not None:
+                keep.append(np.ascontiguousarray(k, dtype=np.int32).reshape(-1))
+                ksp[i] = keep[-1].ctypes.data_as(ip)
+
+    def arr(key, ptr):
+        if key not in outputs[0]:
+            return None
+        return (ptr * n)(*[o[key].ctypes.data_as(ptr) for o in outputs])
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    rc = solvers[0].L.mppi_trace_rollouts_batch(hs, n, cn.ctypes.data_as(ip), ksp, arr("ks", ip), arr("states", fp), arr("controls", fp),
+                                                arr("step_costs", fp), arr("costs", fp), arr("first_crash", ip))
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
+    return outputs
 
 
 def nominal_traj_pair(sol_a, state_a, sol_b, state_b):

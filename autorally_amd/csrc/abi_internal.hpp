@@ -3,7 +3,7 @@
 // (selection table, names); abi_pack.hip: weight images and generator tables; abi_solve.hip: the solve pipeline (noise,
 // rollout + tail launches, result polling, batched solves); abi_host.hip: the host-side halves of a tick (nominal replays,
 // DDP feedback gains, the helper thread, the batched DDP pass and the batched nominal replay of a fleet on the device); abi_trace.hip: chosen rollouts of the last
-// solve replayed with their records.
+// solve replayed with their records, for one handle or a whole fleet.
 #pragma once
 // mppi_abi.hip -- host side of libmppi_hip.so: the C ABI of include/mppi_hip.h.
 //
@@ -159,6 +159,7 @@ struct mppi_handle {
   bool have_ddp = false;
   int ddp_on_device = 0;  // the last DDP pass ran in ddp_fleet_kernel (mppi_compute_feedback_gains_batch), not on the host
   int nominal_on_device = 0;  // the last nominal replay ran in nominal_fleet_kernel (mppi_nominal_traj_batch), not on the host
+  int trace_on_device = 0;  // the last trace ran in the fleet's kernels (mppi_trace_rollouts_batch), not in a launch of the handle's own
   hipStream_t batch_s = nullptr;  // the device's batch stream, looked up once (mppi_compute_control_batch)
   unsigned *d_counter = nullptr;  // [1 + T] arrival counters of the tail kernel
   float *d_part = nullptr;        // [T][K/64][2] chain results of the tail kernel when K > 4096
@@ -444,5 +445,110 @@ constexpr int kTraceChunk = 1024;  // rollouts per launch of mppi_trace_rollouts
 // abi_host.hip: the helper thread of the paired host work (mppi_set_host_threads)
 extern std::atomic<int> g_host_threads;
 void host_helper_arm();
+
+// The buffers of a batched host pass: ONE set per purpose and device beside the device's batch stream, grown on demand and never
+// destroyed -- the instances' inputs (pinned staging -> device, one copy), their results (device -> pinned, one copy) and, where
+// the kernel keeps records, its work area.  Used under the device's FleetBlock::mu, from staging until the results are unpacked;
+// the stream is idle in them whenever the mutex is free.
+struct FleetWork {
+  float *d_in = nullptr, *d_out = nullptr, *d_work = nullptr, *h_in = nullptr, *h_out = nullptr;
+  size_t in_cap = 0, out_cap = 0, work_cap = 0;  // floats
+};
+
+inline hipError_t fleet_grow(float **d, float **h, size_t *cap, size_t need)
+{
+  if (need <= *cap) return hipSuccess;
+  const size_t want = need + need / 2;
+  if (*d) (void)hipFree(*d);
+  if (h && *h) (void)hipHostFree(*h);
+  *d = nullptr;
+  if (h) *h = nullptr;
+  *cap = 0;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(d), sizeof(float) * want);
+  if (e == hipSuccess && h) e = hipHostMalloc(reinterpret_cast<void **>(h), sizeof(float) * want, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    if (*d) (void)hipFree(*d);
+    *d = nullptr;
+    return e;
+  }
+  *cap = want;
+  return hipSuccess;
+}
+
+inline size_t align4(size_t floats) { return (floats + 3) & ~(size_t)3; }
+
+// One batched host pass over the handles hs[0 .. n) of one device (abi_host.hip: the DDP passes and the nominal replays of a fleet;
+// abi_trace.hip: its traces): open() -- the device, its batch stream and fleet block, every handle's offsets into the buffers, the
+// block's lock (held until the pass goes out of scope), the buffers, the inputs staged by the caller and sent in one copy;
+// launch() -- the argument blocks of one chunk of at most kMaxFleet handles staged, sent and its kernel enqueued (a chunk's blocks
+// are ordered behind the launch before it, which reads the device block); finish() -- the results in one copy and the
+// synchronise.  An error of the enqueues is kept in `e`: the calls after it do nothing and finish() fails every handle with
+// `what`.  The results are in w->h_out, at out_off, once finish() has returned MPPI_OK.
+struct FleetPass {
+  mppi_handle *const *hs;
+  int n;
+  const char *what;
+  hipStream_t S = nullptr;
+  FleetBlock *fb = nullptr;
+  FleetWork *w = nullptr;
+  std::vector<size_t> in_off, out_off, work_off;  // [n + 1] floats, every handle's piece a multiple of four
+  std::unique_lock<std::mutex> lk;
+  hipError_t e = hipSuccess;
+
+  // in_floats(i) / out_floats(i) / work_floats(i): handle i's pieces (0: none); stage(i, in): fills handle i's inputs in pinned memory
+  template <class InFloats, class OutFloats, class WorkFloats, class Stage>
+  int open(FleetWork *work, InFloats in_floats, OutFloats out_floats, WorkFloats work_floats, Stage stage)
+  {
+    mppi_handle *h0 = hs[0];
+    const int dev = h0->cfg.device;
+    HIPCHK(h0, ensure_device(dev));
+    S = batch_stream(dev);
+    if (!S) return fail(h0, MPPI_ERR_HIP, "no batch stream");
+    fb = fleet_block(dev);
+    if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
+    in_off = out_off = work_off = std::vector<size_t>((size_t)n + 1, 0);
+    for (int i = 0; i < n; i++) {
+      in_off[i + 1] = in_off[i] + align4(in_floats(i));
+      out_off[i + 1] = out_off[i] + align4(out_floats(i));
+      work_off[i + 1] = work_off[i] + align4(work_floats(i));
+    }
+    lk = std::unique_lock<std::mutex>(fb->mu);
+    w = &work[dev];
+    if (in_off[n] > w->in_cap || out_off[n] > w->out_cap || work_off[n] > w->work_cap) {
+      HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier pass is behind the buffers; nothing else on the stream reads them
+      HIPCHK(h0, fleet_grow(&w->d_in, &w->h_in, &w->in_cap, in_off[n]));
+      HIPCHK(h0, fleet_grow(&w->d_out, &w->h_out, &w->out_cap, out_off[n]));
+      HIPCHK(h0, fleet_grow(&w->d_work, nullptr, &w->work_cap, work_off[n]));
+    }
+    for (int i = 0; i < n; i++) stage(i, w->h_in + in_off[i]);
+    if (in_off[n] > 0) e = hipMemcpyAsync(w->d_in, w->h_in, sizeof(float) * in_off[n], hipMemcpyHostToDevice, S);
+    return MPPI_OK;
+  }
+
+  // handles [at, at + m): fill(i, a) writes handle i's (zeroed) argument block
+  template <class Args, class Fill>
+  void launch(int at, int m, hipError_t (*kernel)(const Args *, const Args *, int, hipStream_t), Fill fill)
+  {
+    unsigned char *host = nullptr;
+    if (e != hipSuccess || (e = arg_block_stage(fb->args, &host)) != hipSuccess) return;
+    Args *args = reinterpret_cast<Args *>(host);
+    for (int i = at; i < at + m; i++) {
+      args[i - at] = Args{};
+      fill(i, args[i - at]);
+    }
+    e = arg_block_send(fb->args, sizeof(Args) * (size_t)m, S);
+    if (e == hipSuccess) e = kernel(args, reinterpret_cast<const Args *>(fb->args.d), m, S);
+  }
+
+  int finish()
+  {
+    if (e == hipSuccess && out_off[n] > 0) e = hipMemcpyAsync(w->h_out, w->d_out, sizeof(float) * out_off[n], hipMemcpyDeviceToHost, S);
+    if (e == hipSuccess) e = hipStreamSynchronize(S);
+    if (e == hipSuccess) return MPPI_OK;
+    (void)hipStreamSynchronize(S);  // nothing enqueued so far is left behind the buffers
+    for (int i = 0; i < n; i++) fail(hs[i], MPPI_ERR_HIP, what, e);
+    return MPPI_ERR_HIP;
+  }
+};
 
 }  // namespace mppi_abi

@@ -82,10 +82,11 @@ FleetBlock *fleet_block(int device)
   if (device < 0 || device >= 64) return nullptr;
   std::lock_guard<std::mutex> lk(g_batch_mu);
   FleetBlock &fb = g_fleet[device];
-  // (the largest of the three uses: a batched solve's blocks, a batched DDP pass's, a batched nominal replay's)
+  // (the largest of the uses: a batched solve's blocks, a batched DDP pass's, a batched nominal replay's, a batched trace's)
   if (!fb.ready)
     fb.ready = arg_block_create(fb.args, std::max({fleet_bytes(kMaxFleet, true), sizeof(DdpFleetArgs) * (size_t)kMaxFleet,
-                                                   sizeof(NominalFleetArgs) * (size_t)kMaxFleet})) == hipSuccess;
+                                                   sizeof(NominalFleetArgs) * (size_t)kMaxFleet, sizeof(TraceFleetArgs) * (size_t)kMaxFleet,
+                                                   sizeof(TraceSelectArgs) * (size_t)kMaxFleet})) == hipSuccess;
   return fb.ready ? &fb : nullptr;
 }
 

@@ -336,6 +336,27 @@ struct TraceArgs {
 bool trace_image_in_lds(const NetDesc &net);  // the k-major image and the waves' tiles fit the kernel's LDS budget
 hipError_t launch_rollout_trace(const NetDesc &net, const TraceArgs &a, hipStream_t stream);
 hipError_t launch_rollout_trace_bf(const TraceArgs &a, hipStream_t stream);
+// ... and the traces of n <= kMaxFleet independent controllers in one launch (mppi_trace_rollouts_batch): grid (workgroups of the
+// member with the most rollouts, members), the members' argument blocks an array in device memory.  Members may differ in
+// everything a TraceArgs holds and in their layer lists; rollout_trace_fleet_kernel serves the network model,
+// rollout_trace_fleet_bf_kernel the basis-function model (net and img_lds unused)
+struct TraceFleetArgs {
+  TraceArgs a;   // a.n: the member's rollouts (0: none); a.ks: its piece of the device index array
+  int img_lds;   // the image is copied to LDS (trace_image_in_lds)
+  NetDesc net;
+};
+hipError_t launch_rollout_trace_fleet(const TraceFleetArgs *h_inst, const TraceFleetArgs *d_inst, int n, hipStream_t stream);
+hipError_t launch_rollout_trace_fleet_bf(const TraceFleetArgs *h_inst, const TraceFleetArgs *d_inst, int n, hipStream_t stream);
+// trace_select_fleet_kernel, in front of the two on the same stream: ks[r] (and ks_out[r] where given) = the rollout of rank r < n
+// in mppi_top_rollouts' order -- a number before a NaN, the larger weight first, the lower index first -- chosen from the
+// member's K device weights.  w == nullptr or n == 0: a member that brought its indices, nothing is written
+struct TraceSelectArgs {
+  const float *w;  // [K] the solve's weights (d_w)
+  int *ks;         // [n] the member's piece of the device index array
+  int *ks_out;     // [n] a copy in the result buffer, or nullptr
+  int K, n;
+};
+hipError_t launch_trace_select_fleet(const TraceSelectArgs *h_inst, const TraceSelectArgs *d_inst, int n, hipStream_t stream);
 
 // solve_kernels.hip
 // everything of one solve iteration after the rollout (solve_tail_kernel up to 4096 rollouts, solve_tail_stream_kernel beyond)

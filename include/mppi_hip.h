@@ -77,6 +77,8 @@ extern "C" {
  *    in one launch; compatible additions, the single and the pair call are unchanged). */
 /*    (still 5) + mppi_nominal_traj_batch, mppi_debug_nominal_info (the nominal trajectories of a fleet in one launch; compatible
  *    additions, the single and the pair call are unchanged). */
+/*    (still 5) + mppi_trace_rollouts_batch, mppi_debug_trace_info (the traces of a fleet in one launch, the largest weights chosen
+ *    on the device; compatible additions, mppi_trace_rollouts and mppi_top_rollouts are unchanged). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -309,6 +311,34 @@ int mppi_trace_rollouts(mppi_handle *h, const int *ks, int n, float *states, flo
  * MPPI_ERR_INVALID for n < 0 or n > K or ks == NULL with n > 0, MPPI_ERR_STATE before the first solve (mppi_rollout_only
  * computes no weights: it does not count). */
 int mppi_top_rollouts(mppi_handle *h, int n, int *ks);
+/* The traces of a whole fleet in one call: handle i traces counts[i] rollouts of its last solve -- the indices ks[i][0..counts[i]),
+ * or, where ks is NULL as a whole or ks[i] is NULL, its counts[i] largest weights in mppi_top_rollouts' order.  ks_out (NULL, or
+ * [n_handles]): ks_out[i] receives the counts[i] indices that were traced.  states, controls, step_costs, costs, first_crash: each
+ * NULL as a whole (not wanted) or [n_handles] pointers to buffers of mppi_trace_rollouts' shapes for counts[i] rollouts; where an
+ * array is given, the entry of every handle with counts[i] > 0 must be non-NULL.  Per handle the result is that of
+ * mppi_top_rollouts (where it chooses) followed by mppi_trace_rollouts: the last completed solve, its state and applied controls,
+ * the current model, cost, costmap and limits, duplicates allowed.
+ * Sharing rule: n_handles >= 2, all on one device, none armed, every counts[i] <= min(K_i, 1024): the set is traced ON THE DEVICE'S
+ * BATCH STREAM -- the largest weights are chosen on the device from K alone (no weight travels to the host; any K), the network
+ * handles share one launch per 64 (layer lists, K, T, scene and limits are data), the basis-function handles one of their own;
+ * one copy of the explicit indices in, ONE copy of the outputs that were asked for out, one synchronise.  Every record is bit for
+ * bit the per-handle call's.  Anything else -- n_handles = 1, an armed handle in the set (handles armed together wait gated on the
+ * batch stream; the per-handle call goes in front of its own gate, and the handle stays armed), a count above 1024, several
+ * devices -- runs the per-handle calls one after the other, with their bits; mppi_debug_trace_info tells which it was.
+ * Order of work: every argument is checked -- MPPI_ERR_INVALID for NULL handles or counts, n_handles < 1, a NULL handle, a handle
+ * listed twice, a negative count, a count above K where the handle chooses, an index outside [0, K), a missing output pointer --,
+ * then every pending solve is collected, then every handle's readiness (MPPI_ERR_STATE before the first solve, and for a choice of
+ * the largest weights after mppi_rollout_only alone; MPPI_ERR_HIP after a lost solve) and the control-cost rule (MPPI_ERR_UNSUPPORTED
+ * if step_costs or costs is given and ANY handle with rollouts to trace has a control cost on; the reason is in that handle's
+ * mppi_last_error; the same call without the two cost arrays is served); only then is anything launched.  On the shared path the
+ * caller's buffers are written after EVERY launch and copy of the call has succeeded.  All counts 0: MPPI_OK, nothing is written.
+ * The call blocks until the results are back.  (csrc/rollout_trace.hip, csrc/abi_trace.hip.) */
+int mppi_trace_rollouts_batch(mppi_handle *const *handles, int n_handles, const int *counts, const int *const *ks, int *const *ks_out,
+                              float *const *states, float *const *controls, float *const *step_costs, float *const *costs,
+                              int *const *first_crash);
+/* Test / tooling hook: *on_device = 1 if the handle's most recent trace ran in the fleet's kernels (the shared path of
+ * mppi_trace_rollouts_batch), 0 if in a launch of its own (or none yet).  MPPI_ERR_INVALID for a NULL argument. */
+int mppi_debug_trace_info(const mppi_handle *h, int *on_device);
 /* Stage-level entry: noise (or explicit noise) + rolloutKernel only; costs[K]. */
 int mppi_rollout_only(mppi_handle *h, const float state[MPPI_STATE_DIM], float *costs);
 /* computeNominalTraj (mppi_controller.cu:501-519), host replay of U_ like the reference:

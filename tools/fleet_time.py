@@ -34,7 +34,13 @@ n mppi_nominal_traj calls on one host thread and n / 2 mppi_nominal_traj_pair ca
 A fleet whose handles cycle through the given layer lists (handle i has list i mod the number of lists), one row per n, every
 column of a row in one process: (a) every handle forced to "fleet_glb16" -- one launch for the mixed fleet --, (b) the same handles
 forced to "glb16", handle by handle, (c) "auto", (d) "fleet16" (one list of hidden widths up to 128 only; else not available),
-(A) "fleet_glb16" a second time: the A/A spread of the visit."""
+(A) "fleet_glb16" a second time: the A/A spread of the visit.
+
+    python tools/fleet_time.py --trace [--n 4 16 64] [--K 1920] [--T 100] [--ticks 100] [--net ...]
+
+The 64 best sampled trajectories of every handle of a solved fleet: mppi_trace_rollouts_batch -- the largest weights chosen on the
+device, one trace launch, one result copy -- against the same handles one by one (mppi_top_rollouts + mppi_trace_rollouts); the
+batch entry is timed twice, interleaved with the per-handle calls: the A/A spread of the visit."""
 import argparse
 import json
 import os
@@ -300,6 +306,71 @@ def nominal_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
     return rows
 
 
+def trace_ms(net, n, K=1920, T=100, rollouts=64, calls=100, warm=5):
+    """The 64 best sampled trajectories of each of n solved handles, each the median wall time of `calls` calls after `warm` warm
+    ones: the batch entry (the largest weights chosen on the device, one trace launch for the fleet) twice -- interleaved, their
+    difference is the A/A spread of the visit -- against the same handles one by one (mppi_top_rollouts + mppi_trace_rollouts).
+    Every call fills buffers allocated once."""
+    from autorally_amd import capi
+    sols, states = fleet(net, "auto", n, K, T)
+    try:
+        for s, st in zip(sols, states):
+            s.compute_control(st)
+        C = capi.C
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        c = rollouts
+        bufs = [dict(ks=np.zeros(c, np.int32), states=np.zeros((c, T, 7), np.float32), controls=np.zeros((c, T, 2), np.float32),
+                     step_costs=np.zeros((c, T), np.float32), costs=np.zeros(c, np.float32), first_crash=np.zeros(c, np.int32)) for _ in sols]
+        arr = lambda key, ptr: (ptr * n)(*[b[key].ctypes.data_as(ptr) for b in bufs])  # noqa: E731
+        hs = (C.c_void_p * n)(*[s.h for s in sols])
+        counts = (C.c_int * n)(*([c] * n))
+        args = (arr("ks", ip), arr("states", fp), arr("controls", fp), arr("step_costs", fp), arr("costs", fp), arr("first_crash", ip))
+        L = sols[0].L
+
+        def batch():
+            assert L.mppi_trace_rollouts_batch(hs, n, counts, None, *args) == capi.OK
+
+        def single():
+            for s, b in zip(sols, bufs):
+                assert L.mppi_top_rollouts(s.h, c, b["ks"].ctypes.data_as(ip)) == capi.OK
+                assert L.mppi_trace_rollouts(s.h, b["ks"].ctypes.data_as(ip), c, capi._fp(b["states"]), capi._fp(b["controls"]),
+                                             capi._fp(b["step_costs"]), capi._fp(b["costs"]), b["first_crash"].ctypes.data_as(ip)) == capi.OK
+
+        def clock(fn):
+            t0 = time.perf_counter()
+            fn()
+            return time.perf_counter() - t0
+        for _ in range(warm):
+            batch()
+            single()
+        ta, tb, ts = [], [], []
+        for _ in range(calls):
+            ta.append(clock(batch))
+            ts.append(clock(single))
+            tb.append(clock(batch))
+        row = {"net": "-".join(map(str, net)), "n": n, "K": K, "T": T, "rollouts": c}
+        row["batch_ms"], row["batch_again_ms"], row["single_ms"] = (1e3 * float(np.median(t)) for t in (ta, tb, ts))
+        batch()
+        row["on_device"] = sols[0].debug_trace_info()
+        return row
+    finally:
+        for s in sols:
+            s.close()
+
+
+def trace_table(nets, ns=(4, 16, 64), K=1920, T=100, calls=100):
+    rows = []
+    for net in nets:
+        for n in ns:
+            row = trace_ms(net, n, K=K, T=T, calls=calls)
+            rows.append(row)
+            print("FLEET TRACE n=%d K=%d T=%d net=%s, %d rollouts each: batch %.4f ms (on_device %d; again %.4f ms: A/A %.4f ms)  handle by handle "
+                  "%.4f ms;  single/batch %.2f" % (n, K, T, row["net"], row["rollouts"], row["batch_ms"], row["on_device"], row["batch_again_ms"],
+                                                    abs(row["batch_ms"] - row["batch_again_ms"]), row["single_ms"], row["single_ms"] / row["batch_ms"]),
+                  flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="*", default=None, help="handles (default 16; --mixed: 4 16 64, one row each)")
@@ -315,12 +386,17 @@ def main():
                     "passes, n = 2, 4, 16, 64 (mppi_compute_feedback_gains_batch)")
     ap.add_argument("--nominal", action="store_true", help="the nominal trajectories of the fleet instead: the batch entry against the "
                     "host replays, n = 2, 4, 16, 64 (mppi_nominal_traj_batch)")
+    ap.add_argument("--trace", action="store_true", help="the best 64 sampled trajectories of every handle instead: the batch entry against "
+                    "the per-handle calls, n = 4, 16, 64 (mppi_trace_rollouts_batch)")
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
     parse = lambda names: [[int(x) for x in s.split("-")] for s in names]  # noqa: E731
     if a.mixed:
         print(json.dumps(mixed_table(parse(a.mixed), a.n or (4, 16, 64), a.K or 1920, a.T, a.ticks, a.warm, a.ways or "abcdA")))
+        return
+    if a.trace:
+        print(json.dumps(trace_table(parse(a.net), a.n or (4, 16, 64), a.K or 1920, a.T, min(a.ticks, 100))))
         return
     a.n = a.n[0] if a.n else 16
     if a.nominal:
