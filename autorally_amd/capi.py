@@ -70,6 +70,7 @@ SYMBOLS = [
     "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
     "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
     "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
+    "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -84,7 +85,8 @@ ABI5_SYMBOLS = ("mppi_debug_set_chained_ticks", "mppi_debug_min_cost", "mppi_arm
 UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_top_rollouts",
                        "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
                        "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
-                       "mppi_trace_rollouts_batch", "mppi_debug_trace_info")
+                       "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
+                       "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info")
 
 _lib = None
 
@@ -192,6 +194,10 @@ def lib():
             fpp = C.POINTER(fp)
             L.mppi_nominal_traj_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
             L.mppi_debug_nominal_info.argtypes = [hp, C.POINTER(C.c_int)]
+        if hasattr(L, "mppi_nominal_and_gains_batch"):  # added without a version step, like mppi_debug_launch_info
+            fpp = C.POINTER(fp)
+            L.mppi_nominal_and_gains_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
+            L.mppi_debug_nominal_and_gains_info.argtypes = [hp, C.POINTER(C.c_int)]
         if hasattr(L, "mppi_trace_rollouts_batch"):  # added without a version step, like mppi_debug_launch_info
             ip, fpp = C.POINTER(C.c_int), C.POINTER(fp)
             ipp = C.POINTER(ip)
@@ -467,6 +473,12 @@ class Solver:
         self._ck(self.L.mppi_debug_nominal_info(self.h, C.byref(on)))
         return on.value
 
+    def debug_nominal_and_gains_info(self):
+        """mppi_debug_nominal_and_gains_info: 1 if the handle's last nominal_and_gains_batch ran in the one kernel, 0 if as the two calls."""
+        fused = C.c_int(-1)
+        self._ck(self.L.mppi_debug_nominal_and_gains_info(self.h, C.byref(fused)))
+        return fused.value
+
     def set_ddp_weights(self, Q, R, Qf):
         self._ck(self.L.mppi_set_ddp_weights(self.h, _fp(_f32(Q, (7,))), _fp(_f32(R, (2,))), _fp(_f32(Qf, (7,)))))
 
@@ -654,6 +666,26 @@ def nominal_traj_batch(solvers, states):
     out = [(np.zeros((s.T, 7), np.float32), np.zeros((s.T, 2), np.float32)) for s in solvers]
     ssp, csp = (fp * n)(*[_fp(o[0]) for o in out]), (fp * n)(*[_fp(o[1]) for o in out])
     rc = solvers[0].L.mppi_nominal_traj_batch(hs, _fp(st), ssp, csp, n)
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
+    return out
+
+
+def nominal_and_gains_batch(solvers, states, outputs=None):
+    """mppi_nominal_and_gains_batch: the nominal replays of several Solver objects and the DDP passes that track them in one call
+    (one launch per 64 where the library can share it).  Returns [(state_seq [T][7], control_seq [T][2])] in the solvers' order; the
+    gains are read with Solver.feedback_gains().  outputs: the arrays to fill (a caller that checks what a refused or a partly
+    failed call wrote); raises MppiError with every handle's message (an empty fleet: MPPI_ERR_INVALID, as the library answers
+    n < 1)."""
+    n = len(solvers)
+    if n < 1 or len(states) != n:
+        raise MppiError(ERR_INVALID, "nominal_and_gains_batch: %d solvers, %d states" % (n, len(states)))
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    st = np.ascontiguousarray(np.stack([_f32(x, (7,)) for x in states]), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    out = outputs if outputs is not None else [(np.zeros((s.T, 7), np.float32), np.zeros((s.T, 2), np.float32)) for s in solvers]
+    ssp, csp = (fp * n)(*[_fp(o[0]) for o in out]), (fp * n)(*[_fp(o[1]) for o in out])
+    rc = solvers[0].L.mppi_nominal_and_gains_batch(hs, _fp(st), ssp, csp, n)
     if rc != OK:
         raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
     return out

@@ -1,7 +1,8 @@
 // abi_host.hip -- the host-side halves of a control tick: nominal trajectory replays (mppi_controller.cu:501-519), DDP
 // feedback gains (:402-445), and the helper thread that takes one of a pair (mppi_set_host_threads); the DDP passes of a whole
 // fleet in one launch of ddp_fleet_kernel (mppi_compute_feedback_gains_batch) and its nominal replays in one launch of
-// nominal_fleet_kernel (mppi_nominal_traj_batch): the two entries here that compute on the device.
+// nominal_fleet_kernel (mppi_nominal_traj_batch), or both in one launch of nominal_gains_fleet_kernel
+// (mppi_nominal_and_gains_batch): the entries here that compute on the device.
 #include "abi_internal.hpp"
 
 #include <stdexcept>
@@ -119,6 +120,7 @@ void host_helper_arm() { host_helper().arm(); }
 
 static FleetWork g_ddp_work[64];      // mppi_compute_feedback_gains_batch -> ddp_fleet_kernel
 static FleetWork g_nominal_work[64];  // mppi_nominal_traj_batch -> nominal_fleet_kernel
+static FleetWork g_nominal_gains_work[64];  // mppi_nominal_and_gains_batch -> nominal_gains_fleet_kernel
 
 // The sharing rule of the batched DDP pass, next to fleet_together: two or more handles of the network model with parameters set,
 // all on one device.  Layer lists, T, hz, limits and weights may differ: they are data.  (The basis-function model stays on the
@@ -237,9 +239,106 @@ static int nominal_fleet_launch(mppi_handle *const *hs, const float *states, flo
   return MPPI_OK;
 }
 
+// The handles of a set that is both nominal_fleet_together and ddp_fleet_together: every handle's replay and the DDP pass that
+// tracks it in one workgroup of nominal_gains_fleet_kernel.  One input copy (the states and the HOST control sequences), launches
+// of up to kMaxFleet, one result copy, one synchronise, as nominal_fleet_launch does it; the targets never come down in between.
+// The caller's buffers and every handle's DDP result are written only after all of that has succeeded.  Returns MPPI_OK,
+// MPPI_ERR_STATE when a handle's factorisation failed (that handle alone has no gains; its sequences are delivered), or the error
+// that stopped the call.
+static int nominal_gains_fleet_launch(mppi_handle *const *hs, const float *states, float *const *state_seqs, float *const *control_seqs,
+                                      int n)
+{
+  FleetPass p{hs, n, "batched nominal replay and DDP pass"};
+  int rc = p.open(g_nominal_gains_work, [&](int i) { return nominal_fleet_in_floats(hs[i]->T); },
+                  [&](int i) { return nominal_gains_fleet_out_floats(hs[i]->T); },
+                  [&](int i) { return ddp_fleet_work_floats(hs[i]->T, hs[i]->net); }, [&](int i, float *in) {
+    memcpy(in, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+    memcpy(in + 7, hs[i]->U.data(), sizeof(float) * (size_t)hs[i]->T * kControlDim);
+  });
+  if (rc) return rc;
+  for (int at = 0; at < n; at += kMaxFleet)
+    p.launch(at, std::min(kMaxFleet, n - at), launch_nominal_gains_fleet, [&](int i, NominalGainsFleetArgs &a) {
+      const mppi_handle *h = hs[i];
+      a.theta = image(h, Image::Theta);
+      a.wimg = image(h, Image::Trace);
+      a.in = p.w->d_in + p.in_off[i];
+      a.out = p.w->d_out + p.out_off[i];
+      a.work = p.w->d_work + p.work_off[i];
+      a.T = h->T;
+      a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
+      a.img_lds = nominal_gains_fleet_image_in_lds(h->net) ? 1 : 0;
+      a.dt = (float)(1.0 / h->cfg.hz);  // the pass's (ddp_fleet_launch)
+      a.dt_nominal = h->dt;             // the replay's (nominal_fleet_launch)
+      for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; a.R[j] = h->ddp_R[j]; }
+      for (int q = 0; q < kStateDim; q++) { a.Q[q] = h->ddp_Q[q]; a.Qf[q] = h->ddp_Qf[q]; }
+      a.net = h->net;
+    });
+  rc = p.finish();
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    const size_t T = (size_t)h->T;
+    const float *o = p.w->h_out + p.out_off[i];
+    const float *seq = o + nominal_gains_fleet_seq_offset(h->T);
+    memcpy(state_seqs[i], seq, sizeof(float) * 7 * T);
+    memcpy(control_seqs[i], seq + 7 * T, sizeof(float) * 2 * T);
+    h->nominal_on_device = h->ddp_on_device = h->nominal_gains_fused = 1;
+    h->have_ddp = false;
+    int status = 0;
+    memcpy(&status, o + 26 * T + 1, sizeof(int));
+    if (status != 0) {
+      rc = fail(h, MPPI_ERR_STATE, "DDP: control Hessian could not be factorised");
+      continue;
+    }
+    DdpResult &r = h->ddp;
+    r.feedback.assign(o, o + 14 * T);
+    r.feedforward.assign(o + 14 * T, o + 16 * T);
+    r.x.assign(o + 16 * T, o + 23 * T);
+    r.u.assign(o + 23 * T, o + 25 * T);
+    r.cost.assign(o + 25 * T, o + 26 * T);
+    r.total_cost = o[26 * T];
+    r.iterations = 1;
+    h->have_ddp = true;
+  }
+  return rc;
+}
+
 }  // namespace mppi_abi
 
 extern "C" {
+
+int mppi_nominal_and_gains_batch(mppi_handle *const *handles, const float *states, float *const *state_seqs, float *const *control_seqs,
+                                 int n)
+{
+  // mppi_nominal_traj_batch's order: every argument, then every handle's readiness, then every pending solve; only then a launch
+  if (!handles || !states || !state_seqs || !control_seqs || n < 1) return MPPI_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!handles[i] || !state_seqs[i] || !control_seqs[i]) return MPPI_ERR_INVALID;
+    for (int q = 0; q < i; q++)
+      if (handles[q] == handles[i]) return fail(handles[i], MPPI_ERR_INVALID, "the same handle twice in one batch");
+  }
+  for (int i = 0; i < n; i++) handles[i]->nominal_gains_fused = 0;
+  if (!nominal_fleet_together(handles, n) || !ddp_fleet_together(handles, n)) {
+    // exactly the two calls, one after the other: their bits, their errors, their order of work
+    const int rc = mppi_nominal_traj_batch(handles, states, state_seqs, control_seqs, n);
+    if (rc) return rc;
+    return mppi_compute_feedback_gains_batch(handles, states, state_seqs, control_seqs, n);
+  }
+  // (every handle of a shared set has its parameters: the sharing rules say so)
+  for (int i = 0; i < n; i++)
+    if (handles[i]->pending) {
+      const int rc = mppi_synchronize(handles[i]);
+      if (rc) return rc;
+    }
+  return nominal_gains_fleet_launch(handles, states, state_seqs, control_seqs, n);  // more than kMaxFleet handles: launches of up to kMaxFleet
+}
+
+int mppi_debug_nominal_and_gains_info(const mppi_handle *h, int *fused)
+{
+  if (!h || !fused) return MPPI_ERR_INVALID;
+  *fused = h->nominal_gains_fused;
+  return MPPI_OK;
+}
 
 int mppi_nominal_traj(mppi_handle *h, const float state[MPPI_STATE_DIM], float *state_seq, float *control_seq)
 {

@@ -159,6 +159,7 @@ struct mppi_handle {
   bool have_ddp = false;
   int ddp_on_device = 0;  // the last DDP pass ran in ddp_fleet_kernel (mppi_compute_feedback_gains_batch), not on the host
   int nominal_on_device = 0;  // the last nominal replay ran in nominal_fleet_kernel (mppi_nominal_traj_batch), not on the host
+  int nominal_gains_fused = 0;  // the last mppi_nominal_and_gains_batch ran in nominal_gains_fleet_kernel, not as the two calls
   int trace_on_device = 0;  // the last trace ran in the fleet's kernels (mppi_trace_rollouts_batch), not in a launch of the handle's own
   hipStream_t batch_s = nullptr;  // the device's batch stream, looked up once (mppi_compute_control_batch)
   unsigned *d_counter = nullptr;  // [1 + T] arrival counters of the tail kernel

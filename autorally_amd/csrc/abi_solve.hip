@@ -86,7 +86,8 @@ FleetBlock *fleet_block(int device)
   if (!fb.ready)
     fb.ready = arg_block_create(fb.args, std::max({fleet_bytes(kMaxFleet, true), sizeof(DdpFleetArgs) * (size_t)kMaxFleet,
                                                    sizeof(NominalFleetArgs) * (size_t)kMaxFleet, sizeof(TraceFleetArgs) * (size_t)kMaxFleet,
-                                                   sizeof(TraceSelectArgs) * (size_t)kMaxFleet})) == hipSuccess;
+                                                   sizeof(TraceSelectArgs) * (size_t)kMaxFleet,
+                                                   sizeof(NominalGainsFleetArgs) * (size_t)kMaxFleet})) == hipSuccess;
   return fb.ready ? &fb : nullptr;
 }
 

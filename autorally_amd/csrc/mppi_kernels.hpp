@@ -465,4 +465,27 @@ inline size_t nominal_fleet_out_floats(int T) { return (size_t)9 * T; }
 bool nominal_fleet_image_in_lds(const NetDesc &net);
 hipError_t launch_nominal_fleet(const NominalFleetArgs *h_inst, const NominalFleetArgs *d_inst, int n, hipStream_t stream);
 
+// nominal_gains_fleet.hip: the nominal replay AND the DDP pass that tracks it (mppi_nominal_and_gains_batch) of n <= kMaxFleet
+// independent controllers in one launch, one workgroup per controller: the replay runs on wave 1 while wave 0 runs the pass's
+// initial rollout; the targets never leave the device.
+//   in:   [7] state | [T][2] the control sequence (before the clamp)
+//   out:  DdpFleetArgs's out (26 T + 2 floats, rounded up to four) | [T][7] state_seq | [T][2] control_seq (clamped): the pass's targets
+//   work: DdpFleetArgs's work
+struct NominalGainsFleetArgs {
+  const float *theta;  // the weights as the reference packs them (row-major; the Jacobians)
+  const float *wimg;   // pack_trace_weights: every W transposed (the forward passes of both waves)
+  const float *in;
+  float *out, *work;
+  int T, negate_yaw_der;
+  int img_lds;         // the image is copied to LDS (nominal_gains_fleet_image_in_lds)
+  float dt;            // the pass's: (float)(1 / hz)
+  float dt_nominal;    // the replay's: the handle's dt
+  float u_lo[2], u_hi[2], Q[7], R[2], Qf[7];
+  NetDesc net;
+};
+inline size_t nominal_gains_fleet_seq_offset(int T) { return (ddp_fleet_out_floats(T) + 3) & ~(size_t)3; }
+inline size_t nominal_gains_fleet_out_floats(int T) { return nominal_gains_fleet_seq_offset(T) + nominal_fleet_out_floats(T); }
+bool nominal_gains_fleet_image_in_lds(const NetDesc &net);
+hipError_t launch_nominal_gains_fleet(const NominalGainsFleetArgs *h_inst, const NominalGainsFleetArgs *d_inst, int n, hipStream_t stream);
+
 }  // namespace mppi

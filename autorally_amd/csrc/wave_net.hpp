@@ -5,7 +5,7 @@
 // read 256 contiguous bytes per k), in LDS or in global memory; kWaveNetAhead k steps are requested while the chunk before them
 // is multiplied.  Any layer list mppi_create accepts is data.
 //
-// Used by rollout_trace.hip (the traced rollouts), ddp_fleet.hip (through ddp_f) and nominal_fleet.hip.  What differs between
+// Used by rollout_trace.hip (the traced rollouts), ddp_fleet.hip (through ddp_f), nominal_fleet.hip and nominal_gains_fleet.hip.  What differs between
 // them is an arithmetic policy: how a neuron's sum takes one product, and what follows the sum.  The library is compiled
 // -ffp-contract=off, so a policy's text is its arithmetic: an fmaf is one rounding, a multiply and an add are two.
 #pragma once

@@ -759,6 +759,49 @@ class MPPIControllerT {
     }
     if (rc != MPPI_OK) throw std::runtime_error(std::string("libmppi_hip: ") + mppi_strerror(rc) + " (" + failed + ")");
   }
+  // finishControlFleetOnDevice followed by computeFeedbackGainsFleet from each controller's solve state -- what the reference's tick
+  // does after every computeControl -- in ONE call (mppi_nominal_and_gains_batch): all solves collected, then every controller's
+  // replay and the DDP pass that tracks it run in one kernel launch, the targets never coming down in between (two or more
+  // network-model controllers on one device; any other set: the two calls, with their bits).  state_solution_ / control_solution_
+  // and the gains are bit for bit those of the two functions in sequence.  Throws under computeFeedbackGainsFleet's rule: a
+  // controller whose control Hessian cannot be factorised makes the call throw, its nominal sequences and the others' gains in place.
+  static void finishTickFleetOnDevice(MPPIControllerT *const *controllers, int n)
+  {
+    if (n < 1) return;
+    std::vector<mppi_handle *> hs((size_t)n);
+    std::vector<float *> xs((size_t)n), us((size_t)n);
+    std::vector<float> states((size_t)n * STATE_DIM);
+    for (int c = 0; c < n; c++) {
+      float tc = 0.0f;
+      controllers[c]->ck(mppi_get_results(controllers[c]->h_, nullptr, &tc, nullptr, nullptr));
+      controllers[c]->trajectory_cost_ = tc;
+      controllers[c]->syncParams(false);
+      hs[(size_t)c] = controllers[c]->h_;
+      xs[(size_t)c] = controllers[c]->state_solution_.data();
+      us[(size_t)c] = controllers[c]->control_solution_.data();
+      for (int i = 0; i < STATE_DIM; i++) states[(size_t)c * STATE_DIM + i] = controllers[c]->solve_state_[i];
+    }
+    const int rc = mppi_nominal_and_gains_batch(hs.data(), states.data(), xs.data(), us.data(), n);
+    if (rc != MPPI_OK && rc != MPPI_ERR_STATE) {  // the text sits on whichever handle recorded it
+      std::string msg = std::string("libmppi_hip: ") + mppi_strerror(rc) + " (";
+      for (int c = 0; c < n; c++) {
+        const char *e = mppi_last_error(controllers[c]->h_);
+        if (e && *e) msg += std::string(msg.back() == '(' ? "" : " | ") + e;
+      }
+      throw std::runtime_error(msg + ")");
+    }
+    std::string failed;
+    for (int c = 0; c < n; c++) {
+      const char *e = mppi_last_error(controllers[c]->h_);
+      const std::string why = e ? e : "";  // (the getter below leaves its own message on a handle without a result)
+      if (mppi_get_feedback_gains(controllers[c]->h_, nullptr, nullptr, nullptr, nullptr, nullptr) == MPPI_OK) {
+        controllers[c]->fetchFeedbackGains();
+      } else {
+        failed += std::string(failed.empty() ? "" : " | ") + "controller " + std::to_string(c) + ": " + why;
+      }
+    }
+    if (rc != MPPI_OK) throw std::runtime_error(std::string("libmppi_hip: ") + mppi_strerror(rc) + " (" + failed + ")");
+  }
   // Solve-ahead (mppi_arm): this controller's NEXT solve is enqueued now, gated -- its kernels start and wait at most max_wait_s
   // for the next startControl / computeControl, which then opens the gate with its state instead of launching.  Results are
   // bit for bit the same.  MPPI_ERR_UNSUPPORTED (no gated form for this configuration) is no error: the solve launches as before.

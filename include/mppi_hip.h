@@ -79,6 +79,8 @@ extern "C" {
  *    additions, the single and the pair call are unchanged). */
 /*    (still 5) + mppi_trace_rollouts_batch, mppi_debug_trace_info (the traces of a fleet in one launch, the largest weights chosen
  *    on the device; compatible additions, mppi_trace_rollouts and mppi_top_rollouts are unchanged). */
+/*    (still 5) + mppi_nominal_and_gains_batch, mppi_debug_nominal_and_gains_info (a fleet's nominal trajectories and the feedback
+ *    gains that track them in one launch; compatible additions, the two batch calls it equals are unchanged). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -424,6 +426,35 @@ int mppi_debug_ddp_info(const mppi_handle *h, int *on_device);
 /* Test hook: out[i] = the DDP kernel's tanhf of in[i], computed on `device` (n floats; the text of csrc/tanhf_scalar.hpp, which has
  * to return the C library's bits).  MPPI_ERR_INVALID for a NULL pointer, n = 0 or a negative device. */
 int mppi_debug_device_tanhf(int device, const float *in, float *out, size_t n);
+
+/* The two closing stages of a fleet's tick in one call -- computeNominalTraj, then computeFeedbackGains(state) from the same state
+ * (what the reference's tick does after every computeControl): handles[n], states [n][7].  Per handle the result is that of
+ * mppi_nominal_traj_batch followed by mppi_compute_feedback_gains_batch with that call's outputs as targets: the nominal sequences
+ * land in state_seqs[i] ([T_i][7]) and control_seqs[i] ([T_i][2], clamped), the gains in the handle (mppi_get_feedback_gains is
+ * unchanged).  The inputs are each handle's HOST control sequence and the call's state.
+ * Sharing rule: where BOTH calls would share a launch -- n >= 2 handles of the network model with parameters set, all on one
+ * device -- the two stages are ONE launch (nominal_gains_fleet_kernel, one workgroup per controller; more than 64 handles: launches of
+ * up to 64 with one input copy, one result copy and one synchronise per call): the replay runs on one wave while another runs the
+ * DDP pass's initial rollout, and the targets never travel through the host.  Layer lists, T, hz, limits, negate_yaw_der and DDP
+ * weights may differ per handle.  The results are BIT FOR BIT those of mppi_nominal_traj_batch followed by
+ * mppi_compute_feedback_gains_batch(handles, states, state_seqs, control_seqs, n).  The gains therefore track the DEVICE replay,
+ * which differs from the host replay that mppi_compute_feedback_gains_batch(..., NULL, NULL, ...) tracks only through sinf / cosf
+ * of the heading (the rounded double results, not glibc's floats).  Anything else -- n = 1, a basis-function handle in the set,
+ * handles on several devices, a handle without parameters -- runs exactly those two calls one after the other, with their bits and
+ * their errors; mppi_debug_nominal_and_gains_info tells which it was.  Below the crossovers of DESIGN 4.20 / 4.21 (a few handles)
+ * the host calls (mppi_nominal_traj, mppi_compute_feedback_gains) serve a caller better than any of the batched ones.
+ * Order of work, as in mppi_nominal_traj_batch: every argument is checked (MPPI_ERR_INVALID for a NULL array, n < 1, a NULL handle
+ * or output pointer in the set, a handle listed twice), then every handle's readiness, then every pending solve is collected; only
+ * then is anything launched.  The caller's buffers and every handle's DDP result are written only after every launch and copy
+ * of the call has succeeded.  A handle whose factorisation fails has no gains and its own mppi_last_error; its nominal sequences
+ * are still delivered, the call returns MPPI_ERR_STATE and every other handle keeps a valid result.  The call uses the device's
+ * batch stream and blocks until the results are back; it touches no handle's solve state beyond collecting pending solves, and an
+ * armed handle stays armed (handles armed TOGETHER: see mppi_nominal_traj_batch). */
+int mppi_nominal_and_gains_batch(mppi_handle *const *handles, const float *states /* n x 7 */,
+                                 float *const *state_seqs /* [i]: T_i x 7 */, float *const *control_seqs /* [i]: T_i x 2 */, int n);
+/* Test / tooling hook: *fused = 1 if the handle's most recent mppi_nominal_and_gains_batch ran in the one kernel, 0 if as the two
+ * calls (or none yet).  MPPI_ERR_INVALID for a NULL argument. */
+int mppi_debug_nominal_and_gains_info(const mppi_handle *h, int *fused);
 
 /* Host threads the library may use for the host-side work of a tick that comes in pairs (mppi_nominal_traj_pair,
  * mppi_compute_feedback_gains_pair): 1 (default) = the caller's thread only (the reference's optimizer thread does everything,

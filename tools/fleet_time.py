@@ -29,6 +29,14 @@ against n single calls on one host thread and against the pair entry with mppi_s
 The nominal trajectories of the fleet (n = 2, 4, 16, 64): mppi_nominal_traj_batch -- one launch of nominal_fleet_kernel -- against
 n mppi_nominal_traj calls on one host thread and n / 2 mppi_nominal_traj_pair calls with mppi_set_host_threads(2).
 
+    python tools/fleet_time.py --finish [--n 2 4 16 64] [--T 100] [--ticks 200] [--net ...]
+
+The two closing stages of the fleet's tick (n = 2, 4, 16, 64): mppi_nominal_and_gains_batch -- one launch of
+nominal_gains_fleet_kernel -- against mppi_nominal_traj_batch followed by mppi_compute_feedback_gains_batch on its outputs, the two
+sides alternating call by call within the run; both sides fill the same caller buffers, as the host layer's state_solution_ /
+control_solution_ are filled, so each includes the copies between those buffers and the staging memory.  The kernel times come from a
+run of their own:  rocprofv3 --kernel-trace --stats -- python tools/fleet_time.py --finish --n 64 --ticks 20
+
     python tools/fleet_time.py --mixed 6-32-32-4 6-64-64-64-64-4 6-129-4 6-256-256-4 [--n 4 16 64] [--K 1920] [--T 100] [--ways abcdA]
 
 A fleet whose handles cycle through the given layer lists (handle i has list i mod the number of lists), one row per n, every
@@ -306,6 +314,64 @@ def nominal_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
     return rows
 
 
+def finish_ms(net, n, K=64, T=100, calls=200, warm=10):
+    """The closing stages of n handles' tick, two ways, each the median wall time of `calls` calls after `warm` warm ones, the two
+    alternating call by call: the fused entry (one launch for the fleet), and the batched replay followed by the batched DDP pass
+    that tracks its outputs.  Every handle replays a warm control sequence from its own state into buffers allocated once."""
+    from autorally_amd import capi
+    sols, states = fleet(net, "auto", n, K, T)
+    try:
+        rng = np.random.RandomState(5)
+        for s in sols:
+            s.set_control_seq(np.stack([rng.uniform(-0.5, 0.5, T), rng.uniform(-0.2, 0.6, T)], axis=1).astype(np.float32))
+        out = [(np.zeros((T, 7), np.float32), np.zeros((T, 2), np.float32)) for _ in sols]
+        fp = capi.C.POINTER(capi.C.c_float)
+        hs = (capi.C.c_void_p * n)(*[s.h for s in sols])
+        st = np.ascontiguousarray(np.stack(states), np.float32)
+        ssp, csp = (fp * n)(*[capi._fp(o[0]) for o in out]), (fp * n)(*[capi._fp(o[1]) for o in out])
+        L = sols[0].L
+
+        def fused():
+            assert L.mppi_nominal_and_gains_batch(hs, capi._fp(st), ssp, csp, n) == capi.OK
+
+        def two():
+            assert L.mppi_nominal_traj_batch(hs, capi._fp(st), ssp, csp, n) == capi.OK
+            assert L.mppi_compute_feedback_gains_batch(hs, capi._fp(st), ssp, csp, n) == capi.OK
+
+        def clock(fn):
+            t0 = time.perf_counter()
+            fn()
+            return time.perf_counter() - t0
+        for _ in range(warm):
+            fused()
+            two()
+        tf, tt, tf2 = [], [], []
+        for _ in range(calls):
+            tf.append(clock(fused))
+            tt.append(clock(two))
+            tf2.append(clock(fused))
+        row = {"net": "-".join(map(str, net)), "n": n, "T": T}
+        row["fused_ms"], row["two_ms"], row["fused_again_ms"] = (1e3 * float(np.median(t)) for t in (tf, tt, tf2))
+        fused()
+        row["fused"] = sols[0].debug_nominal_and_gains_info()
+        return row
+    finally:
+        for s in sols:
+            s.close()
+
+
+def finish_table(nets, ns=(2, 4, 16, 64), T=100, calls=200):
+    rows = []
+    for net in nets:
+        for n in ns:
+            row = finish_ms(net, n, T=T, calls=calls)
+            rows.append(row)
+            print("FLEET FINISH n=%d T=%d net=%s: one call %.4f ms (fused %d; again %.4f ms: A/A %.4f ms)  replay + gains, two calls %.4f ms;  "
+                  "two/one %.2f" % (n, T, row["net"], row["fused_ms"], row["fused"], row["fused_again_ms"],
+                                    abs(row["fused_ms"] - row["fused_again_ms"]), row["two_ms"], row["two_ms"] / row["fused_ms"]), flush=True)
+    return rows
+
+
 def trace_ms(net, n, K=1920, T=100, rollouts=64, calls=100, warm=5):
     """The 64 best sampled trajectories of each of n solved handles, each the median wall time of `calls` calls after `warm` warm
     ones: the batch entry (the largest weights chosen on the device, one trace launch for the fleet) twice -- interleaved, their
@@ -388,6 +454,8 @@ def main():
                     "host replays, n = 2, 4, 16, 64 (mppi_nominal_traj_batch)")
     ap.add_argument("--trace", action="store_true", help="the best 64 sampled trajectories of every handle instead: the batch entry against "
                     "the per-handle calls, n = 4, 16, 64 (mppi_trace_rollouts_batch)")
+    ap.add_argument("--finish", action="store_true", help="the closing stages of the fleet's tick instead: the fused entry against the "
+                    "batched replay followed by the batched gains, n = 2, 4, 16, 64 (mppi_nominal_and_gains_batch)")
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
@@ -397,6 +465,9 @@ def main():
         return
     if a.trace:
         print(json.dumps(trace_table(parse(a.net), a.n or (4, 16, 64), a.K or 1920, a.T, min(a.ticks, 100))))
+        return
+    if a.finish:
+        print(json.dumps(finish_table(parse(a.net), a.n or (2, 4, 16, 64), a.T, a.ticks)))
         return
     a.n = a.n[0] if a.n else 16
     if a.nominal:
