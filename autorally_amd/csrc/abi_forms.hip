@@ -73,6 +73,7 @@ hipError_t one_lds128(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, h
 hipError_t one_lds16(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_lds16(h->net, a, h->num_simds / 4, s); }
 hipError_t one_glb16(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_glb16(h->net, a, h->num_simds / 4, h->glb16_cap, s); }
 hipError_t one_glb44(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_glb44(h->net, a, h->glb44_cap, s); }
+hipError_t one_row32(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_row32(h->net, a, d.arg != 0, s); }  // arg: tree
 hipError_t one_fleet(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_fleet_one(h, a); }  // the fleet's kernel with one instance, on the handle's own stream
 hipError_t one_valu_reg(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_valu_reg(h->hidden, h->n_hidden, a, s); }
 hipError_t one_valu(mppi_handle *h, const FormDesc &d, const RolloutArgs &a, hipStream_t s) { return launch_rollout_valu(h->net, a, s); }
@@ -84,6 +85,7 @@ hipError_t batch_m44(const mppi_handle *h0, const FormDesc &d, const QuadBatchAr
 hipError_t batch_lds44(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_lds44_batch(h0->net, qb, s); }
 hipError_t batch_lds128(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_lds128_batch(h0->net, qb, s); }
 hipError_t batch_glb44(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_glb44_batch(h0->net, qb, h0->glb44_cap, s); }
+hipError_t batch_row32(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_row32_batch(h0->net, qb, d.arg != 0, s); }
 hipError_t batch_bf(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_batch(qb, s); }
 hipError_t batch_bf_row(const mppi_handle *h0, const FormDesc &d, const QuadBatchArgs &qb, hipStream_t s) { return launch_rollout_bf_row_batch(qb, s); }
 // the fleet adapters: the forms of one list / shape / wave count read it from the first handle (fleet_together: it is every handle's)
@@ -133,6 +135,8 @@ constexpr FormDesc kForms[] = {
     {Form::Bf2, Image::Theta, Noise::Never, 0, nullptr, one_bf, 2, {}, nullptr, nullptr, {"basis_funcs25_valu_2w"}, {}},
     {Form::Bf3, Image::Theta, Noise::InKernel, 0, nullptr, one_bf, 3, {batch_bf, false, false, 3}, nullptr, nullptr, {"basis_funcs25_valu_3w"}, {}},
     {Form::BfRow, Image::BfRow, Noise::InKernel, kGate | kByName | kNegateYaw, nullptr, one_bf_row, 0, {batch_bf_row, true, false, 16}, nullptr, nullptr, {"basis_funcs25_row8w"}, {}},
+    {Form::Row32, Image::Row32, Noise::InKernel, kGate | kByName, nullptr, one_row32, 0, {batch_row32, true, true, 16}, nullptr, nullptr, {"valu_row8w", Tag::LayersWidth}, {}},
+    {Form::Row32Tree, Image::Row32, Noise::InKernel, kGate | kByName, nullptr, one_row32, 1, {batch_row32, true, true, 16}, nullptr, nullptr, {"valu_row8w_tree", Tag::LayersWidth}, {}},
     {Form::FleetBf, Image::Theta, Noise::Never, kByName, nullptr, one_fleet, 0, {}, fleet_bf, nullptr, {"basis_funcs25_fleet", Tag::ForcedWaves}, {}},
 };
 static_assert(rows_in_order(kForms, &FormDesc::form), "row i of kForms describes form i");
@@ -200,7 +204,7 @@ static int resident_cap_of(const char *suffix)
 }
 
 // The request names of mppi_set_rollout_variant.  A request is refused by the first of its preconditions that does not hold, in the
-// order of the columns: model kind, shape, K multiple, LDS limit, image present, preparation step.  (Every K multiple divides 64
+// order of the columns: model kind, shape (and its second limit, the last column), K multiple, LDS limit, image present, preparation step.  (Every K multiple divides 64
 // and mppi_create refuses a K that 64 does not divide: that check is a guard no caller can see, whatever its place.)
 namespace {
 using Shape = bool (*)(const mppi_handle *h, Form f);  // f: the form the request would force
@@ -211,6 +215,8 @@ bool lds128_shape(const mppi_handle *h, Form) { return lds128_lds_bytes(h->net) 
 bool lds16_shape(const mppi_handle *h, Form) { return lds16_lds_bytes(h->net) != 0; }
 bool glb16_shape(const mppi_handle *h, Form) { return glb16_supported(h->net); }
 bool glb44_shape(const mppi_handle *h, Form) { return glb44_supported(h->net); }
+bool row32_shape(const mppi_handle *h, Form) { return row32_supported(h->net, true); }
+bool row32_exact_depth(const mppi_handle *h, Form) { return row32_supported(h->net, false); }
 // the image of a form built on request; without parameters yet: mppi_set_nn_params builds it
 int build_image(mppi_handle *h, Form f)
 {
@@ -245,6 +251,8 @@ struct Request {
   int (*prepare)(mppi_handle *h, Form f);
   int waves;                // "fleet_bf_w<N>": the wave count the request forces on the fleet's launch; 0: none
   const char *say;          // the name its refusals speak of; nullptr: its own
+  Shape shape2;             // a second limit on the shape, checked behind `shape`, with its own refusal; nullptr: none
+  const char *shape2_msg;
 };
 const char kRowMsg[] = "row form exists for 6-32x2-4", kM44Msg[] = "m44 form exists for 6-64x2-4 and 6-64x4-4",
            kRow64Msg[] = "row64 form exists for 6-64x2-4 and 6-64x4-4", kOctMsg[] = "oct form exists for 6-64x2-4 and 6-64x4-4",
@@ -253,6 +261,9 @@ const char kRowMsg[] = "row form exists for 6-32x2-4", kM44Msg[] = "m44 form exi
            kLds16Msg[] = "lds16 form needs 6 -> hidden widths 1..128 -> 4 with at least one hidden layer",
            kGlb16Msg[] = "glb16 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer",
            kGlb44Msg[] = "glb44 form needs 6 -> hidden widths 1..256 -> 4 with at least one hidden layer",
+           kRow32Msg[] = "row32 form needs 6 -> one to four hidden widths 1..32 -> 4",
+           kRow32TreeMsg[] = "row32_tree form needs 6 -> one to four hidden widths 1..32 -> 4",
+           kRow32DepthMsg[] = "row32 form keeps the reference's order for at most three hidden layers: the fourth does not fit the registers (row32_tree serves four)",
            kFleetBfK[] = "fleet_bf form needs K to be a multiple of 64";
 constexpr int kNoPref = -1;
 const Request kRequests[] = {
@@ -303,6 +314,12 @@ const Request kRequests[] = {
      nullptr, nullptr, false, prepare_fleet_glb16},
     {"glb44", true, Form::Glb44, Form::Glb44, kNoPref, Gen::Keep, Model::Network, glb44_shape, kGlb44Msg, kRolloutsPerWave,
      "glb44 form needs K to be a multiple of 16", nullptr, nullptr, nullptr, false, build_image},
+    // the row form for every layer list of one to four hidden layers up to 32 wide (narrower layers padded with zeros): the reference's
+    // order in every layer, up to three hidden layers / the output layer as a butterfly
+    {"row32", false, Form::Row32, Form::Row32, kNoPref, Gen::Keep, Model::Network, row32_shape, kRow32Msg, kRolloutsPerWave,
+     "row32 form needs K to be a multiple of 16", nullptr, nullptr, nullptr, false, build_image, 0, nullptr, row32_exact_depth, kRow32DepthMsg},
+    {"row32_tree", false, Form::Row32Tree, Form::Row32Tree, kNoPref, Gen::Keep, Model::Network, row32_shape, kRow32TreeMsg, kRolloutsPerWave,
+     "row32_tree form needs K to be a multiple of 16", nullptr, nullptr, nullptr, false, build_image},
     // the vector-ALU arm of the 64-wide A/B
     {"row64", false, Form::Row64R16, Form::Row64R16, kNoPref, Gen::Keep, Model::Any, form_shape, kRow64Msg},
     {"row64_r16", false, Form::Row64R16, Form::Row64R16, kNoPref, Gen::Keep, Model::Any, form_shape, kRow64Msg},
@@ -362,6 +379,7 @@ int mppi_set_rollout_variant(mppi_handle *h, const char *name)
   }
   const Form f = h->basis ? r->bf : r->net;
   if (r->shape && !r->shape(h, f)) return refuse(r->shape_msg);
+  if (r->shape2 && !r->shape2(h, f)) return refuse(r->shape2_msg);
   if (r->k_msg && h->K % r->k_multiple != 0) return refuse(r->k_msg);
   if (r->lds_bytes && r->lds_bytes(h->net) > r->lds_limit()) {
     snprintf(msg, sizeof(msg), "%s form: the weights of this layer list need %zu bytes of LDS per %s, %zu are available", r->name,

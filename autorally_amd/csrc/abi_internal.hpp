@@ -73,6 +73,9 @@ enum class Form : int {
   Bf1, Bf2, Bf3,                    // rollout_bf.hip: basis-function model, waves per 64 rollouts
   BfRow,                            // rollout_bf_row.hip: basis-function model in the row form's group (four dynamics waves + four
                                     // riders per 16 rollouts), the bits of Bf1..3; by name only ("bf_row")
+  Row32, Row32Tree,                 // rollout_row32.hip: the row form (row_group.hpp) for any list of one to four hidden layers up to 32 wide, a
+                                    // narrower layer padded with zeros; Row32: the reference's order in every layer, at most three hidden
+                                    // layers; Tree: butterfly output layer; by name only ("row32", "row32_tree")
   FleetBf,                          // rollout_fleet_bf.hip: the workgroups of Bf1..3 with the argument block read from device memory and eps from
                                     // the stand-alone generator: up to 64 handles of the basis-function model share a launch; by name only
                                     // ("fleet_bf", "fleet_bf_w1..3"), no gated form
@@ -94,6 +97,8 @@ enum class Image : int {
   Lds16,      // the same lists: image of rollout_lds16.hip (and of rollout_fleet16.hip)
   Glb16,      // image of rollout_glb16.hip: only a handle that asked for "glb16" has one (built at that call)
   Glb44,      // image of rollout_glb44.hip: only a handle that asked for "glb44" has one (built at that call)
+  Row32,      // one to four hidden layers up to 32 wide: the row form's register image for the list (rollout_row32.hip); only a handle
+              // that asked for "row32" / "row32_tree" has one (built at that call)
   Trace,      // network model: k-major image of rollout_trace.hip (every layer's W transposed)
   Count
 };

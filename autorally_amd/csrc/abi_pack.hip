@@ -142,6 +142,60 @@ std::vector<float> pack_row_weights(const std::vector<float> &theta)
   return out;
 }
 
+// Register image of the row form for a layer list of one to four hidden layers up to 32 wide (rollout_row32.hip; row_group.hpp:
+// row_load<NHH>, NHH = hidden layers - 1): pack_row_weights' register order with 16 entries per hidden-to-hidden layer, at the
+// entries of row_pack_layout(NHH) -- w1; the hidden-to-hidden layers; the exact output layer; the pre-scaled hidden biases, two
+// layers per entry; b3; the tree's three entries.  A neuron or an input a layer does not have (width < 32) is weight 0, bias 0;
+// every float that holds no weight or bias is exactly 0.  For 6-32-32-4 this is pack_row_weights' image float for float.
+std::vector<float> pack_row32_weights(const std::vector<float> &theta, const NetDesc &net)
+{
+  std::vector<float> out((size_t)row32_pack_floats(net), 0.0f);
+  if (out.empty()) return out;
+  const int NH = net.n_layers - 2, H = 32;
+  const RowPackLayout E = row_pack_layout(NH - 1);
+  const float *Wl[8], *Bl[8];
+  {
+    const float *p = theta.data();
+    for (int l = 0; l <= NH; l++) {
+      Wl[l] = p;
+      Bl[l] = p + (size_t)net.layers[l + 1] * net.layers[l];
+      p += (size_t)net.layers[l + 1] * net.layers[l] + net.layers[l + 1];
+    }
+  }
+  // weight (n, k) of weight layer l, bias n: 0 where the list has no such neuron or input
+  auto w = [&](int l, int n, int k) { return (n < net.layers[l + 1] && k < net.layers[l]) ? Wl[l][(size_t)n * net.layers[l] + k] : 0.0f; };
+  auto b = [&](int l, int n) { return n < net.layers[l + 1] ? Bl[l][n] : 0.0f; };
+  for (int p = 0; p < 16; p++) {
+    const int j0 = 2 * p, j1 = 2 * p + 1, o0 = 2 * (p & 1), o1 = o0 + 1;
+    auto entry = [&](int i) { return &out[((size_t)i * 16 + p) * 4]; };
+    for (int i = 0; i < 3; i++) {
+      float *e = entry(i);
+      e[0] = w(0, j0, 2 * i); e[1] = w(0, j1, 2 * i); e[2] = w(0, j0, 2 * i + 1); e[3] = w(0, j1, 2 * i + 1);
+    }
+    for (int i = 0; i < H / 2; i++) {
+      for (int l = 1; l < NH; l++) {
+        float *e = entry(E.w2 + (l - 1) * (H / 2) + i);
+        e[0] = w(l, j0, 2 * i); e[1] = w(l, j1, 2 * i); e[2] = w(l, j0, 2 * i + 1); e[3] = w(l, j1, 2 * i + 1);
+      }
+      float *f = entry(E.w3 + i);
+      f[0] = w(NH, o0, 2 * i); f[1] = w(NH, o1, 2 * i); f[2] = w(NH, o0, 2 * i + 1); f[3] = w(NH, o1, 2 * i + 1);
+    }
+    for (int l = 0; l < NH; l++) {
+      float *e = entry(E.bias + l / 2) + 2 * (l & 1);
+      e[0] = b(l, j0) * kTanhScale; e[1] = b(l, j1) * kTanhScale;
+    }
+    float *c = entry(E.b3);
+    c[0] = b(NH, o0); c[1] = b(NH, o1);
+    // tree form (row_out_tree): this lane's own two activations into the four outputs, output (p >> 2) ^ i at position i
+    const int o = p >> 2;
+    float *t0 = entry(E.tree), *t1 = entry(E.tree + 1), *t2 = entry(E.tree + 2);
+    t0[0] = w(NH, o, j0); t0[1] = w(NH, o ^ 1, j0); t0[2] = w(NH, o, j1); t0[3] = w(NH, o ^ 1, j1);
+    t1[0] = w(NH, o ^ 2, j0); t1[1] = w(NH, o ^ 3, j0); t1[2] = w(NH, o ^ 2, j1); t1[3] = w(NH, o ^ 3, j1);
+    t2[0] = b(NH, o);
+  }
+  return out;
+}
+
 // Per-lane image of the basis-function row form (rollout_bf_row.hip: bf_row_load; the layout is written down at
 // kBfRowSlots, mppi_kernels.hpp): lane p = 4 j + y of a rollout's DPP row runs y-thread y of output j, slot m of the lane is
 // basis function i = y + 4 m.  The divisors are those of basis_funcs_from (basis_funcs.hpp; car_bfs.cuh:44-120), 0 = the basis
@@ -536,6 +590,8 @@ constexpr ImageDesc kImages[] = {
      [](H h) { return pack_glb16_weights(h->theta, h->net); }, true, "glb16 image size"},
     {Image::Glb44, [](H h) { return !h->basis && glb44_supported(h->net); }, [](H h) { return (size_t)glb44_pack_floats(h->net); },
      [](H h) { return pack_glb44_weights(h->theta, h->net); }, true, "glb44 image size"},
+    {Image::Row32, [](H h) { return !h->basis && row32_supported(h->net, true); }, [](H h) { return (size_t)row32_pack_floats(h->net); },
+     [](H h) { return pack_row32_weights(h->theta, h->net); }, true, "row32 image size"},
     {Image::Trace, [](H h) { return !h->basis; }, num_params, [](H h) { return pack_trace_weights(h->theta, h->net); }, false, nullptr},
 };
 static_assert(rows_in_order(kImages, &ImageDesc::id), "row i of kImages describes image i");

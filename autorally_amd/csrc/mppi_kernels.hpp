@@ -161,6 +161,28 @@ hipError_t launch_rollout_lds44(const NetDesc &net, const RolloutArgs &a, hipStr
 // two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
 hipError_t launch_rollout_lds44_batch(const NetDesc &net, const QuadBatchArgs &b, hipStream_t stream);
 
+// rollout_row32.hip: the row group (row_group.hpp; rollout_row.hip's form) for ANY layer list 6 -> 1 to 4 hidden widths 1..32 -> 4: every
+// hidden layer runs as a 32-wide one (neurons it does not have: weight 0, bias 0), NHH = hidden layers - 1 hidden-to-hidden chains per
+// step.  Exact ("row32": the reference's order in every layer, the bits of the other exact forms; up to three hidden layers -- the
+// fourth does not fit the registers) and tree ("row32_tree": row_out_tree's output layer, the bits of "row_tree" on 6-32-32-4).  A list
+// of two hidden layers runs rollout_row.hip's kernels.  a.wpack = pack_row32_weights (abi_pack.hip), entries of 16 lanes x 16 B:
+struct RowPackLayout {
+  int w2, w3, bias, b3, tree, entries;  // first entry of: the hidden-to-hidden layers (16 each), the exact output layer (16), the
+                                        // hidden biases (two layers per entry), b3, the tree's three; the image's entries
+};
+constexpr RowPackLayout row_pack_layout(int nhh)
+{
+  const int w3 = 3 + 16 * nhh, bias = w3 + 16, b3 = bias + (nhh + 2) / 2;
+  return RowPackLayout{3, w3, bias, b3, b3 + 1, b3 + 4};
+}
+static_assert(row_pack_layout(1).bias == 35 && row_pack_layout(1).entries == 40, "NHH = 1: pack_row_weights' image");
+constexpr int kRow32MaxHidden = 4, kRow32MaxHiddenExact = 3;
+bool row32_supported(const NetDesc &net, bool tree);
+int row32_pack_floats(const NetDesc &net);
+hipError_t launch_rollout_row32(const NetDesc &net, const RolloutArgs &a, bool tree, hipStream_t stream);
+// two instances of the SAME layer list in one launch: b.n == 2, grid (groups of the larger instance, 2)
+hipError_t launch_rollout_row32_batch(const NetDesc &net, const QuadBatchArgs &b, bool tree, hipStream_t stream);
+
 // rollout_lds128.hip: the lds44 group (m44_group.hpp) for ANY layer list 6 -> hidden widths 1..128 -> 4 whose image fits one workgroup's LDS:
 // a hidden layer is one or two halves of 64 neurons with an accumulator each, its inputs one or two transposed activation
 // sets walked k ascending (the reference's order: bit-identical to the other exact forms); a.wpack = pack_lds128_weights

@@ -73,6 +73,9 @@ extern "C" {
  *    image and lists with the argument block AND the layer list read from device memory; 2..64 handles forced to it -- of ANY
  *    layer lists and caps -- share the launches of mppi_compute_control_batch as "fleet16" handles do; no new export, no gated
  *    form, the automatic choice does not change. */
+/*    (still 5) + rollout variants "row32", "row32_tree", names "valu_row8w_l<N>_w<W>" / "valu_row8w_tree_l<N>_w<W>": the row form
+ *    for every layer list of one to four hidden layers up to 32 wide; by name only, gated form and pair launch; no new export, the
+ *    automatic choice does not change. */
 /*    (still 5) + mppi_compute_feedback_gains_batch, mppi_debug_ddp_info, mppi_debug_device_tanhf (the DDP feedback gains of a fleet
  *    in one launch; compatible additions, the single and the pair call are unchanged). */
 /*    (still 5) + mppi_nominal_traj_batch, mppi_debug_nominal_info (the nominal trajectories of a fleet in one launch; compatible
@@ -225,7 +228,7 @@ int mppi_synchronize(mppi_handle *h);
  * -- states is [n][7], handles[i] solves from states + 7 i.  Where the handles' rollout kernels can share a launch
  * (network model, same layer list and num_iters, all groups of 16 rollouts together at most one per CU: 2 x K=1920 on
  * 256 CUs; the forms that have a batched kernel: the four-wavefront form and the row forms for n <= 4, the automatic
- * "m44" form of 64-wide nets and "lds44" / "lds128" / "glb44" -- forced on every handle, the whole layer list (and "glb44"'s cap) equal -- for n == 2; the
+ * "m44" form of 64-wide nets and "lds44" / "lds128" / "glb44" / "row32" / "row32_tree" -- forced on every handle, the whole layer list (and "glb44"'s cap) equal -- for n == 2; the
  * basis-function model's three-wavefront form, or its "bf_row" form forced on both handles of a pair under the row forms' rule:
  * 2 x K=1920 shares a launch, 2 x K=2560 does not) the n solves cost TWO kernel launches in all, on a stream of the library
  * shared by the device's handles; otherwise ("m44_chain", three m44 handles ...) this is n calls of
@@ -255,7 +258,7 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
  * mppi_compute_control[_async] to supply the state -- that call does not launch, it writes its state, the host's U and hist into
  * the gate and opens it.  May be called with a solve pending (the armed one goes behind it) or idle.  MPPI_ERR_UNSUPPORTED
  * (nothing enqueued, handle unchanged) where the handle's form / configuration has no gated form: num_iters > 1, the
- * basis-function model in any form but "bf_row", forms other than the row forms, the automatic m44 form, "lds44", "lds128", "glb44", "bf_row"
+ * basis-function model in any form but "bf_row", forms other than the row forms, the automatic m44 form, "lds44", "lds128", "glb44", "row32", "row32_tree", "bf_row"
  * and the automatic multi4-tree form with its generator kernel, stage timing, capture, explicit noise.  Results are bit for bit those of the same calls without mppi_arm;
  * the slide stride between ticks may vary, and mppi_set_control_seq / _hist between arm and compute go through the gate.
  * Every call that changes what the armed solve would compute (model, cost, costmap, limits, seed, noise, variant, timing,
@@ -267,7 +270,7 @@ int mppi_compute_control_batch(mppi_handle *const *handles, const float *states,
 int mppi_arm(mppi_handle *h, double max_wait_s);
 /* The same for the solves of one mppi_compute_control_batch[_async](handles, states, n) call: the shared one-launch form where
  * the batch would use it and the form has a gated batched kernel (the row forms; two handles of the automatic "m44" form or of
- * "lds44" or of "lds128" or of "glb44" or of "bf_row"), otherwise each handle armed on its own where it can be
+ * "lds44" or of "lds128" or of "glb44" or of "row32" / "row32_tree" or of "bf_row"), otherwise each handle armed on its own where it can be
  * (MPPI_ERR_UNSUPPORTED if one could not be; the others stay armed).  Only a batch call with the same handles in the same order
  * opens the gates; any other call on one of them calls the whole armed launch off first. */
 int mppi_arm_batch(mppi_handle *const *handles, int n, double max_wait_s);
@@ -554,6 +557,24 @@ int mppi_get_stage_times(mppi_handle *h, mppi_stage_times *out);
  *     with the same whole layer list and the same cap share one launch (mppi_compute_control_batch, mppi_arm_batch);
  *     MPPI_ERR_UNSUPPORTED for the basis-function model and a list without a hidden layer, MPPI_ERR_INVALID ("unknown variant")
  *     for a malformed suffix
+ *     "row32" valu_row8w_l<hidden layers>_w<widest hidden layer>: the ROW form ("row_exact"'s group: the network on the vector ALU, a
+ *     rollout on a 16-lane DPP row, every weight in registers) for ANY layer list 6 -> ONE TO THREE hidden widths 1..32 -> 4; a
+ *     hidden layer narrower than 32 runs as a 32-wide one whose missing neurons have weight 0 and bias 0 (the padded inputs come
+ *     last in every chain: the reference's order and the bits of "valu_lds" / "lds44"; only the sign of a pre-activation that is
+ *     exactly zero can differ); on 6-32-32-4 the bits and the kernels of "row_exact".  The latency form to ask for on these lists:
+ *     K = 1920, T = 100 (us) 6-32-4 32, 6-16-24-4 41, 6-32-32-32-4 55 beside "lds44" 65 / 88 / 156.  By name only;
+ *     the device image is built at this call and held only by handles that asked for the form; it HAS a gated form (mppi_arm,
+ *     chained mppi_control_ticks) and two handles forced to it with the same whole layer list share one launch
+ *     (mppi_compute_control_batch, mppi_arm_batch; three or four solve one by one).  From three hidden layers on a group's
+ *     registers leave room for ONE group per CU: K above 16 x CUs runs in rounds -- correct, and not what the form is for.
+ *     MPPI_ERR_UNSUPPORTED for the basis-function model, a hidden width above 32, no or more than four hidden layers, and for FOUR
+ *     hidden layers (the fourth layer's weights do not fit the registers in this order: "row32_tree" serves such a list)
+ *   re-associated, by name only
+ *     "row32_tree" valu_row8w_tree_l<hidden layers>_w<widest hidden layer>: "row32" with the output layer as "row_tree"'s butterfly,
+ *     for ONE TO FOUR hidden widths 1..32: the reference's order in the hidden layers, inside the 1e-4 tolerance on the controls as
+ *     "row_tree" is; on 6-32-32-4 the bits and the kernels of "row_tree".  K = 1920, T = 100 (us): 6-32-4 26, 6-16-24-4 33,
+ *     6-32-32-32-4 47, 6-32x4-4 61 -- 6-32x4-4 runs "quad" automatically at 118, and has no gated form there.  Image, gated form,
+ *     pair launch, residency and refusals as "row32", four hidden layers accepted
  *   A/B arms and cross-checks (never chosen automatically)
  *     "valu" valu_reg_lds (lane = rollout, the independent implementation every parity test also runs; config 4's untuned
  *     vector-ALU reference), "valu_lds" (the generic kernel on a standard shape), "row64" = "row64_r16"
