@@ -71,6 +71,7 @@ SYMBOLS = [
     "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
     "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
     "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info",
+    "mppi_closed_loop_ticks_batch", "mppi_debug_closed_loop_info", "mppi_debug_closed_loop_check",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -86,7 +87,8 @@ UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_to
                        "mppi_compute_feedback_gains_batch", "mppi_debug_ddp_info", "mppi_debug_device_tanhf",
                        "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
                        "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
-                       "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info")
+                       "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info",
+                       "mppi_closed_loop_ticks_batch", "mppi_debug_closed_loop_info", "mppi_debug_closed_loop_check")
 
 _lib = None
 
@@ -198,6 +200,11 @@ def lib():
             fpp = C.POINTER(fp)
             L.mppi_nominal_and_gains_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int]
             L.mppi_debug_nominal_and_gains_info.argtypes = [hp, C.POINTER(C.c_int)]
+        if hasattr(L, "mppi_closed_loop_ticks_batch"):  # added without a version step, like mppi_debug_launch_info
+            ip, fpp = C.POINTER(C.c_int), C.POINTER(fp)
+            L.mppi_closed_loop_ticks_batch.argtypes = [C.POINTER(hp), fp, C.c_int, C.c_int, C.c_int, fpp, fpp, fpp]
+            L.mppi_debug_closed_loop_info.argtypes = [hp, ip, ip]
+            L.mppi_debug_closed_loop_check.argtypes = [fp, fp, C.c_int, C.c_int, ip]
         if hasattr(L, "mppi_trace_rollouts_batch"):  # added without a version step, like mppi_debug_launch_info
             ip, fpp = C.POINTER(C.c_int), C.POINTER(fp)
             ipp = C.POINTER(ip)
@@ -473,6 +480,13 @@ class Solver:
         self._ck(self.L.mppi_debug_nominal_info(self.h, C.byref(on)))
         return on.value
 
+    def debug_closed_loop_info(self):
+        """mppi_debug_closed_loop_info: (on_device, ticks) of the handle's last closed_loop_ticks_batch -- 1 if its ticks were
+        enqueued on the device with the plant step in plant_fleet_kernel, 0 if it ran the loop of public calls; the ticks completed."""
+        on, ticks = C.c_int(-1), C.c_int(-1)
+        self._ck(self.L.mppi_debug_closed_loop_info(self.h, C.byref(on), C.byref(ticks)))
+        return on.value, ticks.value
+
     def debug_nominal_and_gains_info(self):
         """mppi_debug_nominal_and_gains_info: 1 if the handle's last nominal_and_gains_batch ran in the one kernel, 0 if as the two calls."""
         fused = C.c_int(-1)
@@ -669,6 +683,40 @@ def nominal_traj_batch(solvers, states):
     if rc != OK:
         raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
     return out
+
+
+def closed_loop_ticks_batch(solvers, states, n_ticks, stride):
+    """mppi_closed_loop_ticks_batch: n_ticks closed-loop ticks (solve, plant step with the handle's own model, slide) of several
+    Solver objects in one call; on the device without collecting in between where the library can (Solver.debug_closed_loop_info).
+    Returns [(states [n_ticks + 1][7], controls [n_ticks][stride][2], costs [n_ticks])] in the solvers' order; the last row of a
+    solver's states is its final state.  Raises MppiError with every handle's message."""
+    n = len(solvers)
+    if n < 1 or len(states) != n:
+        raise MppiError(ERR_INVALID, "closed_loop_ticks_batch: %d solvers, %d states" % (n, len(states)))
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    nt, sd = max(int(n_ticks), 0), max(int(stride), 0)
+    fp = C.POINTER(C.c_float)
+    st = np.ascontiguousarray(np.stack([_f32(x, (7,)) for x in states]), dtype=np.float32)
+    out = [(np.zeros((nt + 1, 7), np.float32), np.zeros((nt, sd, 2), np.float32), np.zeros((nt,), np.float32)) for _ in solvers]
+    xl, ul, cl = ((fp * n)(*[_fp(o[k]) for o in out]) for k in range(3))
+    rc = solvers[0].L.mppi_closed_loop_ticks_batch(hs, _fp(st), n, int(n_ticks), int(stride), xl, ul, cl)
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
+    return out
+
+
+def debug_closed_loop_check(etas, controls, stride):
+    """mppi_debug_closed_loop_check: the first tick of a device run's logs (etas [n_ticks], controls [n_ticks][stride][2]) whose eta
+    is below 1 or not finite or whose controls are not finite; -1: none.  Needs no device."""
+    etas = np.ascontiguousarray(etas, dtype=np.float32).ravel()
+    controls = np.ascontiguousarray(controls, dtype=np.float32).ravel()
+    if controls.size != etas.size * 2 * int(stride):
+        raise MppiError(ERR_INVALID, "debug_closed_loop_check: controls must be [n_ticks][stride][2]")
+    bad = C.c_int(-2)
+    rc = lib().mppi_debug_closed_loop_check(_fp(etas), _fp(controls), etas.size, int(stride), C.byref(bad))
+    if rc != OK:
+        raise MppiError(rc, "mppi_debug_closed_loop_check")
+    return bad.value
 
 
 def nominal_and_gains_batch(solvers, states, outputs=None):

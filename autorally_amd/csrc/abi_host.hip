@@ -192,7 +192,7 @@ static int ddp_fleet_launch(mppi_handle *const *hs, const float *states, const f
 // The sharing rule of the batched nominal replay, beside ddp_fleet_together: two or more handles of the network model with
 // parameters set and a trace image, all on one device.  Everything else about a controller is data.  (The basis-function model
 // stays on the host: its functions go through powf, which is ulp-sensitive -- the reason ddp_fleet_together gives.)
-static bool nominal_fleet_together(mppi_handle *const *hs, int n)
+bool nominal_fleet_together(mppi_handle *const *hs, int n)
 {
   if (n < 2) return false;
   for (int i = 0; i < n; i++) {

@@ -165,6 +165,8 @@ struct mppi_handle {
   int ddp_on_device = 0;  // the last DDP pass ran in ddp_fleet_kernel (mppi_compute_feedback_gains_batch), not on the host
   int nominal_on_device = 0;  // the last nominal replay ran in nominal_fleet_kernel (mppi_nominal_traj_batch), not on the host
   int nominal_gains_fused = 0;  // the last mppi_nominal_and_gains_batch ran in nominal_gains_fleet_kernel, not as the two calls
+  int closed_loop_on_device = 0, closed_loop_ticks = 0;  // the last mppi_closed_loop_ticks_batch: its ticks were enqueued on the device's batch stream with
+                                                         // the plant step in plant_fleet_kernel (not the loop of public calls); the ticks it completed
   int trace_on_device = 0;  // the last trace ran in the fleet's kernels (mppi_trace_rollouts_batch), not in a launch of the handle's own
   hipStream_t batch_s = nullptr;  // the device's batch stream, looked up once (mppi_compute_control_batch)
   unsigned *d_counter = nullptr;  // [1 + T] arrival counters of the tail kernel
@@ -451,6 +453,12 @@ constexpr int kTraceChunk = 1024;  // rollouts per launch of mppi_trace_rollouts
 // abi_host.hip: the helper thread of the paired host work (mppi_set_host_threads)
 extern std::atomic<int> g_host_threads;
 void host_helper_arm();
+// abi_host.hip: the sharing rule of the batched nominal replay (mppi_nominal_traj_batch; the closed loop of a fleet asks it too)
+bool nominal_fleet_together(mppi_handle *const *hs, int n);
+// abi_solve.hip: the host's check behind a closed-loop run on the device (mppi_closed_loop_ticks_batch) over one handle's logs -- etas
+// [n_ticks], controls [n_ticks][stride][2]: the first tick whose eta is below 1 or not finite or whose applied controls are not
+// finite; -1: none
+int closed_loop_first_bad_tick(const float *etas, const float *controls, int n_ticks, int stride);
 
 // The buffers of a batched host pass: ONE set per purpose and device beside the device's batch stream, grown on demand and never
 // destroyed -- the instances' inputs (pinned staging -> device, one copy), their results (device -> pinned, one copy) and, where

@@ -2,7 +2,8 @@
 // kernel, polling of the host-mapped result block; result getters.  "Enqueue a solve for n >= 1 handles" is written once, as
 // phases (collect, begin_solves, distrust, solve_step, finish_solves: "the phases of a solve" below); three short drivers say
 // how the argument blocks the phases fill reach the device -- enqueue_solve (one handle, its own stream), enqueue_pair (2-4
-// handles, one rollout launch), enqueue_fleet (2-64 handles of a fleet form, three launches).
+// handles, one rollout launch), enqueue_fleet (2-64 handles of a fleet form, three launches).  closed_loop_fleet is enqueue_fleet's
+// tick n_ticks times over with the plant step between two ticks and nothing collected (mppi_closed_loop_ticks_batch).
 #include "abi_internal.hpp"
 
 using namespace mppi;
@@ -1210,6 +1211,298 @@ static int enqueue_fleet(mppi_handle *const *hs, const float *states, int n)
   return MPPI_OK;
 }
 
+// ---- closed-loop ticks of a fleet on the device (mppi_closed_loop_ticks_batch) --------------------------------------------------
+// enqueue_fleet's tick with nothing collected in between: the state stays on the device (plant_fleet_kernel writes it into the
+// NEXT tick's rollout argument block, whose copy is already on the stream in front of it), the tail kernel smooths the device copy
+// of U with the host's bits and leaves it slid, the generator and the argument ring advance without the host.  The host only runs
+// its bookkeeping ahead -- seq, gen_cur, rng_cur, in_cur, the tail's epoch and the minimum-cost tag, as solve_step moves them -- and
+// is held back by nothing but the ring's events.
+static FleetWork g_loop_work[64];
+static std::mutex g_loop_mu[64];  // a device's g_loop_work: held for a whole run, waits included (only another closed-loop run waits for it)
+constexpr int kLoopChunkTicks = 1024;  // ticks per run of the driver: bounds the log buffers, whatever n_ticks is
+
+int closed_loop_first_bad_tick(const float *etas, const float *controls, int n_ticks, int stride)
+{
+  for (int t = 0; t < n_ticks; t++) {
+    if (!(etas[t] >= 1.0f) || !std::isfinite(etas[t])) return t;
+    for (int j = 0; j < 2 * stride; j++)
+      if (!std::isfinite(controls[(size_t)2 * stride * t + j])) return t;
+  }
+  return -1;
+}
+
+// does the tail's slid copy serve the slide of this run (mppi_slide_control_seq's first branch), or does slide_kernel run?
+static bool loop_swaps(const mppi_handle *h, int stride) { return wants_slid_copy(h) && stride == h->cfg.optimization_stride; }
+
+// one handle's pieces of the run's log buffer, in floats from its start
+struct LoopLog {
+  size_t x, u, c, e, end;
+};
+static LoopLog loop_log(int n_ticks, int stride)
+{
+  LoopLog l;
+  l.x = 0;
+  l.u = align4((size_t)7 * (n_ticks + 1));
+  l.c = l.u + align4((size_t)2 * stride * n_ticks);
+  l.e = l.c + align4((size_t)n_ticks);
+  l.end = l.e + align4((size_t)n_ticks);
+  return l;
+}
+
+// The wait for the run's last tick: the sequence number of handle i's result block moves with every tick, and the limit of
+// mppi_set_wait_timeout applies between two moves.  false: no progress for that long.
+static bool wait_for_ticks(mppi_handle *const *hs, int n, hipStream_t S)
+{
+  for (int i = 0; i < n; i++) {
+    const mppi_handle *h = hs[i];
+    const volatile unsigned *word = reinterpret_cast<const volatile unsigned *>(h->h_res) + 4 * (h->T + 1) + 1;
+    unsigned seen = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    auto t0 = std::chrono::steady_clock::now();
+    unsigned long spins = 0;
+    double next_query_s = 0.01;
+    while (seen != h->seq) {
+      __builtin_ia32_pause();
+      const unsigned cur = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+      if (cur != seen) {  // a tick further
+        seen = cur;
+        t0 = std::chrono::steady_clock::now();
+        next_query_s = 0.01;
+        continue;
+      }
+      if ((++spins & 0xFF) != 0) continue;
+      const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (el > h->wait_timeout_s) return false;
+      if (el > next_query_s) {
+        next_query_s = el + 0.01;
+        if (hipStreamQuery(S) == hipSuccess) break;  // drained: wait_pending says what is missing
+      }
+    }
+  }
+  return true;
+}
+
+// n_ticks <= kLoopChunkTicks ticks of a set that is fleet_together and nominal_fleet_together with one iteration, every pending
+// solve collected.  The logs may be NULL as arrays or entry by entry.
+static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, float *const *state_log,
+                             float *const *control_log, float *const *cost_log)
+{
+  mppi_handle *h0 = hs[0];
+  hipStream_t S = nullptr;
+  if (int rc = use_batch_stream(h0, &S)) return rc;
+  const int dev = h0->cfg.device;
+  FleetBlock *fb = fleet_block(dev);
+  if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
+  const FormDesc &fd = form_desc(h0->forced);
+  const LoopLog lg = loop_log(n_ticks, stride);
+  const size_t arg_floats = align4((sizeof(PlantFleetArgs) * (size_t)n + sizeof(float) - 1) / sizeof(float));
+  const size_t in_floats = arg_floats + (size_t)8 * n, out_floats = lg.end * (size_t)n;
+  if (dev < 0 || dev >= 64) return fail(h0, MPPI_ERR_INVALID, "device out of range");
+  // the run's buffers for the whole run; the fleet block only while the run is enqueued: batched solves, replays and DDP passes of
+  // other threads on this device queue behind the run on the stream, their callers do not sit out its waits
+  std::lock_guard<std::mutex> run_lk(g_loop_mu[dev]);
+  std::unique_lock<std::mutex> lk(fb->mu);
+  for (int i = 0; i < n; i++) {
+    hs[i]->closed_loop_on_device = 1;
+    hs[i]->closed_loop_ticks = 0;
+  }
+  FleetWork *w = &g_loop_work[dev];
+  if (in_floats > w->in_cap || out_floats > w->out_cap) {
+    HIPCHK(h0, hipStreamSynchronize(S));  // nothing of an earlier run is behind the buffers
+    HIPCHK(h0, fleet_grow(&w->d_in, &w->h_in, &w->in_cap, in_floats));
+    HIPCHK(h0, fleet_grow(&w->d_out, &w->h_out, &w->out_cap, out_floats));
+  }
+  if (int rc = begin_solves(hs, n, S, true)) return distrust(hs, n, rc);
+  // the plant's argument blocks (sent once) and the state slots behind them
+  PlantFleetArgs *pa = reinterpret_cast<PlantFleetArgs *>(w->h_in);
+  const PlantFleetArgs *d_pa = reinterpret_cast<const PlantFleetArgs *>(w->d_in);
+  for (int i = 0; i < n; i++) {
+    const mppi_handle *h = hs[i];
+    PlantFleetArgs &a = pa[i];
+    a = PlantFleetArgs{};
+    float *o = w->d_out + lg.end * (size_t)i;
+    a.wimg = image(h, Image::Trace);
+    a.U_even = h->d_in;
+    a.U_odd = loop_swaps(h, stride) ? h->d_in_buf[1 - h->in_cur] : h->d_in;
+    a.scal = h->d_scal;
+    a.state = w->d_in + arg_floats + (size_t)8 * i;
+    a.log_x = o + lg.x; a.log_u = o + lg.u; a.log_c = o + lg.c; a.log_e = o + lg.e;
+    a.T = h->T;
+    a.negate_yaw_der = h->cfg.negate_yaw_der ? 1 : 0;
+    a.stride = stride;
+    a.dt = h->dt;
+    for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; }
+    a.net = h->net;
+    memcpy(w->h_in + arg_floats + (size_t)8 * i, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+    w->h_in[arg_floats + (size_t)8 * i + 7] = 0.0f;
+  }
+  hipError_t e = hipMemcpyAsync(w->d_in, w->h_in, sizeof(float) * in_floats, hipMemcpyHostToDevice, S);
+  if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "closed loop: input copy", e));
+  // behind plant step `tick`: the slide of every handle whose slid copy is not simply swapped in (the swap itself is the host's)
+  auto slide_behind_plant = [&]() -> hipError_t {
+    for (int i = 0; i < n; i++) {
+      const mppi_handle *h = hs[i];
+      if (loop_swaps(h, stride)) continue;
+      if (hipError_t es = launch_slide(h->d_in, h->T, stride, h->cfg.init_control[0], h->cfg.init_control[1], S); es != hipSuccess) return es;
+    }
+    return hipSuccess;
+  };
+  static const float no_state[kStateDim] = {0, 0, 0, 0, 0, 0, 0};  // ticks after the first: plant_fleet_kernel writes the block's state
+  TailLaunch tl[kMaxFleet];
+  for (int tick = 0; tick < n_ticks; tick++) {
+    unsigned char *host = nullptr;
+    e = arg_block_stage(fb->args, &host);  // the run's one wait: the copy out of this slot, four ticks ago
+    if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "fleet argument block", e));
+    RolloutArgs *ra = reinterpret_cast<RolloutArgs *>(host);
+    NoiseFleetDesc *nd = reinterpret_cast<NoiseFleetDesc *>(host + fleet_noise_offset(n));
+    if (fd.fleet_net) {
+      FleetGlbNet *nets = reinterpret_cast<FleetGlbNet *>(host + fleet_net_offset(n));
+      for (int i = 0; i < n; i++) nets[i] = fd.fleet_net(hs[i]);
+    }
+    for (int i = 0; i < n; i++) {
+      mppi_handle *h = hs[i];
+      if (tick > 0) {  // begin_solves' share of a tick
+        h->seq = next_seq(h);
+        forget_solve_state(h);
+      }
+      if (int rc = solve_step(h, tick == 0 ? states + (size_t)MPPI_STATE_DIM * i : no_state, 0, true, S, Eps::Fleet, ra[i], tl[i], &nd[i]))
+        return distrust(hs, n, rc);
+    }
+    fill_solve_tail_fleet(host + fleet_tail_offset(n), tl, n);
+    e = arg_block_send(fb->args, fleet_bytes(n, fd.fleet_net != nullptr), S);
+    unsigned char *dev_blk = fb->args.d;
+    // the plant step of the tick before, BEHIND this tick's argument copy: its state lands in the block the rollout reads
+    if (e == hipSuccess && tick > 0) e = launch_plant_fleet(pa, d_pa, reinterpret_cast<RolloutArgs *>(dev_blk), n, tick - 1, S);
+    if (e == hipSuccess && tick > 0) e = slide_behind_plant();
+    if (e == hipSuccess) e = launch_noise_fleet(nd, reinterpret_cast<const NoiseFleetDesc *>(dev_blk + fleet_noise_offset(n)), n, S);
+    if (e == hipSuccess)
+      e = fd.fleet(hs, ra, reinterpret_cast<const RolloutArgs *>(dev_blk), reinterpret_cast<const FleetGlbNet *>(dev_blk + fleet_net_offset(n)), n, S);
+    if (e == hipSuccess) e = launch_solve_tail_fleet(tl, n, dev_blk + fleet_tail_offset(n), S);
+    if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "closed loop: fleet launch", e));
+    for (int i = 0; i < n; i++) {
+      mppi_handle *h = hs[i];
+      h->launch_instances = n;
+      h->launch_gated = false;
+      // mppi_slide_control_seq's device half, the host's side of it: the slid copy the tail leaves is the next tick's sequence
+      if (loop_swaps(h, stride)) {
+        h->in_cur = 1 - h->in_cur;
+        h->d_in = h->d_in_buf[h->in_cur];
+      }
+    }
+  }
+  e = launch_plant_fleet(pa, d_pa, nullptr, n, n_ticks - 1, S);
+  if (e == hipSuccess) e = slide_behind_plant();
+  if (e == hipSuccess) e = hipMemcpyAsync(w->h_out, w->d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, S);
+  for (int i = 0; i < n && e == hipSuccess; i++)  // the smoothed and slid [U | hist]: what the host's copies become
+    e = hipMemcpyAsync(hs[i]->h_in, hs[i]->d_in, sizeof(float) * (2 * (size_t)hs[i]->T + 4), hipMemcpyDeviceToHost, S);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(S);
+    return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "closed loop: plant step / result copy", e));
+  }
+  for (int i = 0; i < n; i++) {  // finish_solves' share: the last tick is a pending solve like any other
+    hs[i]->explicit_iters = 0;
+    hs[i]->pending = true;
+    hs[i]->pending_timed = false;
+  }
+  lk.unlock();  // everything is enqueued: the waits below hold only the run's own buffers
+  if (!wait_for_ticks(hs, n, S)) {
+    // as a solve whose wait ran out of time: nothing waits for the run again until its device work has drained
+    for (int i = 0; i < n; i++) {
+      mppi_handle *h = hs[i];
+      h->pending = false;
+      h->u_dirty = true;
+      h->slid_valid = false;
+      h->timed_out = true;
+      h->no_result = true;
+      fail(h, MPPI_ERR_HIP, "closed loop: timed out waiting for a tick");
+    }
+    return MPPI_ERR_HIP;
+  }
+  int rc = MPPI_OK;
+  for (int i = 0; i < n; i++) {  // (smooths the host's U from the result block with the OLD history: replaced below)
+    const int r = wait_pending(hs[i]);
+    if (r && !rc) rc = r;
+  }
+  e = hipStreamSynchronize(S);
+  if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "closed loop: synchronise", e));
+  // the host's check behind the run: the ticks ran on after a bad one
+  int bad_tick = -1, bad_handle = -1;
+  for (int i = 0; i < n; i++) {
+    const float *o = w->h_out + lg.end * (size_t)i;
+    const int t = closed_loop_first_bad_tick(o + lg.e, o + lg.u, n_ticks, stride);
+    if (t >= 0 && (bad_tick < 0 || t < bad_tick)) {
+      bad_tick = t;
+      bad_handle = i;
+    }
+  }
+  const int good_ticks = bad_tick >= 0 ? bad_tick : (rc ? 0 : n_ticks);
+  for (int i = 0; i < n; i++) {
+    const float *o = w->h_out + lg.end * (size_t)i;
+    if (state_log && state_log[i]) {
+      memcpy(state_log[i], states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+      memcpy(state_log[i] + 7, o + lg.x + 7, sizeof(float) * 7 * (size_t)good_ticks);
+    }
+    if (control_log && control_log[i]) memcpy(control_log[i], o + lg.u, sizeof(float) * 2 * (size_t)stride * good_ticks);
+    if (cost_log && cost_log[i]) memcpy(cost_log[i], o + lg.c, sizeof(float) * (size_t)good_ticks);
+    hs[i]->closed_loop_on_device = 1;
+    hs[i]->closed_loop_ticks = good_ticks;
+  }
+  if (bad_tick >= 0 || rc) {  // (the caller puts the host's U / history and the states back)
+    for (int i = 0; i < n; i++) hs[i]->no_result = true;
+    if (bad_tick >= 0) {
+      char msg[160];
+      snprintf(msg, sizeof(msg), "closed loop: tick %d of handle %d produced a non-finite normaliser or controls", bad_tick, bad_handle);
+      fail(hs[bad_handle], MPPI_ERR_HIP, msg);
+      rc = fail(h0, MPPI_ERR_HIP, msg);
+    }
+    return distrust(hs, n, rc);
+  }
+  for (int i = 0; i < n; i++) {
+    mppi_handle *h = hs[i];
+    const float *o = w->h_out + lg.end * (size_t)i;
+    memcpy(h->U.data(), h->h_in, sizeof(float) * 2 * (size_t)h->T);
+    memcpy(h->hist.data(), h->h_in + 2 * h->T, sizeof(float) * 4);
+    h->u_dirty = false;
+    h->slid_valid = false;  // as behind mppi_slide_control_seq
+    // the last solve's state: the log's row n_ticks - 1 -- row 0 is the host's (the kernel writes rows 1 .. n_ticks)
+    note_solve_state(h, n_ticks == 1 ? states + (size_t)MPPI_STATE_DIM * i : o + lg.x + (size_t)7 * (n_ticks - 1), true);
+    memcpy(states + (size_t)MPPI_STATE_DIM * i, o + lg.x + (size_t)7 * n_ticks, sizeof(float) * kStateDim);
+  }
+  return MPPI_OK;
+}
+
+// the loop of public calls itself: the reference of the device path, and what every other set runs
+static int closed_loop_reference(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, float *const *state_log,
+                                 float *const *control_log, float *const *cost_log)
+{
+  std::vector<std::vector<float>> xs(n), us(n);
+  std::vector<float *> xp(n), up(n);
+  for (int i = 0; i < n; i++) {
+    xs[i].resize((size_t)hs[i]->T * kStateDim);
+    us[i].resize((size_t)hs[i]->T * kControlDim);
+    xp[i] = xs[i].data();
+    up[i] = us[i].data();
+    hs[i]->closed_loop_on_device = 0;
+    hs[i]->closed_loop_ticks = 0;
+  }
+  for (int tick = 0; tick < n_ticks; tick++) {
+    int rc = mppi_compute_control_batch(hs, states, n);
+    if (rc == MPPI_OK) rc = mppi_nominal_traj_batch(hs, states, xp.data(), up.data(), n);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+      float *s = states + (size_t)MPPI_STATE_DIM * i;
+      if (state_log && state_log[i]) memcpy(state_log[i] + (size_t)7 * tick, s, sizeof(float) * kStateDim);
+      if (control_log && control_log[i]) memcpy(control_log[i] + (size_t)2 * stride * tick, up[i], sizeof(float) * 2 * (size_t)stride);
+      if (cost_log && cost_log[i]) cost_log[i][tick] = hs[i]->traj_cost;
+      memcpy(s, xp[i] + (size_t)7 * stride, sizeof(float) * kStateDim);
+      if (state_log && state_log[i]) memcpy(state_log[i] + (size_t)7 * (tick + 1), s, sizeof(float) * kStateDim);
+      rc = mppi_slide_control_seq(hs[i], stride);
+      if (rc) return rc;
+      hs[i]->closed_loop_ticks = tick + 1;
+    }
+  }
+  return MPPI_OK;
+}
+
 static bool armed_as_batch(mppi_handle *const *hs, int n)
 {
   for (int i = 0; i < n; i++) {
@@ -1323,6 +1616,73 @@ int mppi_control_ticks_batch(mppi_handle *const *hs, const float *states, int n,
       if (rc) return rc;
     }
   }
+  return MPPI_OK;
+}
+
+int mppi_closed_loop_ticks_batch(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, float *const *state_log,
+                                 float *const *control_log, float *const *cost_log)
+{
+  // mppi_nominal_traj_batch's order: every argument, then every handle's readiness, then pending and armed solves; only then a move
+  if (!hs || !states || n < 1 || n_ticks < 1) return MPPI_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!hs[i]) return MPPI_ERR_INVALID;
+    for (int q = 0; q < i; q++)
+      if (hs[q] == hs[i]) return fail(hs[i], MPPI_ERR_INVALID, "the same handle twice in one batch");
+  }
+  for (int i = 0; i < n; i++)
+    if (stride < 1 || stride >= hs[i]->T) return fail(hs[i], MPPI_ERR_INVALID, "closed loop: stride must be in [1, T)");
+  for (int i = 0; i < n; i++)
+    if (const int rc = check_ready(hs[i])) return rc;
+  if (const int rc = collect(hs, n)) return rc;
+  for (int i = 0; i < n; i++) DISARM(hs[i]);
+  bool on_device = fleet_together(hs, n) && nominal_fleet_together(hs, n) && hs[0]->cfg.num_iters == 1;
+  for (int i = 0; i < n && on_device; i++) on_device = hs[i]->explicit_iters == 0;
+  // MPPI_CLOSED_LOOP_DEVICE=0 (tools only, read at every call): the loop of public calls for every set -- tools/fleet_time.py
+  // --closed-loop times the two against each other in one process
+  if (const char *sw = getenv("MPPI_CLOSED_LOOP_DEVICE"); sw && atoi(sw) == 0) on_device = false;
+  if (!on_device) return closed_loop_reference(hs, states, n, n_ticks, stride, state_log, control_log, cost_log);
+  std::vector<float *> xl(n, nullptr), ul(n, nullptr), cl(n, nullptr);
+  // what the host holds before the call: all of it comes back where a tick turns out bad, in whichever piece of a long run
+  std::vector<std::vector<float>> keep_U(n), keep_hist(n);
+  for (int i = 0; i < n; i++) {
+    keep_U[i] = hs[i]->U;
+    keep_hist[i] = hs[i]->hist;
+  }
+  const std::vector<float> keep_states(states, states + (size_t)MPPI_STATE_DIM * n);
+  for (int at = 0; at < n_ticks; at += kLoopChunkTicks) {  // (a long run: its logs come back chunk by chunk)
+    for (int i = 0; i < n; i++) {
+      xl[i] = (state_log && state_log[i]) ? state_log[i] + (size_t)7 * at : nullptr;
+      ul[i] = (control_log && control_log[i]) ? control_log[i] + (size_t)2 * stride * at : nullptr;
+      cl[i] = (cost_log && cost_log[i]) ? cost_log[i] + at : nullptr;
+    }
+    const int rc = closed_loop_fleet(hs, states, n, std::min(kLoopChunkTicks, n_ticks - at), stride, xl.data(), ul.data(), cl.data());
+    for (int i = 0; i < n; i++) hs[i]->closed_loop_ticks += at;
+    if (rc) {  // the host's copies go back, and the next solve uploads them (an earlier piece has moved the device copy)
+      for (int i = 0; i < n; i++) {
+        hs[i]->U = keep_U[i];
+        hs[i]->hist = keep_hist[i];
+        hs[i]->u_dirty = true;
+        hs[i]->slid_valid = false;
+      }
+      memcpy(states, keep_states.data(), sizeof(float) * keep_states.size());
+      return rc;
+    }
+  }
+  return MPPI_OK;
+}
+
+int mppi_debug_closed_loop_info(const mppi_handle *h, int *on_device, int *ticks)
+{
+  if (!h || !on_device || !ticks) return MPPI_ERR_INVALID;
+  *on_device = h->closed_loop_on_device;
+  *ticks = h->closed_loop_ticks;
+  return MPPI_OK;
+}
+
+int mppi_debug_closed_loop_check(const float *etas, const float *controls, int n_ticks, int stride, int *bad_tick)
+{
+  if (!etas || !controls || !bad_tick || n_ticks < 1 || stride < 1) return MPPI_ERR_INVALID;
+  *bad_tick = closed_loop_first_bad_tick(etas, controls, n_ticks, stride);
   return MPPI_OK;
 }
 

@@ -487,6 +487,29 @@ inline size_t nominal_fleet_out_floats(int T) { return (size_t)9 * T; }
 bool nominal_fleet_image_in_lds(const NetDesc &net);
 hipError_t launch_nominal_fleet(const NominalFleetArgs *h_inst, const NominalFleetArgs *d_inst, int n, hipStream_t stream);
 
+// plant_fleet.hip: the plant step of a fleet's closed loop on the device (mppi_closed_loop_ticks_batch) -- the first `stride` steps of
+// nominal_fleet_kernel's replay (its text, its bits) from the controller's device state slot with the controls the tail kernel of
+// tick `tick` smoothed, one workgroup per controller, the argument blocks an array in device memory that is sent ONCE per run: what
+// changes from tick to tick is the launch's `tick` (which of the two [U | hist] buffers, which log rows).
+struct PlantFleetArgs {
+  const float *wimg;    // pack_trace_weights: every W transposed
+  const float *U_even;  // [T][2] the smoothed sequence of the run's even ticks (not yet slid) ...
+  const float *U_odd;   // ... and of its odd ticks (the other buffer where the tail's slid copy is swapped in, else the same one)
+  const float *scal;    // the tail's scalars: [1] eta, [2] the trajectory cost
+  float *state;         // [7] the controller's device state slot: in, and out
+  float *log_x;         // [ticks + 1][7]: row tick + 1 receives the new state (row 0 is the host's)
+  float *log_u;         // [ticks][stride][2]: the clamped controls the plant applied
+  float *log_c;         // [ticks]: the trajectory cost
+  float *log_e;         // [ticks]: eta
+  int T, negate_yaw_der, stride;
+  float dt;
+  float u_lo[2], u_hi[2];
+  NetDesc net;
+};
+// d_ra: the fleet's rollout argument blocks in device memory -- instance i's RolloutArgs::state (a by-value field at offset 0) receives
+// the new state too -- or nullptr (behind the run's last tick)
+hipError_t launch_plant_fleet(const PlantFleetArgs *h_inst, const PlantFleetArgs *d_inst, RolloutArgs *d_ra, int n, int tick, hipStream_t stream);
+
 // nominal_gains_fleet.hip: the nominal replay AND the DDP pass that tracks it (mppi_nominal_and_gains_batch) of n <= kMaxFleet
 // independent controllers in one launch, one workgroup per controller: the replay runs on wave 1 while wave 0 runs the pass's
 // initial rollout; the targets never leave the device.

@@ -84,6 +84,9 @@ extern "C" {
  *    on the device; compatible additions, mppi_trace_rollouts and mppi_top_rollouts are unchanged). */
 /*    (still 5) + mppi_nominal_and_gains_batch, mppi_debug_nominal_and_gains_info (a fleet's nominal trajectories and the feedback
  *    gains that track them in one launch; compatible additions, the two batch calls it equals are unchanged). */
+/*    (still 5) + mppi_closed_loop_ticks_batch, mppi_debug_closed_loop_info, mppi_debug_closed_loop_check (closed-loop ticks of a
+ *    fleet -- solve, plant step, slide -- enqueued on the device without collecting in between; compatible additions, every call it
+ *    equals is unchanged). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -458,6 +461,58 @@ int mppi_nominal_and_gains_batch(mppi_handle *const *handles, const float *state
 /* Test / tooling hook: *fused = 1 if the handle's most recent mppi_nominal_and_gains_batch ran in the one kernel, 0 if as the two
  * calls (or none yet).  MPPI_ERR_INVALID for a NULL argument. */
 int mppi_debug_nominal_and_gains_info(const mppi_handle *h, int *fused);
+
+/* Closed-loop ticks of a whole fleet in one call: handles[n]; states [n][7] holds every controller's start state and receives its
+ * final one.  The plant is the handle's own dynamics model.  The call is EXACTLY this loop of public calls, which is its reference:
+ *     for tick in 0 .. n_ticks-1:
+ *         mppi_compute_control_batch(handles, s, n)
+ *         mppi_nominal_traj_batch(handles, s, state_seqs, control_seqs, n)
+ *         log s_i, control_seqs_i[0 .. stride), the trajectory cost of handle i
+ *         s_i = state_seqs_i[stride]
+ *         mppi_slide_control_seq(handle_i, stride)
+ * with 1 <= stride < min T_i.  The logs are optional (each array, and each entry, may be NULL): state_log[i] receives
+ * [n_ticks + 1][7] (row 0 the start state, row t + 1 the state after tick t), control_log[i] [n_ticks][stride][2] (the clamped
+ * controls the plant applied), cost_log[i] the n_ticks trajectory costs.  Afterwards every handle is bit for bit where the loop
+ * leaves it: the host's U and history, mppi_get_results and mppi_get_applied_controls of the last tick, the generator stream, the
+ * device copy of U (the next solve uploads nothing).
+ * Device path: 2..64 handles that share the launches of mppi_compute_control_batch (all forced to "fleet16", all to
+ * "fleet_multi4" or all to "fleet_glb16") AND the launch of mppi_nominal_traj_batch, with num_iters == 1 and no explicit noise,
+ * stage timing or capture: all n_ticks are enqueued on the device's batch stream and the host waits for none of them -- per tick
+ * the argument copy, the plant step of the tick before (plant_fleet_kernel: the first `stride` steps of nominal_fleet_kernel's
+ * replay, its bits, from a state that stays on the device), the generator, the rollout and the tail, which smooths and slides the
+ * device copy of U.  Only the ring of four staging slots of the argument block holds the host back.  The last tick is collected
+ * as any solve is; the host's U / history are then read back from the device copy and the logs arrive in one copy.
+ * mppi_set_wait_timeout applies to every tick of progress (the sequence number in the result block), not to the whole run.
+ * Fallback: every other set -- n = 1, more than 64 handles, a basis-function handle, mixed or latency forms, num_iters > 1,
+ * explicit noise, several devices, timing or capture -- runs the loop above literally, with its bits; such a set takes the host's
+ * sinf / cosf in the plant wherever mppi_nominal_traj_batch replays on the host.  mppi_debug_closed_loop_info tells which it was.
+ * Order of work, as in mppi_nominal_traj_batch: every argument is checked (MPPI_ERR_INVALID: a NULL array or handle, n < 1,
+ * n_ticks < 1, a handle listed twice, stride outside [1, min T_i)), then every handle's readiness (MPPI_ERR_STATE), then pending
+ * solves of the set are collected and its armed handles disarmed; only then does anything move.
+ * Failure (device path): the ticks run on behind a bad one, so the host checks after the run.  A tick whose eta is below 1 or not
+ * finite, or whose applied controls are not finite, makes the call return MPPI_ERR_HIP; mppi_last_error of handles[0] and of the
+ * handle names the tick and the handle.  EVERY handle of the set is then distrusted: the host's U / history are what they were
+ * before the call, the next solve uploads them again, `states` is unchanged, the logs hold the ticks before the failure
+ * (mppi_debug_closed_loop_info counts them), the result getters refuse until a solve completes, and the generator streams are where
+ * the run left them.  A run longer than 1024 ticks is enqueued and collected in pieces of 1024 (a failure in a later piece still
+ * puts U, history and `states` back to what they were before the CALL); the staging ring's wait inside a piece is not bounded by
+ * mppi_set_wait_timeout.
+ * Other threads: the device's fleet argument block is held only while a piece is being enqueued, not through its waits -- batched
+ * solves, replays and DDP passes of other handles on the device queue behind the run on the batch stream; a second closed-loop call
+ * on the device waits for the first.
+ * Tools only: the environment variable MPPI_CLOSED_LOOP_DEVICE=0, read at every call, sends every set through the loop of public
+ * calls (tools/fleet_time.py --closed-loop times the two against each other in one process); not meant for applications. */
+int mppi_closed_loop_ticks_batch(mppi_handle *const *handles, float *states /* n x 7, in: start, out: final */, int n, int n_ticks,
+                                 int stride, float *const *state_log /* [i]: (n_ticks+1) x 7, or NULL */,
+                                 float *const *control_log /* [i]: n_ticks x stride x 2 (clamped, applied), or NULL */,
+                                 float *const *cost_log /* [i]: n_ticks trajectory costs, or NULL */);
+/* Test / tooling hook: *on_device = 1 if the handle's most recent mppi_closed_loop_ticks_batch ran the device path, 0 if the loop of
+ * public calls (or none yet); *ticks = the ticks that call completed.  MPPI_ERR_INVALID for a NULL argument. */
+int mppi_debug_closed_loop_info(const mppi_handle *h, int *on_device, int *ticks);
+/* Test hook: the host's check behind a device run over one handle's logs -- etas [n_ticks], controls [n_ticks][stride][2]:
+ * *bad_tick = the first tick whose eta is below 1 or not finite or whose controls are not finite, -1 if there is none.  No device
+ * is needed.  MPPI_ERR_INVALID for a NULL argument, n_ticks < 1 or stride < 1. */
+int mppi_debug_closed_loop_check(const float *etas, const float *controls, int n_ticks, int stride, int *bad_tick);
 
 /* Host threads the library may use for the host-side work of a tick that comes in pairs (mppi_nominal_traj_pair,
  * mppi_compute_feedback_gains_pair): 1 (default) = the caller's thread only (the reference's optimizer thread does everything,

@@ -48,7 +48,13 @@ forced to "glb16", handle by handle, (c) "auto", (d) "fleet16" (one list of hidd
 
 The 64 best sampled trajectories of every handle of a solved fleet: mppi_trace_rollouts_batch -- the largest weights chosen on the
 device, one trace launch, one result copy -- against the same handles one by one (mppi_top_rollouts + mppi_trace_rollouts); the
-batch entry is timed twice, interleaved with the per-handle calls: the A/A spread of the visit."""
+batch entry is timed twice, interleaved with the per-handle calls: the A/A spread of the visit.
+
+    python tools/fleet_time.py --closed-loop [--n 64] [--K 1920] [--T 100] [--ticks 200] [--net ...] [--variant fleet_multi4]
+
+Closed-loop ticks of the fleet (solve, plant step, slide): mppi_closed_loop_ticks_batch with all ticks enqueued on the device against
+(r) the reference loop inside the library (the same entry with MPPI_CLOSED_LOOP_DEVICE=0) and (p) the reference loop driven from
+Python; every run from the same start (controls reset, generator reseeded), the ways alternating, the median of three runs each."""
 import argparse
 import json
 import os
@@ -437,6 +443,70 @@ def trace_table(nets, ns=(4, 16, 64), K=1920, T=100, calls=100):
     return rows
 
 
+def closed_loop_ms(net, variant, n=64, K=1920, T=100, ticks=200, stride=1, runs=3, warm=20):
+    """-> a row: ms per tick of the device loop, of the reference loop inside the library and of the reference loop from Python
+    (the median of `runs` runs each, alternating), and what mppi_debug_closed_loop_info says of the first two."""
+    from autorally_amd import capi
+    sols, states = fleet(net, variant, n, K, T)
+    try:
+        def restart():
+            for i, s in enumerate(sols):
+                s.reset_controls()
+                s.seed(1000 + i, 0)
+            return [st.copy() for st in states]
+
+        def library(device):
+            st = restart()
+            os.environ["MPPI_CLOSED_LOOP_DEVICE"] = "1" if device else "0"
+            try:
+                t0 = time.perf_counter()
+                capi.closed_loop_ticks_batch(sols, st, ticks, stride)
+                return (time.perf_counter() - t0) / ticks, sols[0].debug_closed_loop_info()
+            finally:
+                os.environ.pop("MPPI_CLOSED_LOOP_DEVICE", None)
+
+        def python():
+            st = restart()
+            t0 = time.perf_counter()
+            for _ in range(ticks):
+                capi.compute_control_batch(sols, st)
+                seqs = capi.nominal_traj_batch(sols, st)
+                st = [x[0][stride].copy() for x in seqs]
+                for s in sols:
+                    s.slide_control_seq(stride)
+            return (time.perf_counter() - t0) / ticks
+
+        capi.closed_loop_ticks_batch(sols, restart(), warm, stride)
+        td, tr, tp, info_d, info_r = [], [], [], None, None
+        for _ in range(runs):
+            d, info_d = library(True)
+            r, info_r = library(False)
+            td.append(d)
+            tr.append(r)
+            tp.append(python())
+        row = {"net": "-".join(map(str, net)), "variant": variant, "n": n, "K": K, "T": T, "ticks": ticks, "stride": stride}
+        row["device_ms"], row["reference_ms"], row["python_ms"] = (1e3 * float(np.median(t)) for t in (td, tr, tp))
+        row["device_runs_ms"], row["reference_runs_ms"] = [1e3 * t for t in td], [1e3 * t for t in tr]
+        row["on_device"], row["reference_on_device"] = info_d[0], info_r[0]
+        return row
+    finally:
+        for s in sols:
+            s.close()
+
+
+def closed_loop_table(nets, variant=None, n=64, K=1920, T=100, ticks=200):
+    rows = []
+    for net in nets:
+        v = variant or ("fleet_multi4" if net == [6, 32, 32, 4] else "fleet16")
+        row = closed_loop_ms(net, v, n, K, T, ticks)
+        rows.append(row)
+        print("FLEET CLOSED LOOP n=%d K=%d T=%d net=%s %s, %d ticks: device loop %.4f ms per tick (on_device %d)  reference loop in the library "
+              "%.4f ms  from Python %.4f ms;  reference/device %.2f" % (n, K, T, row["net"], v, ticks, row["device_ms"], row["on_device"],
+                                                                      row["reference_ms"], row["python_ms"], row["reference_ms"] / row["device_ms"]),
+              flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="*", default=None, help="handles (default 16; --mixed: 4 16 64, one row each)")
@@ -456,10 +526,16 @@ def main():
                     "the per-handle calls, n = 4, 16, 64 (mppi_trace_rollouts_batch)")
     ap.add_argument("--finish", action="store_true", help="the closing stages of the fleet's tick instead: the fused entry against the "
                     "batched replay followed by the batched gains, n = 2, 4, 16, 64 (mppi_nominal_and_gains_batch)")
+    ap.add_argument("--closed-loop", action="store_true", help="closed-loop ticks of the fleet instead: all ticks enqueued on the device "
+                    "against the reference loop inside the library and from Python (mppi_closed_loop_ticks_batch)")
+    ap.add_argument("--variant", default=None, help="--closed-loop: the fleet form (default fleet_multi4 for 6-32-32-4, else fleet16)")
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
     parse = lambda names: [[int(x) for x in s.split("-")] for s in names]  # noqa: E731
+    if a.closed_loop:
+        print(json.dumps(closed_loop_table(parse(a.net), a.variant, a.n[0] if a.n else 64, a.K or 1920, a.T, a.ticks)))
+        return
     if a.mixed:
         print(json.dumps(mixed_table(parse(a.mixed), a.n or (4, 16, 64), a.K or 1920, a.T, a.ticks, a.warm, a.ways or "abcdA")))
         return
