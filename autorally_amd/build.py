@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmppi_hip.so")
-SOURCES = ["mppi_abi.hip", "abi_forms.hip", "abi_pack.hip", "abi_solve.hip", "abi_host.hip", "abi_trace.hip", "rollout_mfma.hip", "rollout_multi.hip", "rollout_oct.hip", "rollout_row.hip", "rollout_row32.hip", "rollout_row64.hip", "rollout_m44.hip", "rollout_lds44.hip", "rollout_lds128.hip", "rollout_lds16.hip", "rollout_fleet16.hip", "rollout_fleet_multi.hip", "rollout_glb16.hip", "rollout_glb44.hip", "rollout_valu.hip", "rollout_trace.hip", "ddp_fleet.hip", "nominal_fleet.hip", "nominal_gains_fleet.hip", "plant_fleet.hip", "solve_kernels.hip",
+SOURCES = ["mppi_abi.hip", "abi_forms.hip", "abi_pack.hip", "abi_solve.hip", "abi_host.hip", "abi_trace.hip", "rollout_mfma.hip", "rollout_multi.hip", "rollout_oct.hip", "rollout_row.hip", "rollout_row32.hip", "rollout_row64.hip", "rollout_m44.hip", "rollout_lds44.hip", "rollout_lds128.hip", "rollout_lds16.hip", "rollout_fleet16.hip", "rollout_fleet_multi.hip", "rollout_glb16.hip", "rollout_glb44.hip", "rollout_valu.hip", "rollout_trace.hip", "ddp_fleet.hip", "nominal_fleet.hip", "nominal_gains_fleet.hip", "plant_fleet.hip", "plant_drive_fleet.hip", "solve_kernels.hip",
            "noise_mrg32k3a.hip", "rollout_bf.hip", "rollout_fleet_bf.hip", "rollout_bf_row.hip", "ddp_feedback.cpp"]
 HEADERS = ["abi_internal.hpp", "mppi_device.hpp", "mfma_net.hpp", "group_roles.hpp", "m44_core.hpp", "m44_group.hpp", "multi_group.hpp", "row_group.hpp", "wave16_step.hpp", "wave16_image.hpp", "mppi_kernels.hpp", "noise_device.hpp", "ddp_feedback.hpp", "basis_funcs.hpp", "bf_device.hpp", "bf_group.hpp", "bf_row_device.hpp", "host_net.hpp", "tanhf_vec.hpp", "tanhf_scalar.hpp", "ddp_fleet_device.hpp", "nominal_fleet_device.hpp", "wave_net.hpp", os.path.join("..", "..", "include", "mppi_hip.h")]
 # -ffp-contract=off: every FMA in the kernels is explicit (see csrc/mppi_device.hpp)

@@ -72,6 +72,8 @@ SYMBOLS = [
     "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
     "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info",
     "mppi_closed_loop_ticks_batch", "mppi_debug_closed_loop_info", "mppi_debug_closed_loop_check",
+    "mppi_set_plant_model", "mppi_debug_plant_model_info", "mppi_plant_drive_batch", "mppi_debug_plant_drive_info",
+    "mppi_debug_plant_drive_host", "mppi_closed_loop_sim_batch",
 ]
 
 ABI2_SYMBOLS = ("mppi_debug_inject_handover_fault", "mppi_savitsky_golay", "mppi_set_costmap_transform",
@@ -88,7 +90,9 @@ UNVERSIONED_SYMBOLS = ("mppi_debug_launch_info", "mppi_trace_rollouts", "mppi_to
                        "mppi_nominal_traj_batch", "mppi_debug_nominal_info",
                        "mppi_trace_rollouts_batch", "mppi_debug_trace_info",
                        "mppi_nominal_and_gains_batch", "mppi_debug_nominal_and_gains_info",
-                       "mppi_closed_loop_ticks_batch", "mppi_debug_closed_loop_info", "mppi_debug_closed_loop_check")
+                       "mppi_closed_loop_ticks_batch", "mppi_debug_closed_loop_info", "mppi_debug_closed_loop_check",
+                       "mppi_set_plant_model", "mppi_debug_plant_model_info", "mppi_plant_drive_batch", "mppi_debug_plant_drive_info",
+                       "mppi_debug_plant_drive_host", "mppi_closed_loop_sim_batch")
 
 _lib = None
 
@@ -205,6 +209,15 @@ def lib():
             L.mppi_closed_loop_ticks_batch.argtypes = [C.POINTER(hp), fp, C.c_int, C.c_int, C.c_int, fpp, fpp, fpp]
             L.mppi_debug_closed_loop_info.argtypes = [hp, ip, ip]
             L.mppi_debug_closed_loop_check.argtypes = [fp, fp, C.c_int, C.c_int, ip]
+        if hasattr(L, "mppi_plant_drive_batch"):  # added without a version step, like mppi_debug_launch_info
+            ip, fpp = C.POINTER(C.c_int), C.POINTER(fp)
+            L.mppi_set_plant_model.argtypes = [hp, ip, C.c_int, fp, C.c_size_t, C.c_int]
+            L.mppi_debug_plant_model_info.argtypes = [hp, ip]
+            L.mppi_plant_drive_batch.argtypes = [C.POINTER(hp), fp, fpp, fpp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fpp]
+            L.mppi_debug_plant_drive_info.argtypes = [hp, ip]
+            L.mppi_debug_plant_drive_host.argtypes = [ip, C.c_int, fp, C.c_size_t, C.c_int, C.c_float, fp, fp, fp, fp, fp, fp,
+                                                      C.c_int, C.c_int, C.c_int, fp, fp]
+            L.mppi_closed_loop_sim_batch.argtypes = [C.POINTER(hp), fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fpp, fpp, fpp]
         if hasattr(L, "mppi_trace_rollouts_batch"):  # added without a version step, like mppi_debug_launch_info
             ip, fpp = C.POINTER(C.c_int), C.POINTER(fp)
             ipp = C.POINTER(ip)
@@ -487,6 +500,29 @@ class Solver:
         self._ck(self.L.mppi_debug_closed_loop_info(self.h, C.byref(on), C.byref(ticks)))
         return on.value, ticks.value
 
+    def set_plant_model(self, layers=None, theta=None, negate_yaw_der=False):
+        """mppi_set_plant_model: the network of the handle's plant (plant_drive_batch, closed_loop_sim_batch); layers=None and
+        theta=None clear it -- the plant is then the handle's own network."""
+        if layers is None and theta is None:
+            self._ck(self.L.mppi_set_plant_model(self.h, None, 0, None, 0, 0))
+            return
+        ls = np.ascontiguousarray(layers, dtype=np.int32).reshape(-1)
+        th = _f32(theta).ravel()
+        self._ck(self.L.mppi_set_plant_model(self.h, ls.ctypes.data_as(C.POINTER(C.c_int)), ls.size, _fp(th), th.size,
+                                             int(bool(negate_yaw_der))))
+
+    def debug_plant_model_info(self):
+        """mppi_debug_plant_model_info: the layer count of the handle's plant model, 0 without one."""
+        nl = C.c_int(-1)
+        self._ck(self.L.mppi_debug_plant_model_info(self.h, C.byref(nl)))
+        return nl.value
+
+    def debug_plant_drive_info(self):
+        """mppi_debug_plant_drive_info: 1 if the handle's last plant_drive_batch ran in plant_drive_fleet_kernel, 0 if in the host text."""
+        on = C.c_int(-1)
+        self._ck(self.L.mppi_debug_plant_drive_info(self.h, C.byref(on)))
+        return on.value
+
     def debug_nominal_and_gains_info(self):
         """mppi_debug_nominal_and_gains_info: 1 if the handle's last nominal_and_gains_batch ran in the one kernel, 0 if as the two calls."""
         fused = C.c_int(-1)
@@ -700,6 +736,73 @@ def closed_loop_ticks_batch(solvers, states, n_ticks, stride):
     out = [(np.zeros((nt + 1, 7), np.float32), np.zeros((nt, sd, 2), np.float32), np.zeros((nt,), np.float32)) for _ in solvers]
     xl, ul, cl = ((fp * n)(*[_fp(o[k]) for o in out]) for k in range(3))
     rc = solvers[0].L.mppi_closed_loop_ticks_batch(hs, _fp(st), n, int(n_ticks), int(stride), xl, ul, cl)
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
+    return out
+
+
+def plant_drive_batch(solvers, states, seqs, periods, substeps, feedback=False, outputs=None):
+    """mppi_plant_drive_batch: `periods` control periods of `substeps` plant steps of several Solver objects' plants
+    (Solver.set_plant_model; else the solver's own network) under the drive law, in one call (one launch per 64 where the library
+    can share it: Solver.debug_plant_drive_info).  seqs[i]: (state_seq [T][7], control_seq [T][2]) as the nominal calls deliver
+    them; with feedback the gains are each solver's current DDP result.  Returns (states_out [n][7], [applied [periods *
+    substeps][2]]); outputs: that pair to fill (a caller that checks what a refused call wrote).  Raises MppiError with every
+    handle's message."""
+    n = len(solvers)
+    if n < 1 or len(states) != n or len(seqs) != n:
+        raise MppiError(ERR_INVALID, "plant_drive_batch: %d solvers, %d states, %d sequences" % (n, len(states), len(seqs)))
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    st = np.ascontiguousarray(np.stack([_f32(x, (7,)) for x in states]), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    keep = [(_f32(x, (s.T, 7)), _f32(u, (s.T, 2))) for s, (x, u) in zip(solvers, seqs)]
+    xsp, usp = (fp * n)(*[_fp(k[0]) for k in keep]), (fp * n)(*[_fp(k[1]) for k in keep])
+    steps = max(int(periods), 0) * max(int(substeps), 0)
+    if outputs is None:
+        outputs = (np.zeros((n, 7), np.float32), [np.zeros((steps, 2), np.float32) for _ in solvers])
+    app = (fp * n)(*[_fp(a) for a in outputs[1]])
+    rc = solvers[0].L.mppi_plant_drive_batch(hs, _fp(st), xsp, usp, n, int(periods), int(substeps), int(bool(feedback)), _fp(outputs[0]), app)
+    if rc != OK:
+        raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
+    return outputs
+
+
+def debug_plant_drive_host(layers, theta, negate_yaw_der, dt, u_lo, u_hi, x, state_seq, control_seq, feedback, periods, substeps):
+    """mppi_debug_plant_drive_host: the host text of the drive law for a network given by value: (state_out [7], applied
+    [periods * substeps][2]).  feedback: [T][2][7] or None.  Needs no device."""
+    ls = np.ascontiguousarray(layers, dtype=np.int32).reshape(-1)
+    th = _f32(theta).ravel()
+    us = _f32(control_seq)
+    T = us.shape[0]
+    us = us.reshape(T, 2)
+    xs = _f32(state_seq, (T, 7)) if state_seq is not None else None
+    K = _f32(feedback, (T, 2, 7)) if feedback is not None else None
+    out = np.zeros(7, np.float32)
+    app = np.zeros((max(int(periods), 0) * max(int(substeps), 0), 2), np.float32)
+    rc = lib().mppi_debug_plant_drive_host(ls.ctypes.data_as(C.POINTER(C.c_int)), ls.size, _fp(th), th.size, int(bool(negate_yaw_der)),
+                                           float(np.float32(dt)), _fp(_f32(u_lo, (2,))), _fp(_f32(u_hi, (2,))), _fp(_f32(x, (7,))),
+                                           _fp(xs) if xs is not None else None, _fp(us), _fp(K) if K is not None else None, T,
+                                           int(periods), int(substeps), _fp(out), _fp(app))
+    if rc != OK:
+        raise MppiError(rc, "mppi_debug_plant_drive_host")
+    return out, app
+
+
+def closed_loop_sim_batch(solvers, states, n_ticks, stride, substeps, feedback=False):
+    """mppi_closed_loop_sim_batch: n_ticks closed-loop ticks of several Solver objects against their plants (Solver.set_plant_model)
+    under the drive law -- solve, nominal replay (with the gains where feedback is on), `stride` periods of `substeps` plant steps,
+    slide -- in one call; on the device without collecting in between where the library can (Solver.debug_closed_loop_info).
+    Returns [(states [n_ticks + 1][7], controls [n_ticks][stride * substeps][2], costs [n_ticks])] in the solvers' order.  Raises
+    MppiError with every handle's message."""
+    n = len(solvers)
+    if n < 1 or len(states) != n:
+        raise MppiError(ERR_INVALID, "closed_loop_sim_batch: %d solvers, %d states" % (n, len(states)))
+    hs = (C.c_void_p * n)(*[s.h for s in solvers])
+    nt, per = max(int(n_ticks), 0), max(int(stride), 0) * max(int(substeps), 0)
+    fp = C.POINTER(C.c_float)
+    st = np.ascontiguousarray(np.stack([_f32(x, (7,)) for x in states]), dtype=np.float32)
+    out = [(np.zeros((nt + 1, 7), np.float32), np.zeros((nt, per, 2), np.float32), np.zeros((nt,), np.float32)) for _ in solvers]
+    xl, ul, cl = ((fp * n)(*[_fp(o[k]) for o in out]) for k in range(3))
+    rc = solvers[0].L.mppi_closed_loop_sim_batch(hs, _fp(st), n, int(n_ticks), int(stride), int(substeps), int(bool(feedback)), xl, ul, cl)
     if rc != OK:
         raise MppiError(rc, "; ".join(m for m in (s.L.mppi_last_error(s.h).decode() for s in solvers) if m))
     return out

@@ -2,7 +2,9 @@
 // feedback gains (:402-445), and the helper thread that takes one of a pair (mppi_set_host_threads); the DDP passes of a whole
 // fleet in one launch of ddp_fleet_kernel (mppi_compute_feedback_gains_batch) and its nominal replays in one launch of
 // nominal_fleet_kernel (mppi_nominal_traj_batch), or both in one launch of nominal_gains_fleet_kernel
-// (mppi_nominal_and_gains_batch): the entries here that compute on the device.
+// (mppi_nominal_and_gains_batch): the entries here that compute on the device.  A plant of its own per handle
+// (mppi_set_plant_model) and its drive law -- the host text plant_drive_host beside the nominal replay, and the plants of a whole
+// fleet in one launch of plant_drive_fleet_kernel (mppi_plant_drive_batch).
 #include "abi_internal.hpp"
 
 #include <stdexcept>
@@ -303,9 +305,318 @@ static int nominal_gains_fleet_launch(mppi_handle *const *hs, const float *state
   return rc;
 }
 
+// ---- a plant of its own (mppi_set_plant_model, mppi_plant_drive_batch) ------------------------------------------------------------
+static FleetWork g_plant_drive_work[64];  // mppi_plant_drive_batch -> plant_drive_fleet_kernel
+
+const NetDesc &plant_net_of(const mppi_handle *h) { return h->have_plant ? h->plant_net : h->net; }
+static int plant_negate_of(const mppi_handle *h) { return h->have_plant ? h->plant_negate : (h->cfg.negate_yaw_der ? 1 : 0); }
+static const float *plant_image_of(const mppi_handle *h) { return h->have_plant ? h->d_plant_img : image(h, Image::Trace); }
+
+// the largest image a layer list of mppi_create can have: 6 -> 256 x 6 -> 4
+constexpr size_t kPlantImageMaxFloats = (size_t)(kNetIn + 1) * 256 + (size_t)(MPPI_MAX_LAYERS - 3) * 257 * 256 + (size_t)257 * kNetOut;
+
+// Is a fitting image copied to LDS?  One step reads every weight once: the copy would be a second pass.  From two steps on the
+// copy is read back `steps` times from LDS instead of from the L2.  MPPI_PLANT_DRIVE_LDS=0 / 1 (tools only, read at
+// every call): never / whenever it fits -- tools/fleet_time.py --plant-drive measures the two.
+static bool plant_drive_wants_lds(const NetDesc &net, int steps)
+{
+  if (!plant_drive_image_in_lds(net)) return false;
+  if (const char *sw = getenv("MPPI_PLANT_DRIVE_LDS")) return atoi(sw) != 0;
+  return steps >= 2;
+}
+
+void plant_drive_fill(const mppi_handle *h, int periods, int substeps, int feedback, PlantDriveArgs &a)
+{
+  a.wimg = plant_image_of(h);
+  a.net = plant_net_of(h);
+  a.negate_yaw_der = plant_negate_of(h);
+  a.periods = periods;
+  a.substeps = substeps;
+  a.feedback = feedback ? 1 : 0;
+  a.img_lds = plant_drive_wants_lds(a.net, periods * substeps) ? 1 : 0;
+  a.dt_sub = h->dt / (float)substeps;
+  for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; }
+  for (int j = 0; j < kPlantDriveMaxSubsteps; j++) a.a[j] = j < substeps ? (double)j / (double)substeps : 0.0;
+}
+
+// The drive law of include/mppi_hip.h on the host, statement for statement what plant_drive_fleet_kernel computes; only sinf /
+// cosf of the heading are glibc's floats here and the rounded double results there.  model(s, u0, u1, sd): the plant's derivative
+// rows 2 .. 6 (the yaw rate's sign and the dynamics); xs [.. periods + 1][7], us [.. periods + 1][2] the nominal solution; K
+// [.. periods + 1][2][7] the gains or nullptr (no feedback); x_out [7]; applied [periods * substeps][2] or nullptr.
+template <class Model>
+static void plant_drive_host(Model &&model, float dt, const float *u_lo, const float *u_hi, const float *x0, const float *xs,
+                             const float *us, const float *K, int periods, int substeps, float *x_out, float *applied)
+{
+  const int m = substeps;
+  const float dt_sub = dt / (float)m;
+  float s[kStateDim];
+  for (int i = 0; i < kStateDim; i++) s[i] = x0[i];
+  for (int q = 0; q < periods * m; q++) {
+    const int lo = q / m, j = q % m, hi = lo + 1;
+    double u[2];
+    float xd[kStateDim], k[2 * kStateDim];
+    if (j == 0) {  // nothing is interpolated: row hi is not read
+      for (int c = 0; c < 2; c++) u[c] = (double)us[2 * lo + c];
+      if (K) {
+        for (int i = 0; i < kStateDim; i++) xd[i] = xs[7 * lo + i];
+        for (int i = 0; i < 2 * kStateDim; i++) k[i] = K[14 * lo + i];
+      }
+    } else {
+      const double a = (double)j / (double)m, b = 1.0 - a;
+      for (int c = 0; c < 2; c++) u[c] = b * (double)us[2 * lo + c] + a * (double)us[2 * hi + c];
+      if (K) {
+        for (int i = 0; i < kStateDim; i++) xd[i] = (float)(b * (double)xs[7 * lo + i] + a * (double)xs[7 * hi + i]);
+        for (int i = 0; i < 2 * kStateDim; i++) k[i] = (float)(b * (double)K[14 * lo + i] + a * (double)K[14 * hi + i]);
+      }
+    }
+    if (K) {
+      float du[2] = {0.0f, 0.0f};
+      for (int c = 0; c < 2; c++)
+        for (int i = 0; i < kStateDim; i++) du[c] = fmaf(k[7 * c + i], s[i] - xd[i], du[c]);
+      if (!std::isnan(du[0]) && !std::isnan(du[1])) {  // autorally_plant.cpp:243-246: a NaN correction leaves the feed-forward
+        u[0] += (double)du[0];
+        u[1] += (double)du[1];
+      }
+    }
+    float ap[2];
+    for (int c = 0; c < 2; c++) {  // nom_clamp with the HANDLE's limits (the reference clamps to +-1)
+      const float v = (float)u[c];
+      ap[c] = v < u_lo[c] ? u_lo[c] : (v > u_hi[c] ? u_hi[c] : v);
+    }
+    if (applied) {
+      applied[2 * q] = ap[0];
+      applied[2 * q + 1] = ap[1];
+    }
+    const float c = cosf(s[2]), sn = sinf(s[2]);
+    float sd[kStateDim];
+    sd[0] = fmaf(c, s[4], -(sn * s[5]));
+    sd[1] = fmaf(sn, s[4], c * s[5]);
+    model(s, ap[0], ap[1], sd);
+    for (int i = 0; i < kStateDim; i++) s[i] = fmaf(sd[i], dt_sub, s[i]);
+  }
+  for (int i = 0; i < kStateDim; i++) x_out[i] = s[i];
+}
+
+// the network plant: mppi_nominal_traj's statements
+static auto net_plant(HostNetFma &net, int negate)
+{
+  return [&net, negate](const float *s, float u0, float u1, float *sd) {
+    sd[2] = negate ? -s[6] : s[6];
+    const float nin6[6] = {s[3], s[4], s[5], s[6], u0, u1};
+    net.forward(nin6, sd + 3);
+  };
+}
+
+// one handle's drive on the host: the plant set for it, or its own model (which may be the basis-function model)
+static void plant_drive_host_handle(mppi_handle *h, const float *x0, const float *xs, const float *us, const float *K, int periods,
+                                    int substeps, float *x_out, float *applied)
+{
+  if (h->basis) {  // GeneralizedLinear::updateState (generalized_linear.cu:140-167), yaw rate always negated
+    plant_drive_host([h](const float *s, float u0, float u1, float *sd) {
+      float phi[kNumBfs];
+      sd[2] = -s[6];
+      basis_funcs(s, u0, u1, phi);
+      basis_dynamics(h->theta.data(), phi, sd + 3);
+    }, h->dt, h->u_lo, h->u_hi, x0, xs, us, K, periods, substeps, x_out, applied);
+    return;
+  }
+  plant_drive_host(net_plant(h->have_plant ? h->plant_hnet : h->hnet, plant_negate_of(h)), h->dt, h->u_lo, h->u_hi, x0, xs, us, K, periods,
+                   substeps, x_out, applied);
+}
+
+// The sharing rule, as nominal_fleet_together: two or more handles of the network model with parameters set and a plant image,
+// all on one device.  Layer lists (the controller's and the plant's), T, hz and limits are data.
+bool plant_drive_together(mppi_handle *const *hs, int n)
+{
+  if (n < 2) return false;
+  for (int i = 0; i < n; i++) {
+    const mppi_handle *h = hs[i];
+    if (h->basis || !h->have_nn || !plant_image_of(h) || h->cfg.device != hs[0]->cfg.device) return false;
+  }
+  return true;
+}
+
+static size_t drive_in_floats(int periods, int feedback)
+{
+  const size_t rows = (size_t)periods + 1;
+  return 8 + align4(2 * rows) + (feedback ? align4(7 * rows) + 14 * rows : 0);
+}
+
+// The handles of a plant_drive_together set: one input copy (states, the first periods + 1 rows of the sequences and gains),
+// launches of up to kMaxFleet, one result copy, one synchronise; the caller's buffers are written only after all of it succeeded.
+static int plant_drive_launch(mppi_handle *const *hs, const float *states, const float *const *xs, const float *const *us, int n, int periods,
+                              int substeps, int feedback, float *states_out, float *const *applied_log)
+{
+  const size_t rows = (size_t)periods + 1, steps = (size_t)periods * substeps;
+  const size_t off_u = 8, off_x = off_u + align4(2 * rows), off_k = off_x + align4(7 * rows);
+  FleetPass p{hs, n, "batched plant drive"};
+  int rc = p.open(g_plant_drive_work, [&](int) { return drive_in_floats(periods, feedback); }, [&](int) { return 8 + 2 * steps; },
+                  [](int) { return (size_t)0; }, [&](int i, float *in) {
+    memcpy(in, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+    in[7] = 0.0f;
+    memcpy(in + off_u, us[i], sizeof(float) * 2 * rows);
+    if (feedback) {
+      memcpy(in + off_x, xs[i], sizeof(float) * 7 * rows);
+      memcpy(in + off_k, hs[i]->ddp.feedback.data(), sizeof(float) * 14 * rows);
+    }
+  });
+  if (rc) return rc;
+  for (int at = 0; at < n; at += kMaxFleet)
+    p.launch(at, std::min(kMaxFleet, n - at), +[](const PlantDriveArgs *h_inst, const PlantDriveArgs *d_inst, int m, hipStream_t S) {
+      return launch_plant_drive_fleet(h_inst, d_inst, nullptr, m, 0, S);
+    }, [&](int i, PlantDriveArgs &a) {
+      plant_drive_fill(hs[i], periods, substeps, feedback, a);
+      const float *in = p.w->d_in + p.in_off[i];
+      float *out = p.w->d_out + p.out_off[i];
+      a.useq_even = a.useq_odd = in + off_u;
+      a.xseq = feedback ? in + off_x : nullptr;
+      a.gains = feedback ? in + off_k : nullptr;
+      a.state_in = in;
+      a.state_out = out;
+      a.applied = out + 8;
+    });
+  rc = p.finish();
+  if (rc) return rc;
+  for (int i = 0; i < n; i++) {
+    const float *o = p.w->h_out + p.out_off[i];
+    memcpy(states_out + (size_t)MPPI_STATE_DIM * i, o, sizeof(float) * kStateDim);
+    if (applied_log && applied_log[i]) memcpy(applied_log[i], o + 8, sizeof(float) * 2 * steps);
+    hs[i]->plant_drive_on_device = 1;
+  }
+  return MPPI_OK;
+}
+
+// a layer list mppi_create accepts; its parameter count
+static bool plant_layers_ok(const int *layers, int n_layers, size_t *num_params)
+{
+  if (!layers || n_layers < 2 || n_layers > MPPI_MAX_LAYERS) return false;
+  if (layers[0] != kNetIn || layers[n_layers - 1] != kNetOut) return false;
+  size_t np = 0;
+  for (int i = 0; i < n_layers; i++)
+    if (layers[i] <= 0 || layers[i] > 256) return false;
+  for (int i = 0; i + 1 < n_layers; i++) np += (size_t)(layers[i] + 1) * layers[i + 1];
+  *num_params = np;
+  return true;
+}
+
+static NetDesc net_desc_of(const int *layers, int n_layers, size_t num_params)
+{
+  NetDesc net{};
+  net.n_layers = n_layers;
+  for (int i = 0; i < 8; i++) net.layers[i] = i < n_layers ? layers[i] : 0;
+  for (int i = 0; i < n_layers; i++) net.max_width = std::max(net.max_width, layers[i]);
+  net.num_params = (int)num_params;
+  return net;
+}
+
 }  // namespace mppi_abi
 
 extern "C" {
+
+int mppi_set_plant_model(mppi_handle *h, const int *layers, int n_layers, const float *theta, size_t n, int negate_yaw_der)
+{
+  if (!h) return MPPI_ERR_INVALID;
+  if (h->basis) return fail(h, MPPI_ERR_INVALID, "a plant model is a network: the handle was created for basis-function dynamics");
+  if (n_layers == 0 && theta == nullptr) {  // cleared: the plant is the handle's own network again (the image's memory is kept)
+    h->have_plant = false;
+    return MPPI_OK;
+  }
+  size_t np = 0;
+  if (!theta || !plant_layers_ok(layers, n_layers, &np)) return fail(h, MPPI_ERR_INVALID, "plant model: the layer list must be 6 .. 4 with widths 1 .. 256");
+  if (n != np) return fail(h, MPPI_ERR_INVALID, "plant model: theta size != NUM_PARAMS of the layer list");
+  const NetDesc net = net_desc_of(layers, n_layers, np);
+  const std::vector<float> th(theta, theta + n);
+  const std::vector<float> img = pack_trace_weights(th, net);
+  HIPCHK(h, ensure_device(h->cfg.device));
+  // no solve state is touched and an armed handle stays armed: the copy goes to the device's batch stream, which no solve of a
+  // single handle waits on, and no device memory is freed
+  hipStream_t S = batch_stream(h->cfg.device);
+  if (!S) return fail(h, MPPI_ERR_HIP, "no batch stream");
+  float *d = h->d_plant_img;
+  if (!d) HIPCHK(h, hipMalloc(reinterpret_cast<void **>(&d), sizeof(float) * kPlantImageMaxFloats));
+  h->d_plant_img = d;
+  hipError_t e = hipMemcpyAsync(d, img.data(), sizeof(float) * img.size(), hipMemcpyHostToDevice, S);
+  if (e == hipSuccess) e = hipStreamSynchronize(S);
+  if (e != hipSuccess) {  // the image may be half written: no plant model rather than a wrong one
+    h->have_plant = false;
+    return fail(h, MPPI_ERR_HIP, "plant model: image copy", e);
+  }
+  h->plant_net = net;
+  h->plant_negate = negate_yaw_der ? 1 : 0;
+  h->plant_theta = th;
+  h->plant_hnet.init(h->plant_net.layers, h->plant_net.n_layers, h->plant_theta.data());
+  h->have_plant = true;
+  return MPPI_OK;
+}
+
+int mppi_debug_plant_model_info(const mppi_handle *h, int *n_layers)
+{
+  if (!h || !n_layers) return MPPI_ERR_INVALID;
+  *n_layers = h->have_plant ? h->plant_net.n_layers : 0;
+  return MPPI_OK;
+}
+
+int mppi_debug_plant_drive_host(const int *layers, int n_layers, const float *theta, size_t n, int negate_yaw_der, float dt,
+                                const float u_lo[MPPI_CONTROL_DIM], const float u_hi[MPPI_CONTROL_DIM], const float x[MPPI_STATE_DIM],
+                                const float *state_seq, const float *control_seq, const float *feedback, int T, int periods, int substeps,
+                                float state_out[MPPI_STATE_DIM], float *applied)
+{
+  size_t np = 0;
+  if (!theta || !u_lo || !u_hi || !x || !control_seq || !state_out || !plant_layers_ok(layers, n_layers, &np) || n != np) return MPPI_ERR_INVALID;
+  if (feedback && !state_seq) return MPPI_ERR_INVALID;
+  if (T < 2 || periods < 1 || periods >= T || substeps < 1 || substeps > kPlantDriveMaxSubsteps || !(dt > 0.0f)) return MPPI_ERR_INVALID;
+  HostNetFma net;
+  net.init(layers, n_layers, theta);
+  plant_drive_host(net_plant(net, negate_yaw_der ? 1 : 0), dt, u_lo, u_hi, x, state_seq, control_seq, feedback, periods, substeps, state_out,
+                   applied);
+  return MPPI_OK;
+}
+
+int mppi_plant_drive_batch(mppi_handle *const *handles, const float *states, const float *const *state_seqs, const float *const *control_seqs,
+                           int n, int periods, int substeps, int feedback, float *states_out, float *const *applied_log)
+{
+  // mppi_nominal_traj_batch's order: every argument, then every handle's readiness, then every pending solve; only then an output
+  if (!handles || !states || !state_seqs || !control_seqs || !states_out || n < 1) return MPPI_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!handles[i] || !state_seqs[i] || !control_seqs[i]) return MPPI_ERR_INVALID;
+    for (int q = 0; q < i; q++)
+      if (handles[q] == handles[i]) return fail(handles[i], MPPI_ERR_INVALID, "the same handle twice in one batch");
+  }
+  if (substeps < 1 || substeps > kPlantDriveMaxSubsteps) return fail(handles[0], MPPI_ERR_INVALID, "plant drive: substeps must be in [1, 16]");
+  for (int i = 0; i < n; i++)
+    if (periods < 1 || periods >= handles[i]->T) return fail(handles[i], MPPI_ERR_INVALID, "plant drive: periods must be in [1, T)");
+  for (int i = 0; i < n; i++)
+    if (!handles[i]->have_nn) return fail(handles[i], MPPI_ERR_STATE, "mppi_set_nn_params has not been called");
+  for (int i = 0; i < n && feedback; i++)
+    if (!handles[i]->have_ddp) return fail(handles[i], MPPI_ERR_STATE, "plant drive with feedback: the handle has no DDP result");
+  for (int i = 0; i < n; i++)
+    if (handles[i]->pending) {
+      const int rc = mppi_synchronize(handles[i]);
+      if (rc) return rc;
+    }
+  if (plant_drive_together(handles, n))
+    return plant_drive_launch(handles, states, state_seqs, control_seqs, n, periods, substeps, feedback, states_out, applied_log);
+  // n host drives; every result is computed before one is delivered (states_out may be `states`)
+  const size_t steps = (size_t)periods * substeps;
+  std::vector<float> xo((size_t)MPPI_STATE_DIM * n), ap(2 * steps * (size_t)n);
+  for (int i = 0; i < n; i++)
+    plant_drive_host_handle(handles[i], states + (size_t)MPPI_STATE_DIM * i, state_seqs[i], control_seqs[i],
+                            feedback ? handles[i]->ddp.feedback.data() : nullptr, periods, substeps, xo.data() + (size_t)MPPI_STATE_DIM * i,
+                            ap.data() + 2 * steps * i);
+  memcpy(states_out, xo.data(), sizeof(float) * xo.size());
+  for (int i = 0; i < n; i++) {
+    if (applied_log && applied_log[i]) memcpy(applied_log[i], ap.data() + 2 * steps * i, sizeof(float) * 2 * steps);
+    handles[i]->plant_drive_on_device = 0;
+  }
+  return MPPI_OK;
+}
+
+int mppi_debug_plant_drive_info(const mppi_handle *h, int *on_device)
+{
+  if (!h || !on_device) return MPPI_ERR_INVALID;
+  *on_device = h->plant_drive_on_device;
+  return MPPI_OK;
+}
 
 int mppi_nominal_and_gains_batch(mppi_handle *const *handles, const float *states, float *const *state_seqs, float *const *control_seqs,
                                  int n)

@@ -167,6 +167,17 @@ struct mppi_handle {
   int nominal_gains_fused = 0;  // the last mppi_nominal_and_gains_batch ran in nominal_gains_fleet_kernel, not as the two calls
   int closed_loop_on_device = 0, closed_loop_ticks = 0;  // the last mppi_closed_loop_ticks_batch: its ticks were enqueued on the device's batch stream with
                                                          // the plant step in plant_fleet_kernel (not the loop of public calls); the ticks it completed
+  // mppi_set_plant_model: the network of the plant that mppi_plant_drive_batch and mppi_closed_loop_sim_batch step -- its layer
+  // list, its parameters, its host twin and its trace image (pack_trace_weights) in d_plant_img, which is allocated once for the
+  // largest image a layer list can have and freed with the handle (so that a change never frees device memory beside an armed
+  // solve).  have_plant == false: the plant is the handle's own network with the handle's negate_yaw_der.
+  bool have_plant = false;
+  NetDesc plant_net{};
+  int plant_negate = 0;
+  std::vector<float> plant_theta;
+  HostNetFma plant_hnet;
+  float *d_plant_img = nullptr;
+  int plant_drive_on_device = 0;  // the last mppi_plant_drive_batch ran in plant_drive_fleet_kernel, not in the host text
   int trace_on_device = 0;  // the last trace ran in the fleet's kernels (mppi_trace_rollouts_batch), not in a launch of the handle's own
   hipStream_t batch_s = nullptr;  // the device's batch stream, looked up once (mppi_compute_control_batch)
   unsigned *d_counter = nullptr;  // [1 + T] arrival counters of the tail kernel
@@ -331,6 +342,8 @@ struct ImageDesc {
 };
 const ImageDesc &image_desc(Image id);  // row id of the table
 inline float *image(const mppi_handle *h, Image id) { return h->img[(int)id].d; }
+// abi_pack.hip: Image::Trace's packing for any network (mppi_set_plant_model packs the plant's with it)
+std::vector<float> pack_trace_weights(const std::vector<float> &theta, const mppi::NetDesc &net);
 int upload_image(mppi_handle *h, Image id);  // packs the image from h->theta and copies it (an image built on request: allocated at the first call)
 int upload_images(mppi_handle *h);           // every image the handle has, and the one the form it asked for by name needs
 int seed_device(mppi_handle *h, uint64_t seed, uint64_t offset);
@@ -455,6 +468,13 @@ extern std::atomic<int> g_host_threads;
 void host_helper_arm();
 // abi_host.hip: the sharing rule of the batched nominal replay (mppi_nominal_traj_batch; the closed loop of a fleet asks it too)
 bool nominal_fleet_together(mppi_handle *const *hs, int n);
+// abi_host.hip: the plant of a handle (mppi_set_plant_model; else the handle's own network) and what of a PlantDriveArgs block is the
+// same for the batched call and the closed loop: the plant's image and layer list, negate_yaw_der, dt / substeps, the handle's
+// limits, the interpolation weights, where the image goes.  The pointers are the caller's.
+const NetDesc &plant_net_of(const mppi_handle *h);
+void plant_drive_fill(const mppi_handle *h, int periods, int substeps, int feedback, PlantDriveArgs &a);
+// the sharing rule of mppi_plant_drive_batch (the closed loop of a fleet asks it too)
+bool plant_drive_together(mppi_handle *const *hs, int n);
 // abi_solve.hip: the host's check behind a closed-loop run on the device (mppi_closed_loop_ticks_batch) over one handle's logs -- etas
 // [n_ticks], controls [n_ticks][stride][2]: the first tick whose eta is below 1 or not finite or whose applied controls are not
 // finite; -1: none

@@ -3,7 +3,8 @@
 // phases (collect, begin_solves, distrust, solve_step, finish_solves: "the phases of a solve" below); three short drivers say
 // how the argument blocks the phases fill reach the device -- enqueue_solve (one handle, its own stream), enqueue_pair (2-4
 // handles, one rollout launch), enqueue_fleet (2-64 handles of a fleet form, three launches).  closed_loop_fleet is enqueue_fleet's
-// tick n_ticks times over with the plant step between two ticks and nothing collected (mppi_closed_loop_ticks_batch).
+// tick n_ticks times over with the plant step between two ticks and nothing collected (mppi_closed_loop_ticks_batch; with a plant of
+// its own under the drive law: mppi_closed_loop_sim_batch).
 #include "abi_internal.hpp"
 
 using namespace mppi;
@@ -1282,10 +1283,14 @@ static bool wait_for_ticks(mppi_handle *const *hs, int n, hipStream_t S)
 }
 
 // n_ticks <= kLoopChunkTicks ticks of a set that is fleet_together and nominal_fleet_together with one iteration, every pending
-// solve collected.  The logs may be NULL as arrays or entry by entry.
-static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, float *const *state_log,
+// solve collected.  The logs may be NULL as arrays or entry by entry.  substeps == 0: mppi_closed_loop_ticks_batch, the plant step in
+// plant_fleet_kernel; substeps >= 1: mppi_closed_loop_sim_batch without feedback on a set that is plant_drive_together as well, the
+// plant in plant_drive_fleet_kernel (`stride` periods of `substeps` steps, the rows of U clamped by the kernel itself).
+static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, int substeps, float *const *state_log,
                              float *const *control_log, float *const *cost_log)
 {
+  const bool sim = substeps > 0;
+  const int per_tick = sim ? stride * substeps : stride;  // applied controls per tick
   mppi_handle *h0 = hs[0];
   hipStream_t S = nullptr;
   if (int rc = use_batch_stream(h0, &S)) return rc;
@@ -1293,8 +1298,8 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
   FleetBlock *fb = fleet_block(dev);
   if (!fb) return fail(h0, MPPI_ERR_HIP, "no argument block for the fleet");
   const FormDesc &fd = form_desc(h0->forced);
-  const LoopLog lg = loop_log(n_ticks, stride);
-  const size_t arg_floats = align4((sizeof(PlantFleetArgs) * (size_t)n + sizeof(float) - 1) / sizeof(float));
+  const LoopLog lg = loop_log(n_ticks, per_tick);
+  const size_t arg_floats = align4(((sim ? sizeof(PlantDriveArgs) : sizeof(PlantFleetArgs)) * (size_t)n + sizeof(float) - 1) / sizeof(float));
   const size_t in_floats = arg_floats + (size_t)8 * n, out_floats = lg.end * (size_t)n;
   if (dev < 0 || dev >= 64) return fail(h0, MPPI_ERR_INVALID, "device out of range");
   // the run's buffers for the whole run; the fleet block only while the run is enqueued: batched solves, replays and DDP passes of
@@ -1315,11 +1320,28 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
   // the plant's argument blocks (sent once) and the state slots behind them
   PlantFleetArgs *pa = reinterpret_cast<PlantFleetArgs *>(w->h_in);
   const PlantFleetArgs *d_pa = reinterpret_cast<const PlantFleetArgs *>(w->d_in);
+  PlantDriveArgs *da = reinterpret_cast<PlantDriveArgs *>(w->h_in);
+  const PlantDriveArgs *d_da = reinterpret_cast<const PlantDriveArgs *>(w->d_in);
   for (int i = 0; i < n; i++) {
     const mppi_handle *h = hs[i];
+    float *o = w->d_out + lg.end * (size_t)i;
+    memcpy(w->h_in + arg_floats + (size_t)8 * i, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
+    w->h_in[arg_floats + (size_t)8 * i + 7] = 0.0f;
+    if (sim) {
+      PlantDriveArgs &a = da[i];
+      a = PlantDriveArgs{};
+      plant_drive_fill(h, stride, substeps, 0, a);
+      a.useq_even = h->d_in;
+      a.useq_odd = loop_swaps(h, stride) ? h->d_in_buf[1 - h->in_cur] : h->d_in;
+      a.clamp_rows = 1;
+      a.scal = h->d_scal;
+      a.state_in = a.state_out = w->d_in + arg_floats + (size_t)8 * i;
+      a.applied = o + lg.u;
+      a.log_x = o + lg.x; a.log_c = o + lg.c; a.log_e = o + lg.e;
+      continue;
+    }
     PlantFleetArgs &a = pa[i];
     a = PlantFleetArgs{};
-    float *o = w->d_out + lg.end * (size_t)i;
     a.wimg = image(h, Image::Trace);
     a.U_even = h->d_in;
     a.U_odd = loop_swaps(h, stride) ? h->d_in_buf[1 - h->in_cur] : h->d_in;
@@ -1332,9 +1354,11 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
     a.dt = h->dt;
     for (int j = 0; j < kControlDim; j++) { a.u_lo[j] = h->u_lo[j]; a.u_hi[j] = h->u_hi[j]; }
     a.net = h->net;
-    memcpy(w->h_in + arg_floats + (size_t)8 * i, states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
-    w->h_in[arg_floats + (size_t)8 * i + 7] = 0.0f;
   }
+  // the plant step behind tick `tick`; ra: the next tick's rollout argument blocks in device memory, or nullptr
+  auto launch_plant = [&](RolloutArgs *ra, int tick) -> hipError_t {
+    return sim ? launch_plant_drive_fleet(da, d_da, ra, n, tick, S) : launch_plant_fleet(pa, d_pa, ra, n, tick, S);
+  };
   hipError_t e = hipMemcpyAsync(w->d_in, w->h_in, sizeof(float) * in_floats, hipMemcpyHostToDevice, S);
   if (e != hipSuccess) return distrust(hs, n, fail(h0, MPPI_ERR_HIP, "closed loop: input copy", e));
   // behind plant step `tick`: the slide of every handle whose slid copy is not simply swapped in (the swap itself is the host's)
@@ -1371,7 +1395,7 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
     e = arg_block_send(fb->args, fleet_bytes(n, fd.fleet_net != nullptr), S);
     unsigned char *dev_blk = fb->args.d;
     // the plant step of the tick before, BEHIND this tick's argument copy: its state lands in the block the rollout reads
-    if (e == hipSuccess && tick > 0) e = launch_plant_fleet(pa, d_pa, reinterpret_cast<RolloutArgs *>(dev_blk), n, tick - 1, S);
+    if (e == hipSuccess && tick > 0) e = launch_plant(reinterpret_cast<RolloutArgs *>(dev_blk), tick - 1);
     if (e == hipSuccess && tick > 0) e = slide_behind_plant();
     if (e == hipSuccess) e = launch_noise_fleet(nd, reinterpret_cast<const NoiseFleetDesc *>(dev_blk + fleet_noise_offset(n)), n, S);
     if (e == hipSuccess)
@@ -1389,7 +1413,7 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
       }
     }
   }
-  e = launch_plant_fleet(pa, d_pa, nullptr, n, n_ticks - 1, S);
+  e = launch_plant(nullptr, n_ticks - 1);
   if (e == hipSuccess) e = slide_behind_plant();
   if (e == hipSuccess) e = hipMemcpyAsync(w->h_out, w->d_out, sizeof(float) * out_floats, hipMemcpyDeviceToHost, S);
   for (int i = 0; i < n && e == hipSuccess; i++)  // the smoothed and slid [U | hist]: what the host's copies become
@@ -1428,7 +1452,7 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
   int bad_tick = -1, bad_handle = -1;
   for (int i = 0; i < n; i++) {
     const float *o = w->h_out + lg.end * (size_t)i;
-    const int t = closed_loop_first_bad_tick(o + lg.e, o + lg.u, n_ticks, stride);
+    const int t = closed_loop_first_bad_tick(o + lg.e, o + lg.u, n_ticks, per_tick);
     if (t >= 0 && (bad_tick < 0 || t < bad_tick)) {
       bad_tick = t;
       bad_handle = i;
@@ -1441,7 +1465,7 @@ static int closed_loop_fleet(mppi_handle *const *hs, float *states, int n, int n
       memcpy(state_log[i], states + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
       memcpy(state_log[i] + 7, o + lg.x + 7, sizeof(float) * 7 * (size_t)good_ticks);
     }
-    if (control_log && control_log[i]) memcpy(control_log[i], o + lg.u, sizeof(float) * 2 * (size_t)stride * good_ticks);
+    if (control_log && control_log[i]) memcpy(control_log[i], o + lg.u, sizeof(float) * 2 * (size_t)per_tick * good_ticks);
     if (cost_log && cost_log[i]) memcpy(cost_log[i], o + lg.c, sizeof(float) * (size_t)good_ticks);
     hs[i]->closed_loop_on_device = 1;
     hs[i]->closed_loop_ticks = good_ticks;
@@ -1494,6 +1518,45 @@ static int closed_loop_reference(mppi_handle *const *hs, float *states, int n, i
       if (control_log && control_log[i]) memcpy(control_log[i] + (size_t)2 * stride * tick, up[i], sizeof(float) * 2 * (size_t)stride);
       if (cost_log && cost_log[i]) cost_log[i][tick] = hs[i]->traj_cost;
       memcpy(s, xp[i] + (size_t)7 * stride, sizeof(float) * kStateDim);
+      if (state_log && state_log[i]) memcpy(state_log[i] + (size_t)7 * (tick + 1), s, sizeof(float) * kStateDim);
+      rc = mppi_slide_control_seq(hs[i], stride);
+      if (rc) return rc;
+      hs[i]->closed_loop_ticks = tick + 1;
+    }
+  }
+  return MPPI_OK;
+}
+
+// mppi_closed_loop_sim_batch's loop of public calls: its definition, and what every set without a device path runs
+static int closed_loop_sim_reference(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, int substeps, int feedback,
+                                     float *const *state_log, float *const *control_log, float *const *cost_log)
+{
+  const size_t per_tick = (size_t)stride * substeps;
+  std::vector<std::vector<float>> xs(n), us(n), ap(n);
+  std::vector<float *> xp(n), up(n), app(n);
+  std::vector<float> s_next((size_t)MPPI_STATE_DIM * n);
+  for (int i = 0; i < n; i++) {
+    xs[i].resize((size_t)hs[i]->T * kStateDim);
+    us[i].resize((size_t)hs[i]->T * kControlDim);
+    ap[i].resize(2 * per_tick);
+    xp[i] = xs[i].data();
+    up[i] = us[i].data();
+    app[i] = ap[i].data();
+    hs[i]->closed_loop_on_device = 0;
+    hs[i]->closed_loop_ticks = 0;
+  }
+  for (int tick = 0; tick < n_ticks; tick++) {
+    int rc = mppi_compute_control_batch(hs, states, n);
+    if (rc == MPPI_OK)
+      rc = feedback ? mppi_nominal_and_gains_batch(hs, states, xp.data(), up.data(), n) : mppi_nominal_traj_batch(hs, states, xp.data(), up.data(), n);
+    if (rc == MPPI_OK) rc = mppi_plant_drive_batch(hs, states, xp.data(), up.data(), n, stride, substeps, feedback, s_next.data(), app.data());
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+      float *s = states + (size_t)MPPI_STATE_DIM * i;
+      if (state_log && state_log[i]) memcpy(state_log[i] + (size_t)7 * tick, s, sizeof(float) * kStateDim);
+      if (control_log && control_log[i]) memcpy(control_log[i] + 2 * per_tick * tick, app[i], sizeof(float) * 2 * per_tick);
+      if (cost_log && cost_log[i]) cost_log[i][tick] = hs[i]->traj_cost;
+      memcpy(s, s_next.data() + (size_t)MPPI_STATE_DIM * i, sizeof(float) * kStateDim);
       if (state_log && state_log[i]) memcpy(state_log[i] + (size_t)7 * (tick + 1), s, sizeof(float) * kStateDim);
       rc = mppi_slide_control_seq(hs[i], stride);
       if (rc) return rc;
@@ -1619,9 +1682,13 @@ int mppi_control_ticks_batch(mppi_handle *const *hs, const float *states, int n,
   return MPPI_OK;
 }
 
-int mppi_closed_loop_ticks_batch(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, float *const *state_log,
-                                 float *const *control_log, float *const *cost_log)
+// mppi_closed_loop_ticks_batch (substeps == 0: the plant is the controller's own model, one step per period) and
+// mppi_closed_loop_sim_batch (substeps >= 1: the handle's plant under the drive law)
+static int closed_loop_entry(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, int substeps, int feedback,
+                             float *const *state_log, float *const *control_log, float *const *cost_log)
 {
+  const bool sim = substeps > 0;
+  const size_t per_tick = sim ? (size_t)stride * substeps : (size_t)stride;
   // mppi_nominal_traj_batch's order: every argument, then every handle's readiness, then pending and armed solves; only then a move
   if (!hs || !states || n < 1 || n_ticks < 1) return MPPI_ERR_INVALID;
   for (int i = 0; i < n; i++) {
@@ -1640,6 +1707,9 @@ int mppi_closed_loop_ticks_batch(mppi_handle *const *hs, float *states, int n, i
   // MPPI_CLOSED_LOOP_DEVICE=0 (tools only, read at every call): the loop of public calls for every set -- tools/fleet_time.py
   // --closed-loop times the two against each other in one process
   if (const char *sw = getenv("MPPI_CLOSED_LOOP_DEVICE"); sw && atoi(sw) == 0) on_device = false;
+  // the plant of its own: without feedback, where the drive shares a launch too; with feedback the loop of public calls
+  if (sim) on_device = on_device && !feedback && plant_drive_together(hs, n);
+  if (!on_device && sim) return closed_loop_sim_reference(hs, states, n, n_ticks, stride, substeps, feedback, state_log, control_log, cost_log);
   if (!on_device) return closed_loop_reference(hs, states, n, n_ticks, stride, state_log, control_log, cost_log);
   std::vector<float *> xl(n, nullptr), ul(n, nullptr), cl(n, nullptr);
   // what the host holds before the call: all of it comes back where a tick turns out bad, in whichever piece of a long run
@@ -1652,10 +1722,10 @@ int mppi_closed_loop_ticks_batch(mppi_handle *const *hs, float *states, int n, i
   for (int at = 0; at < n_ticks; at += kLoopChunkTicks) {  // (a long run: its logs come back chunk by chunk)
     for (int i = 0; i < n; i++) {
       xl[i] = (state_log && state_log[i]) ? state_log[i] + (size_t)7 * at : nullptr;
-      ul[i] = (control_log && control_log[i]) ? control_log[i] + (size_t)2 * stride * at : nullptr;
+      ul[i] = (control_log && control_log[i]) ? control_log[i] + 2 * per_tick * at : nullptr;
       cl[i] = (cost_log && cost_log[i]) ? cost_log[i] + at : nullptr;
     }
-    const int rc = closed_loop_fleet(hs, states, n, std::min(kLoopChunkTicks, n_ticks - at), stride, xl.data(), ul.data(), cl.data());
+    const int rc = closed_loop_fleet(hs, states, n, std::min(kLoopChunkTicks, n_ticks - at), stride, substeps, xl.data(), ul.data(), cl.data());
     for (int i = 0; i < n; i++) hs[i]->closed_loop_ticks += at;
     if (rc) {  // the host's copies go back, and the next solve uploads them (an earlier piece has moved the device copy)
       for (int i = 0; i < n; i++) {
@@ -1669,6 +1739,19 @@ int mppi_closed_loop_ticks_batch(mppi_handle *const *hs, float *states, int n, i
     }
   }
   return MPPI_OK;
+}
+
+int mppi_closed_loop_ticks_batch(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, float *const *state_log,
+                                 float *const *control_log, float *const *cost_log)
+{
+  return closed_loop_entry(hs, states, n, n_ticks, stride, 0, 0, state_log, control_log, cost_log);
+}
+
+int mppi_closed_loop_sim_batch(mppi_handle *const *hs, float *states, int n, int n_ticks, int stride, int substeps, int feedback,
+                               float *const *state_log, float *const *control_log, float *const *cost_log)
+{
+  if (substeps < 1 || substeps > kPlantDriveMaxSubsteps) return MPPI_ERR_INVALID;
+  return closed_loop_entry(hs, states, n, n_ticks, stride, substeps, feedback, state_log, control_log, cost_log);
 }
 
 int mppi_debug_closed_loop_info(const mppi_handle *h, int *on_device, int *ticks)

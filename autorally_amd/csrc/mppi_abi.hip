@@ -44,7 +44,7 @@ void free_all(mppi_handle *h)
 {
   if (!h) return;
   float *fp[] = {h->d_in_buf[0], h->d_in_buf[1], h->d_scal, h->d_noise, h->d_stage, h->d_costs,
-                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_map, h->d_part, h->d_cap, h->d_trace};
+                 h->d_w, h->d_costs_alt, h->d_w_alt, h->d_map, h->d_part, h->d_cap, h->d_trace, h->d_plant_img};
   for (float *p : fp)
     if (p) (void)hipFree(p);
   for (const DeviceImage &im : h->img)

@@ -510,6 +510,38 @@ struct PlantFleetArgs {
 // the new state too -- or nullptr (behind the run's last tick)
 hipError_t launch_plant_fleet(const PlantFleetArgs *h_inst, const PlantFleetArgs *d_inst, RolloutArgs *d_ra, int n, int tick, hipStream_t stream);
 
+// plant_drive_fleet.hip: a plant of its own for a fleet (mppi_plant_drive_batch, mppi_closed_loop_sim_batch) -- `periods` control
+// periods of `substeps` plant steps each on the PLANT's network (mppi_set_plant_model; else the handle's own), driven by the law of
+// include/mppi_hip.h: the nominal controls interpolated between rows lo and lo + 1 in double, optionally the DDP feedback
+// K (x - x_des) in fp32, the handle's clamp, one step of nom_step's text with dt / substeps.  One wave per controller, the argument
+// blocks an array in device memory.  The closed loop sends them ONCE per run and passes the tick with the launch, as
+// plant_fleet_kernel's; the batched call launches with tick 0.
+constexpr int kPlantDriveMaxSubsteps = 16;
+struct PlantDriveArgs {
+  const float *wimg;       // pack_trace_weights of the plant's network
+  const float *useq_even;  // [periods + 1 ..][2] the nominal controls: control_seq rows, or (clamp_rows) the smoothed U of the run's even ticks ...
+  const float *useq_odd;   // ... and of its odd ticks (the batched call: the same pointer)
+  const float *xseq;       // [periods + 1 ..][7] the nominal states; nullptr without feedback
+  const float *gains;      // [periods + 1 ..][2][7] the feedback gains; nullptr without feedback
+  const float *state_in;   // [7] the start state ...
+  float *state_out;        // ... and where the new one goes (the closed loop: the same slot)
+  float *applied;          // [ticks][periods * substeps][2] the applied controls, or nullptr
+  const float *scal;       // closed loop: the tail's scalars ([1] eta, [2] the trajectory cost); nullptr: no log_c / log_e
+  float *log_x;            // closed loop: [ticks + 1][7], row tick + 1 receives the new state; or nullptr
+  float *log_c, *log_e;    // closed loop: [ticks] the trajectory cost and eta
+  int periods, substeps, negate_yaw_der;
+  int feedback;            // apply K (x - x_des)
+  int clamp_rows;          // the rows of useq are the raw U: clamp each before it is used (the closed loop without a replay launch)
+  int img_lds;             // the image is copied to LDS (plant_drive_image_in_lds)
+  float dt_sub;            // dt / (float)substeps
+  float u_lo[2], u_hi[2];
+  double a[kPlantDriveMaxSubsteps];  // a[j] = (double)j / (double)substeps
+  NetDesc net;             // the plant's layer list
+};
+bool plant_drive_image_in_lds(const NetDesc &net);
+// d_ra: as launch_plant_fleet's -- instance i's RolloutArgs::state receives the new state too -- or nullptr
+hipError_t launch_plant_drive_fleet(const PlantDriveArgs *h_inst, const PlantDriveArgs *d_inst, RolloutArgs *d_ra, int n, int tick, hipStream_t stream);
+
 // nominal_gains_fleet.hip: the nominal replay AND the DDP pass that tracks it (mppi_nominal_and_gains_batch) of n <= kMaxFleet
 // independent controllers in one launch, one workgroup per controller: the replay runs on wave 1 while wave 0 runs the pass's
 // initial rollout; the targets never leave the device.

@@ -87,6 +87,10 @@ extern "C" {
 /*    (still 5) + mppi_closed_loop_ticks_batch, mppi_debug_closed_loop_info, mppi_debug_closed_loop_check (closed-loop ticks of a
  *    fleet -- solve, plant step, slide -- enqueued on the device without collecting in between; compatible additions, every call it
  *    equals is unchanged). */
+/*    (still 5) + mppi_set_plant_model, mppi_debug_plant_model_info, mppi_plant_drive_batch, mppi_debug_plant_drive_info,
+ *    mppi_debug_plant_drive_host, mppi_closed_loop_sim_batch (a plant network of its own per handle, stepped at pose rate under the
+ *    reference's interpolated feed-forward and feedback law, for one batched call and inside a closed loop; compatible additions,
+ *    mppi_closed_loop_ticks_batch is unchanged). */
 #define MPPI_ABI_VERSION 5
 #define MPPI_STATE_DIM 7   /* [x, y, yaw, roll, u_x, u_y, yaw_mder]  NeuralNetModel<7,2,3,...> */
 #define MPPI_CONTROL_DIM 2 /* [steering, throttle] */
@@ -513,6 +517,83 @@ int mppi_debug_closed_loop_info(const mppi_handle *h, int *on_device, int *ticks
  * *bad_tick = the first tick whose eta is below 1 or not finite or whose controls are not finite, -1 if there is none.  No device
  * is needed.  MPPI_ERR_INVALID for a NULL argument, n_ticks < 1 or stride < 1. */
 int mppi_debug_closed_loop_check(const float *etas, const float *controls, int n_ticks, int stride, int *bad_tick);
+
+/* A plant of its own.  mppi_closed_loop_ticks_batch steps the controller's own network once per control period, open loop: the
+ * reference's debug_mode self-simulation.  The entries below give every handle a plant that is a DIFFERENT network, stepped
+ * `substeps` times per control period (pose rate), and driven by the reference's interpolated feed-forward and feedback law
+ * (AutorallyPlant::pubControl, autorally_plant.cpp:217-253; SimPlant::controlAt of host/run_control_loop.hpp).
+ *
+ * mppi_set_plant_model: the plant's network -- any layer list mppi_create accepts (first 6, last 4, widths 1..256, at most 8
+ * entries), theta packed as for mppi_set_nn_params, and the plant's own negate_yaw_der.  n_layers == 0 with theta == NULL clears it:
+ * the plant is then the handle's own network with the handle's negate_yaw_der (also the state before the first call).  A
+ * basis-function handle: MPPI_ERR_INVALID.  A wrong layer list or n: MPPI_ERR_INVALID, and the plant is what it was.  The model is
+ * kept as a host network and as a device image (the image plant_fleet_kernel reads); the call touches no solve state, an armed
+ * handle stays armed (the copy uses the device's batch stream: handles armed TOGETHER wait gated on that stream, see
+ * mppi_nominal_traj_batch).  A handle's FIRST model allocates the image's device memory, once and for the largest image a layer list
+ * can have (1.3 MB, freed with the handle): give a handle its first model before arming it, not beside a gated launch.
+ * mppi_debug_plant_model_info: *n_layers = the plant's layer count, 0 without one. */
+int mppi_set_plant_model(mppi_handle *h, const int *layers, int n_layers, const float *theta, size_t n, int negate_yaw_der);
+int mppi_debug_plant_model_info(const mppi_handle *h, int *n_layers);
+/* The drive law.  Inputs per controller: the start state x[7]; a nominal solution state_seq [T][7] and control_seq [T][2] (already
+ * clamped: what the nominal calls deliver); optionally the gains feedback [T][2][7] (mppi_get_feedback_gains' layout); periods P
+ * with 1 <= P < T; substeps m with 1 <= m <= 16; the plant network and its negate_yaw_der; the handle's float dt and its limits.
+ * dt_sub = dt / (float)m, one fp32 division (dt itself at m = 1).  Plant step q = 0 .. P m - 1, lo = q / m, j = q % m, hi = lo + 1,
+ * a = (double)j / (double)m:
+ *   j == 0: nothing is interpolated -- u_ff, x_des and K are row lo (row hi is not read);
+ *   j > 0:  each is (1 - a) v[lo] + a v[hi], evaluated in double as controlAt does; x_des and K are rounded to float, u stays double;
+ *   feedback (only when asked for): du[c] = 0, then for i ascending du[c] = fmaf(K[c][i], x[i] - x_des[i], du[c]) in fp32; if
+ *           neither du is NaN, u[c] += (double)du[c] (the reference's fallback to feed-forward);
+ *   applied control: clamp((float)u[c], u_lo[c], u_hi[c]) with mppi_nominal_traj's clamp and the HANDLE's limits.  The reference
+ *           clamps to +-1; the handle's limits are a deliberate deviation: with them the case m = 1 without feedback and without a
+ *           plant model IS plant_fleet_kernel's step, i.e. the first P rows of mppi_nominal_traj_batch, bit for bit;
+ *   update: one step of mppi_nominal_traj's text on the plant network with dt_sub (the kinematics with fmaf, per neuron the
+ *           k-ascending fmaf chain with the bias added afterwards, tanhf, s = fmaf(sd, dt_sub, s)).
+ * On the host sin / cos of the heading are sinf / cosf; on the device they are the rounded double results -- the one place the two
+ * texts may differ, as in mppi_nominal_traj_batch.
+ *
+ * mppi_plant_drive_batch: the law for handles[n] from states [n][7], with state_seqs / control_seqs what the nominal calls
+ * delivered; states_out [n][7] receives every plant's state after P periods (it may be `states`), applied_log[i] the
+ * [periods * substeps][2] applied controls (the array or an entry may be NULL).  With feedback != 0 the gains are each handle's
+ * current DDP result; a handle without one: MPPI_ERR_STATE.
+ * Order of work and refusals, as in mppi_nominal_traj_batch: every argument is checked first (MPPI_ERR_INVALID: a NULL array other
+ * than applied_log, n < 1, a NULL handle or sequence, a handle listed twice, periods outside [1, min T_i), substeps outside
+ * [1, 16]), then every handle's readiness (MPPI_ERR_STATE), then pending solves are collected; the outputs are written only after
+ * every launch and copy of the call has succeeded.
+ * Sharing rule, as mppi_nominal_traj_batch's: n >= 2 handles of the network model with parameters set, all on one device, run in
+ * plant_drive_fleet_kernel (one wave per controller; more than 64 handles: launches of up to 64; one input copy, one result copy
+ * and one synchronise per call); anything else -- n = 1, a basis-function handle in the set (its plant is its own model), several
+ * devices -- runs the host text per handle.  mppi_debug_plant_drive_info tells which it was (*on_device). */
+int mppi_plant_drive_batch(mppi_handle *const *handles, const float *states /* n x 7 */, const float *const *state_seqs /* [i]: T_i x 7 */,
+                           const float *const *control_seqs /* [i]: T_i x 2 */, int n, int periods, int substeps, int feedback,
+                           float *states_out /* n x 7 */, float *const *applied_log /* [i]: periods x substeps x 2, or NULL */);
+int mppi_debug_plant_drive_info(const mppi_handle *h, int *on_device);
+/* Test hook: the host text of the law for a network given by value -- no handle and no device.  feedback: [T][2][7] or NULL (no
+ * feedback; state_seq may then be NULL too); applied: [periods * substeps][2] or NULL.  MPPI_ERR_INVALID for a NULL argument, a
+ * layer list mppi_create refuses, n != its parameter count, T < 2, periods outside [1, T), substeps outside [1, 16] or dt <= 0. */
+int mppi_debug_plant_drive_host(const int *layers, int n_layers, const float *theta, size_t n, int negate_yaw_der, float dt,
+                                const float u_lo[MPPI_CONTROL_DIM], const float u_hi[MPPI_CONTROL_DIM], const float x[MPPI_STATE_DIM],
+                                const float *state_seq, const float *control_seq, const float *feedback, int T, int periods, int substeps,
+                                float state_out[MPPI_STATE_DIM], float *applied);
+/* Closed-loop ticks of a fleet against that plant.  The call is DEFINED as this loop of public calls, which the library also
+ * contains (its reference and its fall-back):
+ *     for tick in 0 .. n_ticks-1:
+ *         mppi_compute_control_batch(handles, s, n)
+ *         feedback ? mppi_nominal_and_gains_batch(handles, s, xs, us, n) : mppi_nominal_traj_batch(handles, s, xs, us, n)
+ *         mppi_plant_drive_batch(handles, s, xs, us, n, stride, substeps, feedback, s_next, applied)
+ *         log s_i, applied_i, the trajectory cost of handle i;  s = s_next;  mppi_slide_control_seq(handle_i, stride)
+ * control_log[i] is [n_ticks][stride * substeps][2]; the other logs, the post-conditions on every handle, the order of work and the
+ * argument checks are mppi_closed_loop_ticks_batch's, with substeps outside [1, 16] refused as well.
+ * Device path (feedback == 0): the sets that take mppi_closed_loop_ticks_batch's device path AND share the launch of
+ * mppi_plant_drive_batch.  Every tick is enqueued on the device's batch stream and the host waits for none: behind a tick's tail
+ * plant_drive_fleet_kernel reads the device copy of U the tail has just smoothed (it clamps the rows itself: no replay launch is
+ * needed), steps the plant from the controller's device state slot and writes the new state into the next tick's rollout argument
+ * block, exactly as plant_fleet_kernel does.  Failure: mppi_closed_loop_ticks_batch's check behind the run, and its restore.
+ * feedback != 0, and every other set, run the loop above literally, with its bits: a tick whose DDP factorisation fails returns
+ * that call's MPPI_ERR_STATE.  mppi_debug_closed_loop_info reports this entry too.  MPPI_CLOSED_LOOP_DEVICE=0 (tools only) applies. */
+int mppi_closed_loop_sim_batch(mppi_handle *const *handles, float *states /* n x 7, in: start, out: final */, int n, int n_ticks,
+                               int stride, int substeps, int feedback, float *const *state_log /* [i]: (n_ticks+1) x 7, or NULL */,
+                               float *const *control_log /* [i]: n_ticks x (stride x substeps) x 2 (applied), or NULL */,
+                               float *const *cost_log /* [i]: n_ticks trajectory costs, or NULL */);
 
 /* Host threads the library may use for the host-side work of a tick that comes in pairs (mppi_nominal_traj_pair,
  * mppi_compute_feedback_gains_pair): 1 (default) = the caller's thread only (the reference's optimizer thread does everything,

@@ -54,7 +54,18 @@ batch entry is timed twice, interleaved with the per-handle calls: the A/A sprea
 
 Closed-loop ticks of the fleet (solve, plant step, slide): mppi_closed_loop_ticks_batch with all ticks enqueued on the device against
 (r) the reference loop inside the library (the same entry with MPPI_CLOSED_LOOP_DEVICE=0) and (p) the reference loop driven from
-Python; every run from the same start (controls reset, generator reseeded), the ways alternating, the median of three runs each."""
+Python; every run from the same start (controls reset, generator reseeded), the ways alternating, the median of three runs each.
+
+    python tools/fleet_time.py --closed-loop-sim [--n 64] [--K 1920] [--T 100] [--ticks 100] [--net ...] [--variant fleet_multi4]
+
+Closed-loop ticks against a plant of its own (the controller's weights scaled by 1.05) under the drive law: for m in {1, 4} and
+feedback off / on, mppi_closed_loop_sim_batch's first way (the device loop where it has one) against the loop of public calls inside
+the library (MPPI_CLOSED_LOOP_DEVICE=0), alternating in one process, the median of three runs each.
+
+    python tools/fleet_time.py --plant-drive [--n 64] [--T 100] [--ticks 200] [--net ...]
+
+mppi_plant_drive_batch with feedback, the plant's image copied to LDS against the image read from global memory
+(MPPI_PLANT_DRIVE_LDS = 1 / 0), alternating call by call, for one step, one period of four and two periods of four."""
 import argparse
 import json
 import os
@@ -507,6 +518,105 @@ def closed_loop_table(nets, variant=None, n=64, K=1920, T=100, ticks=200):
     return rows
 
 
+def _with_plants(sols, net):
+    """every handle's plant: its own layer list with the weights of a perturbed copy (scaled by 1.05)"""
+    for s in sols:
+        s.set_plant_model(net, np.asarray(s.cfg["theta"], np.float32) * np.float32(1.05), s.cfg["negate_yaw_der"])
+
+
+def closed_loop_sim_ms(net, variant, substeps, feedback, n=64, K=1920, T=100, ticks=100, stride=1, runs=3, warm=10):
+    """-> a row: ms per tick of mppi_closed_loop_sim_batch's device loop and of the loop of public calls inside the library
+    (MPPI_CLOSED_LOOP_DEVICE=0), the median of `runs` runs each, alternating in one process, and what mppi_debug_closed_loop_info says
+    of each.  The plant is the controller's network with its weights scaled by 1.05."""
+    from autorally_amd import capi
+    sols, states = fleet(net, variant, n, K, T)
+    try:
+        _with_plants(sols, net)
+
+        def library(device, count):
+            for i, s in enumerate(sols):
+                s.reset_controls()
+                s.seed(1000 + i, 0)
+            st = [x.copy() for x in states]
+            os.environ["MPPI_CLOSED_LOOP_DEVICE"] = "1" if device else "0"
+            try:
+                t0 = time.perf_counter()
+                capi.closed_loop_sim_batch(sols, st, count, stride, substeps, feedback)
+                return (time.perf_counter() - t0) / count, sols[0].debug_closed_loop_info()
+            finally:
+                os.environ.pop("MPPI_CLOSED_LOOP_DEVICE", None)
+
+        library(True, warm)
+        td, tr, info_d, info_r = [], [], None, None
+        for _ in range(runs):
+            d, info_d = library(True, ticks)
+            r, info_r = library(False, ticks)
+            td.append(d)
+            tr.append(r)
+        row = {"net": "-".join(map(str, net)), "variant": variant, "n": n, "K": K, "T": T, "ticks": ticks, "stride": stride,
+               "substeps": substeps, "feedback": int(bool(feedback))}
+        row["device_ms"], row["reference_ms"] = (1e3 * float(np.median(t)) for t in (td, tr))
+        row["device_runs_ms"], row["reference_runs_ms"] = [1e3 * t for t in td], [1e3 * t for t in tr]
+        row["on_device"], row["reference_on_device"] = info_d[0], info_r[0]
+        return row
+    finally:
+        for s in sols:
+            s.close()
+
+
+def closed_loop_sim_table(nets, variant=None, n=64, K=1920, T=100, ticks=100):
+    rows = []
+    for net in nets:
+        v = variant or ("fleet_multi4" if net == [6, 32, 32, 4] else "fleet16")
+        for substeps in (1, 4):
+            for feedback in (False, True):
+                row = closed_loop_sim_ms(net, v, substeps, feedback, n, K, T, ticks)
+                rows.append(row)
+                print("FLEET CLOSED LOOP SIM n=%d K=%d T=%d net=%s %s m=%d feedback=%d, %d ticks: first way %.4f ms per tick (on_device %d)  loop "
+                      "of public calls in the library %.4f ms;  ratio %.2f" % (n, K, T, row["net"], v, substeps, feedback, ticks, row["device_ms"],
+                                                                              row["on_device"], row["reference_ms"], row["reference_ms"] / row["device_ms"]),
+                      flush=True)
+    return rows
+
+
+def plant_drive_ms(net, n=64, T=100, periods=1, substeps=4, feedback=True, calls=200, warm=10):
+    """-> a row: ms per call of mppi_plant_drive_batch with every image copied to LDS and with every image in global memory
+    (MPPI_PLANT_DRIVE_LDS = 1 / 0), the median of `calls` calls each, alternating in blocks of ten."""
+    from autorally_amd import capi
+    sols, states = fleet(net, "auto", n, 64, T)
+    try:
+        _with_plants(sols, net)
+        seqs = capi.nominal_and_gains_batch(sols, states)
+        out = None
+        times = {"1": [], "0": []}
+        for c in range(warm + calls):
+            for sw in ("1", "0"):
+                os.environ["MPPI_PLANT_DRIVE_LDS"] = sw
+                t0 = time.perf_counter()
+                out = capi.plant_drive_batch(sols, states, seqs, periods, substeps, feedback, outputs=out)
+                if c >= warm:
+                    times[sw].append(time.perf_counter() - t0)
+        os.environ.pop("MPPI_PLANT_DRIVE_LDS", None)
+        return {"net": "-".join(map(str, net)), "n": n, "T": T, "periods": periods, "substeps": substeps, "feedback": int(bool(feedback)),
+                "lds_ms": 1e3 * float(np.median(times["1"])), "global_ms": 1e3 * float(np.median(times["0"])),
+                "on_device": sols[0].debug_plant_drive_info()}
+    finally:
+        os.environ.pop("MPPI_PLANT_DRIVE_LDS", None)
+        for s in sols:
+            s.close()
+
+
+def plant_drive_table(nets, n=64, T=100, calls=200):
+    rows = []
+    for net in nets:
+        for periods, substeps in ((1, 1), (1, 4), (2, 4)):
+            row = plant_drive_ms(net, n, T, periods, substeps, True, calls)
+            rows.append(row)
+            print("FLEET PLANT DRIVE n=%d T=%d net=%s P=%d m=%d feedback=1 (on_device %d): image in LDS %.4f ms per call, in global memory %.4f ms" % (
+                n, T, row["net"], periods, substeps, row["on_device"], row["lds_ms"], row["global_ms"]), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="*", default=None, help="handles (default 16; --mixed: 4 16 64, one row each)")
@@ -529,10 +639,20 @@ def main():
     ap.add_argument("--closed-loop", action="store_true", help="closed-loop ticks of the fleet instead: all ticks enqueued on the device "
                     "against the reference loop inside the library and from Python (mppi_closed_loop_ticks_batch)")
     ap.add_argument("--variant", default=None, help="--closed-loop: the fleet form (default fleet_multi4 for 6-32-32-4, else fleet16)")
+    ap.add_argument("--closed-loop-sim", action="store_true", help="closed-loop ticks against a plant of its own instead: the device loop "
+                    "against the loop of public calls inside the library, m in {1, 4}, feedback off / on (mppi_closed_loop_sim_batch)")
+    ap.add_argument("--plant-drive", action="store_true", help="the batched plant drive instead: the plant's image in LDS against the image "
+                    "in global memory (mppi_plant_drive_batch)")
     a = ap.parse_args()
     from autorally_amd import build as B
     B.build()
     parse = lambda names: [[int(x) for x in s.split("-")] for s in names]  # noqa: E731
+    if a.closed_loop_sim:
+        print(json.dumps(closed_loop_sim_table(parse(a.net), a.variant, a.n[0] if a.n else 64, a.K or 1920, a.T, min(a.ticks, 100))))
+        return
+    if a.plant_drive:
+        print(json.dumps(plant_drive_table(parse(a.net), a.n[0] if a.n else 64, a.T, a.ticks)))
+        return
     if a.closed_loop:
         print(json.dumps(closed_loop_table(parse(a.net), a.variant, a.n[0] if a.n else 64, a.K or 1920, a.T, a.ticks)))
         return
